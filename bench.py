@@ -12,9 +12,15 @@ wave slot; P=1 is the literal single-pair C2 case, which runs on the chained str
 wavefronts and is reported next to the batch number as `single_pair`).  PA_SLICE=0 runs the batch on the strip kernels of
 rounds 1-5 (pair_kernel<8>: 130 TCUPS).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: set-up, W warm-up steps, K timed steps, one result line (`value` in GCUPS and
+`ms_per_step`, the wall time of one timed step).  `--dump-outputs DIR` writes what the last timed step returned, the edit
+distance of every pair, to DIR/costs.npy (float64; a fixed seeded sample with its indices beyond 2^21 pairs).  `--full` adds
+every other leg (C3, C4, C5, the batched A*PA2 legs, banded, single pair, PCIe-inclusive, the CPU baselines, the C4
+sharding legs) and the regression check against profiles/bench_reference.json; the `--no-*` options switch legs of `--full` off.
 
 One process per GPU; pairs are independent, so ranks shard the batch with no data-path collective
 (weak scaling: every rank aligns its own `--pairs` pairs).  torch is used only for
@@ -84,6 +90,33 @@ def spread(xs):
             "rel_spread": round((xs[-1] - xs[0]) / med, 4) if med else 0.0}
 
 
+DUMP_MAX_VALUES = 1 << 21  # per array: costs.npy and costs_index.npy stay within 16 MiB each
+
+
+def dump_costs(out_dir: str, costs, name: str = "costs") -> None:
+    """DIR/<name>.npy: the edit distances the timed path returned, as float64 (exact for int32).  A batch of more than
+    DUMP_MAX_VALUES pairs writes a fixed seeded sample of them and DIR/<name>_index.npy with the pairs' indices."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    vals = np.asarray(costs, dtype=np.float64)
+    if vals.size > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.default_rng(20240601).choice(vals.size, DUMP_MAX_VALUES, replace=False))
+        np.save(d / f"{name}_index.npy", idx.astype(np.float64))
+        vals = vals[idx]
+    np.save(d / f"{name}.npy", vals)
+
+
+def generate_pairs(generate_pair, n: int, div: float, seeds, threads: int):
+    """generate_pair(n, div, seed) for every seed, in order, on `threads` host threads (numpy releases the GIL in its array
+    operations): the same bytes as a plain loop, in a fraction of its time for the 8192 x 100 kbp of the headline."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        return list(ex.map(lambda s: generate_pair(n, div, seed=s), seeds))
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -92,6 +125,10 @@ def parse_args():
     ap.add_argument("--pairs", type=int, default=8192, help="independent pairs per GPU per step")
     ap.add_argument("--seq-len", dest="n", type=int, default=100_000, help="sequence length (bp)")
     ap.add_argument("--div", type=float, default=0.05, help="divergence (edit rate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's edit distances to DIR/costs.npy (float64) for output-for-output comparisons of builds")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg besides the headline (engine, batched A*PA2, C4, C5, banded, CPU baselines, ...) and the regression check")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-single-pair", action="store_true")
     ap.add_argument("--no-c4", action="store_true", help="skip the batched alignment-with-traceback leg")
@@ -151,7 +188,7 @@ def main():
         torch.cuda.synchronize()
 
     # ---- synthetic input (seed = global pair index + 1), resident in HBM before timing ----
-    pairs = [generate_pair(args.n, args.div, seed=rank * args.pairs + i + 1) for i in range(args.pairs)]
+    pairs = generate_pairs(generate_pair, args.n, args.div, [rank * args.pairs + i + 1 for i in range(args.pairs)], quota // world)
     batch = pa.Batch(pairs)
     st = batch.stats()
     shape = batch.shape()
@@ -176,11 +213,13 @@ def main():
         checksum = int(chk.item())
     else:
         checksum = int(costs.astype("int64").sum())
+    if args.dump_outputs:  # (every rank its own pairs)
+        dump_costs(args.dump_outputs, costs, "costs" if world == 1 else f"costs_rank{rank}")
 
     # ---- C4 strong scaling (BASELINE configs[3]: "10 000 x 10 kbp sharded across the GPUs"): every rank aligns its LPT shard with
     #      traceback on its GPU, one tensor gather of costs + one of CIGAR bytes; total work fixed as N grows ----
     c4_sharded = None
-    if not args.no_c4_sharded:
+    if args.full and not args.no_c4_sharded:
         from astar_pairwise_aligner_amd.sharding import sharded_align
 
         divs = (0.01, 0.05, 0.10, 0.15)
@@ -414,7 +453,7 @@ def main():
         noise["c4_sharded.pairs_per_sec"] = c4_sharded.get("ms_repetitions", {}).get("rel_spread", 0.0)
 
     # ---- the literal single-pair C2 case (latency bound) ----
-    if not args.no_single_pair and args.pairs != 1:
+    if args.full and not args.no_single_pair and args.pairs != 1:
         b1 = pa.Batch(pairs[:1])
         b1.run()
         best = 1e9
@@ -430,7 +469,7 @@ def main():
         b1.close()
 
     # ---- banded C2: the same pairs inside the diagonal band of the expected divergence (GapGap domain), exact costs ----
-    if not args.no_banded and world == 1:
+    if args.full and not args.no_banded and world == 1:
         t = time.perf_counter()
         bb = pa.Batch(pairs, band=args.div + 0.01)
         bcosts, _ = bb.run()
@@ -455,7 +494,7 @@ def main():
         bb.close()
 
     # ---- C4 (BASELINE configs[3]): 10 000 x 10 kbp, 1-15 % mixed divergence, cost AND CIGAR on the GPU ----
-    if not args.no_c4 and world == 1:
+    if args.full and not args.no_c4 and world == 1:
         divs = (0.01, 0.05, 0.10, 0.15)
         c4 = [generate_pair(10_000, divs[i % 4], seed=1_000_000 + i) for i in range(args.c4_pairs)]
         bt = pa.Batch(c4, trace=True)
@@ -494,7 +533,7 @@ def main():
             out["c4_batch_align"]["dt_trace_kernel_ms"] = f"failed: {e}"
 
     # ---- PCIe-inclusive rate of the headline workload: host buffers -> device layout -> one pass (never `value`) ----
-    if world == 1:
+    if args.full and world == 1:
         t = time.perf_counter()
         bp = pa.Batch(pairs)
         bp.run()
@@ -505,7 +544,7 @@ def main():
     # ---- C3 (BASELINE configs[2]): ONE 100 kbp pair, A*PA2 with traceback through pa_align (the drop-in path).  `simple` runs as
     #      one persistent launch per band-doubling pass with the band logic in the kernel (csrc/sweep_wave.hpp); `full` (GCSH +
     #      pruning + incremental doubling: host-side heuristic) runs one launch per 256-column block ----
-    if not args.no_engine and world == 1:
+    if args.full and not args.no_engine and world == 1:
         import oracle as _orc
 
         a3, b3 = generate_pair(100_000, 0.05, seed=1)
@@ -614,7 +653,7 @@ def main():
             assert got[:50] == want, "drop-in loop: GPU and CPU-kernel engine disagree"
 
     # ---- C5 (BASELINE configs[4]): ONE 10 Mbp x 10 Mbp pair, 5 %, doubling-band A*PA2 (`simple`), traceback off, through pa_align ----
-    if not args.no_c5 and world == 1:
+    if args.full and not args.no_c5 and world == 1:
         a5, b5 = generate_pair(10_000_000, 0.05, seed=1)
         al5 = pa.AstarPa2Params.simple().make_aligner(False)
         t = time.perf_counter()
@@ -632,7 +671,7 @@ def main():
     # ---- batched A*PA2 (pa_batch_create_params): AstarPa2Params::simple() for many pairs, ONE wavefront per pair runs the whole band
     #      search, the device traceback walks the banded blocks.  Cost, CIGAR and statistics are what a loop over pa_align returns
     #      (tests/test_gpu_apa2_batch.py); here the rates, and a sample checked against the CPU-kernel engine ----
-    if not args.no_apa2 and world == 1:
+    if args.full and not args.no_apa2 and world == 1:
         import oracle as _orc
 
         divs = (0.01, 0.05, 0.10, 0.15)
@@ -740,7 +779,7 @@ def main():
             del c3a
 
     # ---- CPU baseline: the AVX2 port of the reference's SIMD schedule, 1 core, bounded sample ----
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle
 
         a0, b0 = pairs[0]
@@ -874,44 +913,45 @@ def main():
         except Exception as e:  # a malformed summary must not break the bench line
             out["roofline"]["traffic_note"] = f"pmc summary unreadable: {e}"
 
-    # ---- regressions: every leg against the reference line (profiles/bench_reference.json: the last committed bench line) ----
-    try:
-        ref_path = ROOT / "profiles" / "bench_reference.json"
-        ref = json.loads(ref_path.read_text())
-        watch = [("value", True), ("single_pair.ms", False), ("banded.pairs_per_sec", True), ("c4_batch_align.pairs_per_sec", True),
-                 ("c4_batch_align.forward_kernel_ms", False), ("c4_batch_align.trace_kernel_ms", False), ("c4_batch_align.dt_trace_kernel_ms", False),
-                 # (the kernel times of the C4 A*PA2 legs are spans over four overlapping chunks since round 4: not comparable, not watched)
-                 ("c4_astarpa2_simple.pairs_per_sec", True), ("c4_astarpa2_simple.c_abi_pairs_per_sec", True),
-                 ("c4_astarpa2_full.pairs_per_sec", True), ("c3_batch_512.pairs_per_sec", True), ("c3_batch_4096.pairs_per_sec", True),
-                 ("c3_batch_4096_full.pairs_per_sec", True), ("c3_engine.simple.ms", False), ("c3_engine.full.ms", False), ("c5.seconds", False),
-                 ("dropin_loop.pairs_per_sec", True), ("dropin_loop.threads8_pairs_per_sec", True), ("c4_sharded.pairs_per_sec", True),
-                 ("pcie_inclusive_gcups", True)]
+    # ---- regressions (--full): every leg against the reference line (profiles/bench_reference.json: the last committed bench line) ----
+    if args.full:
+        try:
+            ref_path = ROOT / "profiles" / "bench_reference.json"
+            ref = json.loads(ref_path.read_text())
+            watch = [("value", True), ("single_pair.ms", False), ("banded.pairs_per_sec", True), ("c4_batch_align.pairs_per_sec", True),
+                     ("c4_batch_align.forward_kernel_ms", False), ("c4_batch_align.trace_kernel_ms", False), ("c4_batch_align.dt_trace_kernel_ms", False),
+                     # (the kernel times of the C4 A*PA2 legs are spans over four overlapping chunks since round 4: not comparable, not watched)
+                     ("c4_astarpa2_simple.pairs_per_sec", True), ("c4_astarpa2_simple.c_abi_pairs_per_sec", True),
+                     ("c4_astarpa2_full.pairs_per_sec", True), ("c3_batch_512.pairs_per_sec", True), ("c3_batch_4096.pairs_per_sec", True),
+                     ("c3_batch_4096_full.pairs_per_sec", True), ("c3_engine.simple.ms", False), ("c3_engine.full.ms", False), ("c5.seconds", False),
+                     ("dropin_loop.pairs_per_sec", True), ("dropin_loop.threads8_pairs_per_sec", True), ("c4_sharded.pairs_per_sec", True),
+                     ("pcie_inclusive_gcups", True)]
 
-        def dig(d, path):
-            for k in path.split("."):
-                d = d[k]
-            return float(d)
+            def dig(d, path):
+                for k in path.split("."):
+                    d = d[k]
+                return float(d)
 
-        regs = []
-        for path, higher in watch:
-            try:
-                was, now = dig(ref, path), dig(out, path)
-            except (KeyError, TypeError, ValueError):
-                continue
-            worse = (was - now) / was if higher else (now - was) / was
-            # a leg that was repeated fires only beyond its own run-to-run spread (host-bound legs: 10-30 %); the others beyond 5 %
-            # (the end-to-end rates of the batched legs include the host's creation of 10 000 Python strings: 5-8 % from run to run)
-            host_bound = path.startswith(("c4_astarpa2_", "c3_batch_", "c4_batch_align.pairs", "pcie_inclusive"))
-            if path == "c5.seconds":
-                host_bound = True  # (twelve pipelined passes of one pair, a single run: 1.5-1.8 s from run to run, profiles/README.md)
-            limit = max((0.15 if path == "c5.seconds" else 0.10) if host_bound else 0.05, 1.25 * noise.get(path, 0.0))
-            if worse > limit:
-                regs.append({"leg": path, "reference": was, "now": now, "worse_by_pct": round(100 * worse, 1), "limit_pct": round(100 * limit, 1)})
-        out["regressions"] = regs
-        out["regressions_noise"] = {k: round(v, 4) for k, v in sorted(noise.items())}
-        out["regressions_reference"] = ref.get("_from", "profiles/bench_reference.json")
-    except Exception as e:  # (reporting only)
-        out["regressions"] = f"no reference line: {e}"
+            regs = []
+            for path, higher in watch:
+                try:
+                    was, now = dig(ref, path), dig(out, path)
+                except (KeyError, TypeError, ValueError):
+                    continue
+                worse = (was - now) / was if higher else (now - was) / was
+                # a leg that was repeated fires only beyond its own run-to-run spread (host-bound legs: 10-30 %); the others beyond 5 %
+                # (the end-to-end rates of the batched legs include the host's creation of 10 000 Python strings: 5-8 % from run to run)
+                host_bound = path.startswith(("c4_astarpa2_", "c3_batch_", "c4_batch_align.pairs", "pcie_inclusive"))
+                if path == "c5.seconds":
+                    host_bound = True  # (twelve pipelined passes of one pair, a single run: 1.5-1.8 s from run to run, profiles/README.md)
+                limit = max((0.15 if path == "c5.seconds" else 0.10) if host_bound else 0.05, 1.25 * noise.get(path, 0.0))
+                if worse > limit:
+                    regs.append({"leg": path, "reference": was, "now": now, "worse_by_pct": round(100 * worse, 1), "limit_pct": round(100 * limit, 1)})
+            out["regressions"] = regs
+            out["regressions_noise"] = {k: round(v, 4) for k, v in sorted(noise.items())}
+            out["regressions_reference"] = ref.get("_from", "profiles/bench_reference.json")
+        except Exception as e:  # (reporting only)
+            out["regressions"] = f"no reference line: {e}"
 
     print(json.dumps(out))
     batch.close()

@@ -221,7 +221,7 @@ def test_bench_two_rank_code_path_dry_run(tmp_path):
     env = dict(os.environ, PA_BENCH_DRY_MULTI="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29617", str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "8",
-           "--seq-len", "20000", "--no-cpu-baseline", "--no-single-pair", "--no-c4", "--no-banded", "--c4-pairs", "300", "--c4-strong-pairs", "900"]
+           "--seq-len", "20000", "--full", "--no-cpu-baseline", "--no-single-pair", "--no-c4", "--no-banded", "--c4-pairs", "300", "--c4-strong-pairs", "900"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -242,3 +242,33 @@ def test_bench_two_rank_code_path_dry_run(tmp_path):
     assert sum(t["pairs"] for t in cs["rank_timing_s"]) == 900
     assert cs["weak"]["scaling"] == "weak" and cs["weak"]["n_gpus"] == 2 and cs["weak"]["pairs_per_sec"] > 0 and cs["weak"]["ms_repetitions"]["reps"] == 3
     assert cs["astarpa2_simple"]["pairs"] == 900
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path, oracle):
+    """A plain bench.py run is the headline alone: the result line's fields, `steps` timed steps, no other leg, and with
+    --dump-outputs the last timed step's edit distances in DIR/costs.npy (float64), equal to the oracle's for the same seeded pairs."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    from astar_pairwise_aligner_amd.generate import generate_pair
+
+    root = Path(__file__).resolve().parent.parent
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "40", "--seq-len", "3000",
+           "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["unit"] == "GCUPS" and j["higher_is_better"] is True and j["dtype"] == "u32" and j["value"] > 0
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    for leg in ("single_pair", "banded", "c4_batch_align", "pcie_inclusive_gcups", "c3_engine", "dropin_loop", "c5", "c4_astarpa2_simple",
+                "cpu_baseline", "cpu_baseline_nproc", "c4_sharded", "regressions"):
+        assert leg not in j, leg
+    got = np.load(tmp_path / "dump" / "costs.npy")
+    assert got.dtype == np.float64 and got.shape == (40,)
+    pairs = [generate_pair(3000, 0.05, seed=i + 1) for i in range(40)]
+    assert got.tolist() == [float(oracle.levenshtein(a, b)) for a, b in pairs]
+    assert int(got.sum()) == j["config"]["cost_checksum"]

@@ -1,10 +1,13 @@
-mkdir -p gpurun_out
-timeout 1500 python -m pytest tests -m gpu -x -q > gpurun_out/r06c_gpu_suite.log 2>&1; echo "pytest rc=$?"
-tail -5 gpurun_out/r06c_gpu_suite.log
-( time python bench.py > gpurun_out/r06c_bench_line.json 2> gpurun_out/r06c_bench.err ) 2>&1 | tail -4
-python - <<'PY'
-import json
-j=json.loads(open('gpurun_out/r06c_bench_line.json').read().strip().splitlines()[-1])
+#!/bin/bash
+# The GPU suite and one full bench line, with the figures worth a glance.   bash tools/_health.sh <out dir>
+OUT=${1:?usage: bash tools/_health.sh <out dir>}
+mkdir -p "$OUT"
+timeout 1500 python -m pytest tests -m gpu -x -q > "$OUT/gpu_suite.log" 2>&1; echo "pytest rc=$?"
+tail -5 "$OUT/gpu_suite.log"
+( time python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err" ) 2>&1 | tail -4
+python - "$OUT/bench_line.json" <<'PY'
+import json, sys
+j=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(j['value'], j['ms_per_step'], j['roofline'].get('frac'))
 print(json.dumps(j.get('c4_sharded'))[:1500])
 print(json.dumps(j.get('dropin_loop'))[:800])

@@ -13,5 +13,5 @@ rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD
 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $OUT/lds -o lds -- $CMD > $OUT/lds.log 2>&1
 python tools/pmc_summary.py $OUT
 # the engine legs (C3 presets, drop-in loop, C5 sweep) under the kernel trace: per-kernel time of sweep_kernel & co
-ENG="python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-single-pair --no-c4 --no-banded --no-c4-sharded"
+ENG="python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-single-pair --no-c4 --no-banded --no-c4-sharded"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/engine_trace -o engine -- $ENG > $OUT/engine_trace.log 2>&1

@@ -16,8 +16,8 @@ PA_APA2_PRESET=simple bash tools/pmc_apa2.sh > $OUT/pmc_apa2_simple.log 2>&1
 cp gpurun_out/pmc_apa2_simple/summary.json $OUT/pmc_apa2_simple_summary.json
 # the bench line with the fresh counters in place (bench.py reads profiles/pmc_latest.json)
 cp gpurun_out/pmc/summary.json profiles/pmc_latest.json
-python bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -o bench -- python bench.py --no-cpu-baseline > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_rocprof.err
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -o bench -- python bench.py --full --no-cpu-baseline > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_rocprof.err
 cp $OUT/bench_trace/*kernel_stats.csv $OUT/bench_kernel_stats.csv 2>/dev/null
 rm -rf $OUT/bench_trace gpurun_out/pmc/*/ gpurun_out/pmc_apa2_*/*/ 2>/dev/null
 ls -la $OUT
