@@ -223,7 +223,7 @@ int run(Plan* p, hipStream_t s, const uint32_t* d_codes, const uint64_t* d_prof,
         }
         (void)hipFree(dbg);
     }
-    hipLaunchKernelGGL(slice_score_kernel, dim3(G, getenv("PA_SCORE_ONE") ? 1u : (p->max_row_blocks * 256u + kScoreSpan - 1) / kScoreSpan), dim3(64), 0, s, p->d_groups.as<SliceGroup>(), p->d_spairs.as<SlicePair>(), p->d_V.as<uint2>(), d_costs);
+    hipLaunchKernelGGL(slice_score_kernel, dim3(G, (p->max_row_blocks * 256u + kScoreSpan - 1) / kScoreSpan), dim3(64), 0, s, p->d_groups.as<SliceGroup>(), p->d_spairs.as<SlicePair>(), p->d_V.as<uint2>(), d_costs);
     if (!hip_ok(hipGetLastError(), "slice_score_kernel")) return PA_E_HIP;
     return 0;
 }
