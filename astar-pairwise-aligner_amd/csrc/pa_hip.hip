@@ -1166,6 +1166,15 @@ int search_out(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t 
     }
     const size_t w = (plen + 63) / 64, n = tlen;
     if (const int rc = search_profile(pattern, plen, unmatched_cost, prof, v0)) return rc;
+    if (w == 0) {  // no rows: search_rect launches nothing, so the text is checked here (profile.rs:29-38 rejects it as well)
+        for (size_t i = 0; i < n; ++i) {
+            const uint8_t ch = text[i] & 0xDF;
+            if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') {
+                set_error("text must be actgACTG only");
+                return PA_E_INVALID_BASE;
+            }
+        }
+    }
     std::vector<uint64_t> v(v0);
     std::vector<uint8_t> hrow;
     if (const int rc = search_rect(text, n, prof, w, v, hrow, nullptr)) return rc;
@@ -1218,10 +1227,12 @@ extern "C" int pa_search_trace(const uint8_t* pattern, size_t plen, const uint8_
     std::vector<uint64_t> prof, v0;
     if (const int rc = search_out(pattern, plen, text, tlen, unmatched_cost, out, prof, v0)) return rc;
     const size_t w = (plen + 63) / 64;
-    if (idx >= out.size() || w == 0) {
+    if (idx >= out.size()) {
         set_error("pa_search_trace: idx out of range");
         return PA_E_ARG;
     }
+    // An empty pattern (w == 0) goes through the general path as in the reference: width 0, an empty re-fill whose cost 0 is
+    // the target, no step -- "" and [(idx, 0)].
     // idx_to_pos, search.rs:105-115
     int64_t pi, pj;
     if (idx <= tlen) {

@@ -84,7 +84,8 @@ int pa_search(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t t
  * (FILL variant of the scatter-profile strip kernel, width = 2|pattern| doubling) and walked back on the host in the
  * reference's order: matches, then 'D' (one text character), 'I' (one pattern character), 'X'.
  * *cigar_out: malloc'ed "=I4=X=" string; *path_out: malloc'ed (text index, pattern index) pairs from the start of the
- * alignment to its end, *npos_out of them.  Release both with free(). */
+ * alignment to its end, *npos_out of them.  Release both with free().  An empty pattern gives "" and the one position
+ * (idx, 0), as the reference does; idx > |pattern| + |text| and an unmatched_cost outside [0, 1] are PA_E_ARG. */
 int pa_search_trace(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t tlen, float unmatched_cost, size_t idx,
                     char** cigar_out, int32_t** path_out, size_t* npos_out);
 

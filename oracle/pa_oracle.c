@@ -267,7 +267,7 @@ int pa_or_search_trace(const uint8_t* pattern, size_t plen, const uint8_t* text,
     pa_v_t* fill = NULL;
     uint8_t* ops = NULL;   /* one op per step, end -> start */
     int32_t* poss = NULL;  /* (i, j) per visited position, end -> start */
-    if (idx > plen + tlen || w == 0) goto done;
+    if (idx > plen + tlen) goto done; /* an empty pattern gives "" and [(idx, 0)]: width 0, no step */
     if (pa_or_search(pattern, plen, text, tlen, unmatched_cost, out) != 0) goto done;
     for (size_t i = 0; i < tlen; ++i) t[i] = (uint8_t)scatter_char(text[i]);
     for (size_t j = 0; j < plen; ++j) {
