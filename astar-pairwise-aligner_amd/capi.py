@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "pa_align", "pa_batch_align_multi", "pa_batch_create_trace_params",
     "pa_bp_ctx_create", "pa_bp_ctx_compute", "pa_bp_ctx_fill", "pa_bp_ctx_destroy",
     "pa_batch_create_params", "pa_batch_pair_stats", "pa_runtime_hints", "pa_batch_align_multi_params", "pa_release_pools", "pa_align_file_params", "pa_batch_params_supported", "pa_alloc_cache_stats", "pa_free_cigars",
-    "pa_batch_full_info", "pa_batch_rdv_stats", "pa_combine_stats", "pa_params_nw", "pa_params_simple", "pa_params_full", "pa_debug_gcsh_probe", "pa_debug_gcsh_matches", "pa_batch_window_retries", "pa_batch_window_retry_bytes",
+    "pa_batch_full_info", "pa_batch_rdv_stats", "pa_combine_stats", "pa_params_nw", "pa_params_simple", "pa_params_full", "pa_debug_gcsh_probe", "pa_debug_gcsh_matches", "pa_debug_strip", "pa_batch_window_retries", "pa_batch_window_retry_bytes",
     "pa_batch_slice_info", "pa_set_reference_cost_only",
 ]
 
@@ -216,6 +216,50 @@ def gcsh_matches(a: bytes, b: bytes, k: int, p: int) -> list[tuple[int, int]]:
     if n < 0:
         raise PaError(f"pa_debug_gcsh_matches rc={n}: {last_error()}")
     return [tuple(x) for x in out[:n].tolist()]
+
+
+class _StripProbeJob(C.Structure):
+    _fields_ = [("a", C.c_void_p), ("a_len", C.c_size_t), ("b", C.c_void_p), ("b_len", C.c_size_t)] + [
+        (f, C.c_int32) for f in ("col0", "n", "word0", "nlanes", "tap", "fill_word0", "fill_stride", "hin_is_hout")
+    ] + [("v", C.c_void_p), ("hin", C.c_void_p), ("values", C.c_void_p), ("hout", C.c_void_p), ("sum", C.c_int32)]
+
+
+STRIP_DUAL, STRIP_SINGLE, STRIP_RDV = 0, 1, 2
+
+
+def strip_probe(mode: int, variant: int, jobs, nwaves: int = 0, patience: int = 0):
+    """pa_debug_strip (tests): strip jobs of the batched A*PA2 band search through the strips those kernels run (csrc/strip2_kernel.hpp,
+    csrc/strip_kernel.hpp).  `jobs`: dicts with a, b (ACGT bytes), col0, n, word0, nlanes, v (uint64 [ceil(|b| / 64), 2]: V(p, m) per
+    word), hout (uint8 [|a|]) and optionally hin (uint8 [|a|]), hin_is_hout, tap, values (like v), fill_word0, fill_stride.  Inputs are
+    not modified.  Returns ([{"v", "hout", "sum"} per job], rendezvous counters (took, served, alone, withdrawn) or None)."""
+    L = load()
+    L.pa_debug_strip.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pa_debug_strip.restype = C.c_int
+    arr = (_StripProbeJob * max(len(jobs), 1))()
+    keep = []
+    outs = []
+    for t, jd in enumerate(jobs):
+        a, b = bytes(jd["a"]), bytes(jd["b"])
+        v = np.array(jd["v"], np.uint64, copy=True, order="C")
+        hout = np.array(jd["hout"], np.uint8, copy=True, order="C")
+        hin = None if jd.get("hin") is None else np.ascontiguousarray(jd["hin"], np.uint8)
+        values = None if jd.get("values") is None else np.ascontiguousarray(jd["values"], np.uint64)
+        keep += [a, b, hin, values]
+        x = arr[t]
+        x.a, x.a_len, x.b, x.b_len = _buf(a).value, len(a), _buf(b).value, len(b)
+        x.col0, x.n, x.word0, x.nlanes = jd["col0"], jd["n"], jd["word0"], jd["nlanes"]
+        x.tap, x.fill_word0, x.fill_stride, x.hin_is_hout = jd.get("tap", -1), jd.get("fill_word0", 0), jd.get("fill_stride", 0), int(jd.get("hin_is_hout", 0))
+        x.v, x.hout = v.ctypes.data, hout.ctypes.data
+        x.hin = None if hin is None else hin.ctypes.data
+        x.values = None if values is None else values.ctypes.data
+        outs.append({"v": v, "hout": hout})
+    cnt = np.zeros(4, np.uint64)
+    rc = L.pa_debug_strip(mode, variant, nwaves, patience, C.cast(arr, C.c_void_p) if jobs else None, len(jobs), _p(cnt))
+    if rc != 0:
+        raise PaError(f"pa_debug_strip rc={rc}: {last_error()}")
+    for t, o in enumerate(outs):
+        o["sum"] = int(arr[t].sum)
+    return outs, (tuple(int(c) for c in cnt) if mode == STRIP_RDV else None)
 
 
 def release_pools() -> None:

@@ -300,7 +300,7 @@ struct FullDevBackend {
             // the tap: the deltas leaving the lane whose last row is 64 wt - 1, if that row is in this strip
             int tl = -1;
             if (tap_inside && wt > sw0 && wt <= sw0 + take) tl = kk == 2 ? (wt - sw0) - 1 : 2 * (wt - sw0) - 1;
-            if (kk == 1 && rp.enabled && dual_ok(j) && rdv_strip<true>(rdv, wave, rp, j, tl, err, &rdv_cnt, &strip_units, my_prio)) {
+            if (kk == 1 && rp.enabled && dual_ok<true>(j) && rdv_strip<true>(rdv, wave, rp, j, tl, err, &rdv_cnt, &strip_units, my_prio)) {
                 sync_mem();
                 ck = -1;
                 break;  // (a strip that qualifies is the block's only one)

@@ -196,7 +196,7 @@ struct DevBackend {
             j.hin_n = 0;
             j.vsum_out = nullptr;
             // (a strip that is not the last one is full, the last one does not need an exact bottom row: NOPASS)
-            if (kk == 1 && rp.enabled && dual_ok(j) && rdv_strip<false>(rdv, wave, rp, j, -1, err, &rdv_cnt, &strip_units, my_prio)) {
+            if (kk == 1 && rp.enabled && dual_ok<false>(j) && rdv_strip<false>(rdv, wave, rp, j, -1, err, &rdv_cnt, &strip_units, my_prio)) {
                 // (this block and a block of another wavefront ran as one strip -- or a partner ran it: the column and the sum are in memory)
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
                 break;

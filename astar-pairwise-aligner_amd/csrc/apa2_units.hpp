@@ -9,6 +9,7 @@
 #include "rdv_params.hpp"
 
 namespace pa {
+struct StripJob;  // strip_kernel.hpp
 namespace apa2 {
 
 hipError_t launch_apa2_kernel(int grid, hipStream_t s, const PairJob* jobs, const int32_t* order, int npairs, const SearchParams& sp, uint32_t* ticket,
@@ -17,6 +18,16 @@ hipError_t launch_apa2_full_kernel(int grid, hipStream_t s, const FullJob* jobs,
                                    uint32_t* err, uint32_t* dbg, unsigned long long* probe_stats, const RdvParams& rp, unsigned long long* rdv_stats);
 hipError_t launch_gcsh_probe_kernel(hipStream_t s, const FullJob* jobs, const int32_t* q, int nq, int32_t* out, uint32_t* err);
 hipError_t launch_gcsh_build_kernel(int grid, hipStream_t s, const GcshBuildJob* jobs, int npairs, uint32_t* ticket);
+
+// apa2_full_unit.hip, tests only (pa_debug_strip): `blocks` workgroups of strip jobs (device memory; taps[i]: job i's tap lane) through the
+// strips of the band-search kernels -- kStripProbeDual: two jobs fused per wavefront (variant 1 = TAP); kStripProbeSingle: one job per
+// wavefront (variant 0: the half-wave strip of apa2_kernel.hpp, 1 / 2 / 3: the half-wave / K = 1 / K = 2 TAP strips of apa2_full_kernel.hpp);
+// kStripProbeRdv: `nwaves` wavefronts per workgroup meet through rdv_strip (variant 1 = TAP), counters[0..4) += took, served, alone,
+// withdrawn.  strip_probe_dual_ok: dual_ok<tap> on the host.
+enum : int { kStripProbeDual = 0, kStripProbeSingle = 1, kStripProbeRdv = 2 };
+bool strip_probe_dual_ok(const StripJob& j, bool tap);
+hipError_t launch_strip_probe_kernel(hipStream_t s, int mode, int variant, int blocks, int nwaves, const StripJob* jobs, const int32_t* taps,
+                                     uint32_t patience, uint32_t* err, unsigned long long* counters);
 
 // sketch_unit.hip: found_out[pair] = how many of 64 sampled 16-mers of a occur in b near the diagonal (an estimate of (1 - e)^16 in 64ths);
 // the same layout as pa_hip.hip's PairDesc (element offsets into the concatenated sequences)

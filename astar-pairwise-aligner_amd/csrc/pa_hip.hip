@@ -3308,6 +3308,157 @@ extern "C" int pa_debug_gcsh_probe(const uint8_t* a, size_t a_len, const uint8_t
     return 0;
 }
 
+// Diagnostics / tests: strip jobs of the band-search kernels through the instances those kernels use (apa2_full_unit.hip,
+// strip_probe_kernel).  Every job gets buffers of its own in one device arena; a and b are encoded by the batch profile kernels.
+extern "C" int pa_debug_strip(int mode, int variant, int nwaves, uint32_t patience, pa_strip_probe_job* jobs, size_t njobs, uint64_t* counters4) {
+    using apa2::kStripProbeDual;
+    using apa2::kStripProbeRdv;
+    using apa2::kStripProbeSingle;
+    if (!ensure_device()) return PA_E_HIP;
+    auto bad_arg = [](const char* what, size_t t) {
+        set_error("pa_debug_strip: job %zu: %s", t, what);
+        return PA_E_ARG;
+    };
+    if (!jobs || njobs == 0 || njobs > (1u << 20)) return bad_arg("no jobs, or too many", 0);
+    if (mode == kStripProbeDual) {
+        if ((variant != 0 && variant != 1) || njobs % 2 != 0) return bad_arg("dual: variant 0 or 1, an even number of jobs", 0);
+    } else if (mode == kStripProbeSingle) {
+        if (variant < 0 || variant > 3) return bad_arg("single: variant 0 .. 3", 0);
+    } else if (mode == kStripProbeRdv) {
+        if ((variant != 0 && variant != 1) || nwaves < 2 || nwaves > 4 || njobs % (size_t)nwaves != 0)
+            return bad_arg("rdv: variant 0 or 1, 2 .. 4 waves, whole workgroups", 0);
+    } else {
+        return bad_arg("mode 0, 1 or 2", 0);
+    }
+    const bool tap_variant = mode == kStripProbeSingle ? variant >= 1 : variant == 1;
+    const int k = mode == kStripProbeSingle && variant == 3 ? 2 : 1;
+    const int max_lanes = mode == kStripProbeSingle ? (variant == 3 ? 128 : (variant == 2 ? 64 : 32)) : 32;
+    // arena layout: per job a, b, codes, profile, v, hin, values, hout, sum; then the descriptors (all regions 256-byte aligned)
+    struct Off {
+        size_t a, b, codes, prof, v, hin, values, hout, sum, nwb;
+    };
+    std::vector<Off> off(njobs);
+    size_t top = 0, max_a = 0, max_b = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = top;
+        top += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    for (size_t t = 0; t < njobs; ++t) {
+        const pa_strip_probe_job& J = jobs[t];
+        if (!J.a || !J.b || !J.v || !J.hout || J.a_len == 0 || J.b_len == 0 || J.a_len > (1u << 30) || J.b_len > (1u << 30))
+            return bad_arg("a, b, v and hout are required, 1 <= |a|, |b| <= 2^30", t);
+        const size_t nwb = (J.b_len + 63) / 64;
+        if (J.n < 1 || J.col0 < 0 || (size_t)J.col0 + (size_t)J.n > J.a_len) return bad_arg("columns outside a (n >= 1, col0 + n <= |a|)", t);
+        if (J.nlanes < 2 || J.nlanes % 2 != 0 || J.nlanes > max_lanes) return bad_arg("nlanes odd or out of range for the mode", t);
+        if (J.word0 < 0 || (size_t)J.word0 + (size_t)(J.nlanes / 2) > nwb) return bad_arg("rows beyond b's profile", t);
+        if (tap_variant ? (J.tap < -1 || J.tap >= (k == 2 ? J.nlanes / 2 : J.nlanes)) : J.tap != -1) return bad_arg("tap out of range (-1 without TAP)", t);
+        if (J.values && !tap_variant) return bad_arg("values without TAP", t);
+        if ((J.hin_is_hout != 0 && J.hin_is_hout != 1) || (J.hin_is_hout && J.hin)) return bad_arg("hin_is_hout is 0 or 1, and 1 takes no hin", t);
+        Off& o = off[t];
+        o.nwb = nwb;
+        o.a = take(J.a_len);
+        o.b = take(J.b_len);
+        o.codes = take((J.a_len + 15) / 16 * 4);
+        o.prof = take(nwb * 16);
+        o.v = take(nwb * 16);
+        o.hin = J.hin ? take(J.a_len) : 0;
+        o.values = J.values ? take(nwb * 16) : 0;
+        o.hout = take(J.a_len);
+        o.sum = take(4);
+        max_a = std::max(max_a, J.a_len);
+        max_b = std::max(max_b, J.b_len);
+    }
+    const size_t o_desc = take(njobs * sizeof(PairDesc)), o_jobs = take(njobs * sizeof(StripJob)), o_taps = take(njobs * 4), o_misc = take(64);
+    DeviceBuf d;
+    if (!d.alloc(top)) return PA_E_HIP;
+    uint8_t* base = d.as<uint8_t>();
+    std::vector<uint8_t> h(top, 0);
+    PairDesc* desc = (PairDesc*)(h.data() + o_desc);
+    StripJob* sj = (StripJob*)(h.data() + o_jobs);
+    int32_t* taps = (int32_t*)(h.data() + o_taps);
+    for (size_t t = 0; t < njobs; ++t) {
+        const pa_strip_probe_job& J = jobs[t];
+        const Off& o = off[t];
+        std::memcpy(h.data() + o.a, J.a, J.a_len);
+        std::memcpy(h.data() + o.b, J.b, J.b_len);
+        std::memcpy(h.data() + o.v, J.v, o.nwb * 16);
+        if (J.hin) std::memcpy(h.data() + o.hin, J.hin, J.a_len);
+        if (J.values) std::memcpy(h.data() + o.values, J.values, o.nwb * 16);
+        std::memcpy(h.data() + o.hout, J.hout, J.a_len);
+        desc[t].a_off = o.a;
+        desc[t].b_off = o.b;
+        desc[t].code_off = o.codes / 4;
+        desc[t].prof_off = o.prof / 16;
+        desc[t].n = (int)J.a_len;
+        desc[t].m = (int)J.b_len;
+        // as apa2_kernel.hpp / apa2_full_kernel.hpp build a block's strip: the last (only) strip of the block, no granules
+        StripJob j;
+        std::memset(&j, 0, sizeof j);
+        j.a_codes = (const uint32_t*)(base + o.codes);
+        j.b_prof = (const uint32_t*)(base + o.prof);
+        j.v = (uint32_t*)(base + o.v);
+        j.hin_gran = nullptr;
+        j.hin_arr = J.hin_is_hout ? base + o.hout : (J.hin ? base + o.hin : nullptr);
+        j.hout_gran = nullptr;
+        j.hout_arr = tap_variant ? base + o.hout : nullptr;
+        j.values = J.values ? (uint32_t*)(base + o.values) : nullptr;
+        j.sum_out = (int32_t*)(base + o.sum);
+        j.n = J.n;
+        j.word0 = J.word0;
+        j.nlanes = J.nlanes;
+        j.fill_stride = J.fill_stride;
+        j.fill_word0 = J.fill_word0;
+        j.exact_tail = 0;
+        j.flags = 0;
+        j.col0 = J.col0;
+        j.tail_rows = -1;
+        j.k = k;
+        j.ckpt = nullptr;
+        j.ckpt_stride = 0;
+        j.hin_n = 0;
+        j.vsum_out = nullptr;
+        if (mode != kStripProbeSingle && !apa2::strip_probe_dual_ok(j, tap_variant)) return bad_arg("dual_ok refuses the job", t);
+        sj[t] = j;
+        taps[t] = J.tap;
+    }
+    uint32_t* misc = (uint32_t*)(base + o_misc);  // [0] err, [1] invalid base, [8..16) counters
+    hipStream_t s = 0;
+    if (!hip_ok(hipMemcpy(base, h.data(), top, hipMemcpyHostToDevice), "H2D strip probe")) return PA_E_HIP;
+    for (size_t b0 = 0; b0 < njobs; b0 += 32768) {  // gridDim.y limit
+        const unsigned ny = (unsigned)std::min<size_t>(32768, njobs - b0);
+        const PairDesc* dd = (const PairDesc*)(base + o_desc) + b0;
+        hipLaunchKernelGGL(encode_a_batch_kernel, dim3((unsigned)(((max_a + 15) / 16 + 255) / 256), ny), dim3(256), 0, s, base, (uint32_t*)base, dd, misc + 1);
+        hipLaunchKernelGGL(build_b_batch_kernel, dim3((unsigned)(((max_b + 63) / 64 + 3) / 4), ny), dim3(256), 0, s, base, (uint64_t*)base, dd, misc + 1);
+        if (!hip_ok(hipGetLastError(), "profile kernels")) return PA_E_HIP;
+    }
+    uint32_t bad = 0;
+    if (!hip_ok(hipMemcpy(&bad, misc + 1, 4, hipMemcpyDeviceToHost), "D2H")) return PA_E_HIP;
+    if (bad) {
+        set_error("pa_debug_strip: a sequence holds a character outside ACGT");
+        return PA_E_INVALID_BASE;
+    }
+    const int blocks = (int)(mode == kStripProbeDual ? njobs / 2 : (mode == kStripProbeRdv ? njobs / (size_t)nwaves : njobs));
+    if (!hip_ok(apa2::launch_strip_probe_kernel(s, mode, variant, blocks, nwaves, (const StripJob*)(base + o_jobs), (const int32_t*)(base + o_taps), patience,
+                                                misc, (unsigned long long*)(misc + 8)),
+                "strip_probe_kernel") ||
+        !hip_ok(hipDeviceSynchronize(), "sync") || !hip_ok(hipMemcpy(h.data(), base, top, hipMemcpyDeviceToHost), "D2H strip probe"))
+        return PA_E_HIP;
+    const uint32_t* hm = (const uint32_t*)(h.data() + o_misc);
+    if (counters4) std::memcpy(counters4, hm + 8, 32);
+    if (hm[0] != PA_ERR_NONE) {
+        set_error("pa_debug_strip: the device reported error %u", hm[0]);
+        return PA_E_TIMEOUT;
+    }
+    for (size_t t = 0; t < njobs; ++t) {
+        const Off& o = off[t];
+        std::memcpy(jobs[t].v, h.data() + o.v, o.nwb * 16);
+        std::memcpy(jobs[t].hout, h.data() + o.hout, jobs[t].a_len);
+        std::memcpy(&jobs[t].sum, h.data() + o.sum, 4);
+    }
+    return 0;
+}
+
 // Reporting (whole-family batches, pa_batch_create_params with GCSH / pruning / incremental doubling): host milliseconds spent finding
 // the matches of the heuristic at creation, their number, and -- with PA_APA2_PROBE_STATS set -- the h probes of the last forward pass
 // and the load rounds (64 layers each) they took.

@@ -55,9 +55,12 @@ __device__ __forceinline__ DualJob dual_from(const StripJob& j, int tap) {
     d.prio = 0;
     return d;
 }
-// Does a strip of the band-search kernels qualify (see the header)?
-__device__ __forceinline__ bool dual_ok(const StripJob& j) {
-    return j.nlanes <= 32 && j.hin_gran == nullptr && j.hout_gran == nullptr && j.exact_tail == 0 && j.flags == 0 && j.sum_out != nullptr && j.n > 0;
+// Does a strip of the band-search kernels qualify (see the header)?  The fused strip ignores tail_rows, vsum_out, ckpt and hin_n, and
+// without TAP also hout_arr and values (dual_from): a job that sets any of them would come out silently wrong, so it does not qualify.
+template <bool TAP>
+__host__ __device__ __forceinline__ bool dual_ok(const StripJob& j) {
+    return j.tail_rows < 0 && j.vsum_out == nullptr && j.ckpt == nullptr && j.hin_n == 0 && (TAP || (j.hout_arr == nullptr && j.values == nullptr)) &&
+           j.nlanes <= 32 && j.hin_gran == nullptr && j.hout_gran == nullptr && j.exact_tail == 0 && j.flags == 0 && j.sum_out != nullptr && j.n > 0;
 }
 
 template <bool PRED>

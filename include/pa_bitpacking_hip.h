@@ -204,6 +204,30 @@ long pa_debug_gcsh_matches(const uint8_t* a, size_t a_len, const uint8_t* b, siz
  * by one wavefront -- at nq positions (queries[2 t] = i, queries[2 t + 1] = j): out[t] = h(i, j), out[nq] = number of contour layers. */
 int pa_debug_gcsh_probe(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int32_t k, int32_t p_local, const int32_t* queries,
                         size_t nq, int32_t* out);
+/* Diagnostics / tests: strip jobs of the batched A*PA2 band search (csrc/strip2_kernel.hpp, csrc/strip_kernel.hpp) run exactly as those
+ * kernels run them: columns col0 .. col0 + n of a (encoded by the library), rows 64 word0 .. 64 word0 + 32 nlanes of b's profile.
+ * v: ceil(b_len / 64) words V(p:u64, m:u64), the block's left column in, its right column out (words outside the strip untouched).
+ * hin: a_len top-row bytes (bit0 = +1, bit1 = -1), or NULL for all +1; hin_is_hout = 1 reads the top row from hout instead (the
+ * Update pattern: the tapped row overwrites the row it was given).  hout: a_len bytes; TAP strips write the deltas leaving logical
+ * lane `tap` there (tap = -1: none).  values (TAP only, or NULL): ceil(b_len / 64) words, the left edge on words [fill_word0, fill_stride)
+ * of the strip, V::one elsewhere.  sum: the bottom-row sum.
+ * mode 0: jobs 2t and 2t + 1 fused in one wavefront (run_strip_dual; variant 1 = TAP); mode 1: one job per wavefront (variant 0: the
+ * half-wave strip of `simple`, 1 / 2 / 3: the half-wave / K = 1 / K = 2 TAP strips of `full`); mode 2: workgroups of nwaves (2..4)
+ * wavefronts, each posts its job once through the rendezvous with `patience` (100 MHz ticks; variant 1 = TAP), counters4 = took,
+ * served, alone, withdrawn.  A job production would not build in that mode is PA_E_ARG, before anything is launched. */
+typedef struct pa_strip_probe_job {
+    const uint8_t* a;
+    size_t a_len;
+    const uint8_t* b;
+    size_t b_len;
+    int32_t col0, n, word0, nlanes, tap, fill_word0, fill_stride, hin_is_hout;
+    uint32_t* v;
+    const uint8_t* hin;
+    const uint32_t* values;
+    uint8_t* hout;
+    int32_t sum;
+} pa_strip_probe_job;
+int pa_debug_strip(int mode, int variant, int nwaves, uint32_t patience, pa_strip_probe_job* jobs, size_t njobs, uint64_t* counters4);
 
 /* Many-pair mode over several GPUs from ONE process (independent pairs shard with no data-path exchange; the
  * reference runs them one after another, pa-bin/src/main.rs:24-35): a WORK QUEUE.  The pairs are sorted by estimated work
