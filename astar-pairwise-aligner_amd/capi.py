@@ -27,6 +27,8 @@ EXPORTED_SYMBOLS = [
     "pa_batch_create_params", "pa_batch_pair_stats", "pa_runtime_hints", "pa_batch_align_multi_params", "pa_release_pools", "pa_align_file_params", "pa_batch_params_supported", "pa_alloc_cache_stats", "pa_free_cigars",
     "pa_batch_full_info", "pa_batch_rdv_stats", "pa_combine_stats", "pa_params_nw", "pa_params_simple", "pa_params_full", "pa_debug_gcsh_probe", "pa_debug_gcsh_matches", "pa_debug_strip", "pa_batch_window_retries", "pa_batch_window_retry_bytes",
     "pa_batch_slice_info", "pa_set_reference_cost_only",
+    "pa_search_batch_create", "pa_search_batch_run", "pa_search_batch_rows", "pa_search_batch_trace", "pa_search_batch_info",
+    "pa_search_batch_destroy",
 ]
 
 _lib = None
@@ -80,6 +82,15 @@ def load(build_if_stale: bool = True) -> C.CDLL:
     L.pa_search.restype = C.c_int
     L.pa_search_trace.argtypes = [vp, sz, vp, sz, C.c_float, sz, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz)]
     L.pa_search_trace.restype = C.c_int
+    L.pa_search_batch_create.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp, sz, C.c_float]
+    L.pa_search_batch_create.restype = vp
+    L.pa_search_batch_run.argtypes = [vp, vp, vp, C.POINTER(C.c_float)]
+    L.pa_search_batch_rows.argtypes = [vp, vp, vp]
+    L.pa_search_batch_trace.argtypes = [vp, vp, vp, vp]
+    L.pa_search_batch_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 4
+    L.pa_search_batch_info.restype = None
+    L.pa_search_batch_destroy.argtypes = [vp]
+    L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
     L.pa_batch_run.argtypes = [vp, vp, C.POINTER(C.c_float)]
@@ -332,6 +343,100 @@ def search_trace(pattern: bytes, text: bytes, unmatched_cost: float, idx: int):
         if path.value:
             libc.free(path)
     return text_cigar, [(int(arr[2 * k]), int(arr[2 * k + 1])) for k in range(npos.value)]
+
+
+class SearchBatch:
+    """Many semi-global searches in one pass (pa_search_batch_*): query q searches patterns[i] in texts[j] for queries[q] = (i, j).
+    Every pattern and text is uploaded once, however many queries use it."""
+
+    def __init__(self, patterns: list[bytes], texts: list[bytes], queries, unmatched_cost: float):
+        L = load()
+        if any(not isinstance(x, bytes) for x in list(patterns) + list(texts)):
+            raise ValueError("patterns and texts must be bytes")
+        q = np.asarray(queries, dtype=np.int64).reshape(-1, 2)
+        if q.size and (q.min() < 0 or q[:, 0].max() >= len(patterns) or q[:, 1].max() >= len(texts)):
+            raise ValueError("query index out of range")
+        self._keep = (list(patterns), list(texts))
+        self.plens = np.array([len(p) for p in patterns] or [0], np.uint64)
+        self.tlens = np.array([len(t) for t in texts] or [0], np.uint64)
+        self.q_pattern = np.ascontiguousarray(q[:, 0], np.uint32) if len(q) else np.zeros(1, np.uint32)
+        self.q_text = np.ascontiguousarray(q[:, 1], np.uint32) if len(q) else np.zeros(1, np.uint32)
+        self.queries = len(q)
+        pp = (C.c_char_p * max(len(patterns), 1))(*patterns)
+        tp = (C.c_char_p * max(len(texts), 1))(*texts)
+        self._h = L.pa_search_batch_create(pp, _p(self.plens), len(patterns), tp, _p(self.tlens), len(texts), _p(self.q_pattern),
+                                           _p(self.q_text), self.queries, C.c_float(unmatched_cost))
+        if not self._h:
+            msg = last_error()
+            if "unknown base" in msg or "actgACTG" in msg:
+                raise ValueError(msg)
+            raise PaError(msg)
+        self.last_kernel_ms = 0.0
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc == -1:
+            raise ValueError(last_error())
+        if rc != 0:
+            raise PaError(f"{what} rc={rc}: {last_error()}")
+
+    def _lens(self, q: int) -> int:
+        return int(self.plens[self.q_pattern[q]]) + int(self.tlens[self.q_text[q]]) + 1
+
+    def run(self):
+        """-> (best cost int32[queries], lowest index reaching it uint64[queries]); the kernel time is kept in `last_kernel_ms`."""
+        costs = np.zeros(max(self.queries, 1), np.int32)
+        idx = np.zeros(max(self.queries, 1), np.uint64)
+        ms = C.c_float(0)
+        self._check(load().pa_search_batch_run(self._h, _p(costs), _p(idx), C.byref(ms)), "pa_search_batch_run")
+        self.last_kernel_ms = float(ms.value)
+        return costs[: self.queries], idx[: self.queries]
+
+    def rows(self, queries=None) -> list[np.ndarray]:
+        """pa_search's out array of every query (or of the listed ones), after run()."""
+        sel = range(self.queries) if queries is None else [int(q) for q in queries]
+        offsets = np.full(max(self.queries, 1), np.iinfo(np.uint64).max, np.uint64)
+        total = 0
+        for q in sel:
+            offsets[q] = total
+            total += self._lens(q)
+        out = np.zeros(max(total, 1), np.int32)
+        self._check(load().pa_search_batch_rows(self._h, _p(out), _p(offsets)), "pa_search_batch_rows")
+        return [out[int(offsets[q]): int(offsets[q]) + self._lens(q)] for q in sel]
+
+    def trace(self, idx=None) -> list[tuple[str, tuple[int, int]]]:
+        """[(CIGAR, (text index, pattern index) where the alignment starts)] of every query's best hit, or of idx[q]."""
+        L = load()
+        n = self.queries
+        cig = (C.c_void_p * max(n, 1))()
+        starts = np.zeros(2 * max(n, 1), np.int64)
+        want = None
+        if idx is not None:
+            want = np.ascontiguousarray(np.asarray(idx, dtype=np.uint64).reshape(-1))
+            if len(want) != n:
+                raise ValueError("one index per query")
+        rc = L.pa_search_batch_trace(self._h, _p(want) if want is not None else None, cig, _p(starts))
+        try:
+            self._check(rc, "pa_search_batch_trace")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        return [(cigars[q], (int(starts[2 * q]), int(starts[2 * q + 1]))) for q in range(n)]
+
+    def info(self) -> dict:
+        vals = [C.c_double(0) for _ in range(4)]
+        load().pa_search_batch_info(self._h, *[C.byref(v) for v in vals])
+        return {"waves": int(vals[0].value), "packed": int(vals[1].value), "chained": int(vals[2].value), "lane_use": vals[3].value}
+
+    def close(self):
+        if self._h:
+            load().pa_search_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def read_pairs(path: str) -> list[tuple[bytes, bytes]]:

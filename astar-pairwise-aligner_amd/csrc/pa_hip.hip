@@ -1035,11 +1035,10 @@ __global__ void encode_text_cc_kernel(const uint8_t* __restrict__ a, int n, uint
 }
 
 // ---- semi-global search (pa-bitpacking/src/search.rs) ------------------------------------------------------------
-namespace {
 
 // ScatterProfile of the pattern (profile.rs:39-63: wildcards N/* (any), Y (C|T), R (A|G); padding rows match everything)
 // and the left column of the search (every ceil(i / unmatched_cost)-th row costs 1, search.rs:57-65).
-int search_profile(const uint8_t* pattern, size_t plen, float unmatched_cost, std::vector<uint64_t>& prof, std::vector<uint64_t>& v0) {
+int pa::search_profile(const uint8_t* pattern, size_t plen, float unmatched_cost, std::vector<uint64_t>& prof, std::vector<uint64_t>& v0) {
     const size_t w = (plen + 63) / 64;
     prof.assign(4 * std::max<size_t>(w, 1), 0);
     for (size_t j = 0; j < plen; ++j) {
@@ -1069,6 +1068,8 @@ int search_profile(const uint8_t* pattern, size_t plen, float unmatched_cost, st
     }
     return 0;
 }
+
+namespace {
 
 // scatter_profile::compute::<2, _, 4, FILL>(text[0..n), pattern profile, h = zeros, v, exact_end = true, values)
 // (search.rs:71,152) on the GPU: v is updated in place, hrow[n] receives the bottom-row deltas (bit0 = +1, bit1 = -1),

@@ -77,6 +77,9 @@ bool launch_strips(const StripJob* d_jobs, int njobs, bool fill, uint32_t* d_tic
 bool launch_pairs(const StripJob* d_jobs, const int32_t* d_first, int npairs, uint32_t* d_ticket_err, hipStream_t s, int k, bool ckpt = false);
 int align_hip(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, const pa_astarpa2_params& params, bool trace, bool self_check,
               int32_t* cost_out, std::string* cigar_out, pa_astarpa2_stats* stats_out);
+// The semi-global search's ScatterProfile of a pattern (four u64 match masks per 64-row word, padding rows match everything) and its
+// left column v0 (V words), max(ceil(plen / 64), 1) words each.  PA_E_INVALID_BASE on a character outside ACGTNYR* (either case).
+int search_profile(const uint8_t* pattern, size_t plen, float unmatched_cost, std::vector<uint64_t>& prof, std::vector<uint64_t>& v0);
 bool encode_a_device(const uint8_t* d_a, int n, uint32_t* d_codes, uint32_t* d_bad, hipStream_t s);
 bool build_b_device(const uint8_t* d_b, int m, uint64_t* d_prof, uint32_t* d_bad, hipStream_t s);
 // both in one launch; all `code_words` words of d_codes are written (zero beyond the sequence); `bad` may be host-mapped memory

@@ -89,6 +89,37 @@ int pa_search(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t t
 int pa_search_trace(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t tlen, float unmatched_cost, size_t idx,
                     char** cigar_out, int32_t** path_out, size_t* npos_out);
 
+/* ---- batched semi-global search -------------------------------------------------------------------------------------------
+ * Many pa_search queries in one pass.  Patterns and texts are uploaded once each; query q searches patterns[q_pattern[q]] in
+ * texts[q_text[q]], so many patterns can share one text without copying it.  Same alphabets and unmatched_cost rule as pa_search.
+ * A query whose pattern has at most 2048 rows runs in a segment of g = 1, 2, 4 .. 64 lanes of one wavefront (the smallest power of
+ * two with 32 g >= |pattern|), 64 / g queries to a wavefront; longer patterns run on the chained strips of pa_search.
+ * PA_SEARCH_BATCH_NO_PACK=1 puts every query on strips of its own (one wavefront per query and strip), for comparison.
+ * Errors: a non-ACGT text or a bad pattern character of a query is PA_E_INVALID_BASE and the message names the first such query;
+ * an unmatched_cost outside [0, 1] or NaN, a query index out of range or a length above 2^30 is PA_E_ARG.  A failed create returns
+ * NULL.  Zero queries is valid. */
+typedef struct pa_search_batch pa_search_batch;
+pa_search_batch* pa_search_batch_create(const uint8_t* const* patterns, const size_t* plens, size_t npatterns,
+                                        const uint8_t* const* texts, const size_t* tlens, size_t ntexts,
+                                        const uint32_t* q_pattern, const uint32_t* q_text, size_t nqueries,
+                                        float unmatched_cost);
+/* Best hit per query: best_cost[q] = min over all plen + tlen + 1 entries of pa_search's out; best_idx[q] = the lowest index that
+ * reaches it.  Either may be NULL.  kernel_ms (optional): HIP-event time of the forward kernels and the reduction.  May be called
+ * again; it gives the same results. */
+int pa_search_batch_run(pa_search_batch* sb, int32_t* best_cost, uint64_t* best_idx, float* kernel_ms);
+/* After a run: query q's full out array at out + offsets[q], element for element what pa_search returns.  offsets[q] == UINT64_MAX
+ * skips query q. */
+int pa_search_batch_rows(const pa_search_batch* sb, int32_t* out, const uint64_t* offsets);
+/* idx == NULL: trace each query's best hit, else idx[q] (> plen + tlen is PA_E_ARG).  cigars_out[q] is malloc'ed (release with
+ * pa_free_cigars).  start_out[2q], [2q+1] = (text index, pattern index) where the alignment starts, i.e. path[0] of
+ * pa_search_trace.  Runs the forward pass first if pa_search_batch_run has not.  The windows text[end - min(end, 2 |pattern|) .. end)
+ * are re-filled on the GPU in chunks whose `values` stay below a share of the free device memory (PA_SEARCH_TRACE_BUDGET_MB
+ * overrides) and walked on the GPU in pa_search_trace's order.  On error nothing is delivered (every cigars_out[q] is NULL). */
+int pa_search_batch_trace(pa_search_batch* sb, const uint64_t* idx, char** cigars_out, int64_t* start_out);
+/* Plan shape: wavefronts launched (segment waves + strips), queries on the segment kernel, queries on chained strips, and lanes
+ * carrying pattern rows (sum of ceil(|pattern| / 32)) over lanes launched (64 per wavefront). */
+void pa_search_batch_info(const pa_search_batch* sb, double* waves, double* packed, double* chained, double* lane_use);
+void pa_search_batch_destroy(pa_search_batch* sb);
 /* ---- batched full-DP (cost only) on device-resident pairs ------------------------------------------ */
 /* What `AstarPa2Params::nw().make_aligner(false).cost(a,b)` computes (astarpa2/src/params.rs:46-68,
  * blocks.rs:252-277) for many independent pairs at once. */
