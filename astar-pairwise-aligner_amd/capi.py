@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "pa_batch_slice_info", "pa_set_reference_cost_only",
     "pa_search_batch_create", "pa_search_batch_run", "pa_search_batch_rows", "pa_search_batch_trace", "pa_search_batch_info",
     "pa_search_batch_destroy",
+    "pa_affine_batch_create", "pa_affine_batch_run", "pa_affine_batch_align", "pa_affine_batch_info", "pa_affine_batch_destroy",
 ]
 
 _lib = None
@@ -90,6 +91,13 @@ def load(build_if_stale: bool = True) -> C.CDLL:
     L.pa_search_batch_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 4
     L.pa_search_batch_info.restype = None
     L.pa_search_batch_destroy.argtypes = [vp]
+    L.pa_affine_batch_create.argtypes = [vp, vp, vp, vp, sz, vp, C.c_int]
+    L.pa_affine_batch_create.restype = vp
+    L.pa_affine_batch_run.argtypes = [vp, vp, C.POINTER(C.c_float)]
+    L.pa_affine_batch_align.argtypes = [vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pa_affine_batch_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
+    L.pa_affine_batch_info.restype = None
+    L.pa_affine_batch_destroy.argtypes = [vp]
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -437,6 +445,177 @@ class SearchBatch:
             self.close()
         except Exception:
             pass
+
+
+class _AffineCostC(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("sub", "ins", "del_", "ins_open", "ins_extend", "del_open", "del_extend")]
+
+
+AFFINE_MAX_COST = 1000
+AFFINE_ROWS_PER_LANE = 16  # rows of b per lane of the kernel (csrc/affine_kernel.hpp kRows)
+
+
+class AffineCost:
+    """A gap-affine cost model: AffineCost<0> or AffineCost<2> of pa-affine-types (cost_model.rs:112-190).  None = no such edge.
+    `layers` lists the affine layers as (kind, open, extend), kind "ins" or "del", in the reference's order [insert, delete]; a gap of
+    length L in a layer costs open + L * extend."""
+
+    def __init__(self, sub=None, ins=None, del_=None, layers=()):
+        self.sub, self.ins, self.del_ = sub, ins, del_
+        self.layers = [tuple(x) for x in layers]
+
+    @classmethod
+    def lcs(cls):
+        return cls(None, 1, 1)
+
+    @classmethod
+    def unit(cls):
+        return cls(1, 1, 1)
+
+    @classmethod
+    def linear(cls, sub, indel):
+        return cls(sub, indel, indel)
+
+    @classmethod
+    def linear_asymmetric(cls, sub, ins, del_):
+        return cls(sub, ins, del_)
+
+    @classmethod
+    def affine(cls, sub, open, extend):
+        return cls(sub, None, None, [("ins", open, extend), ("del", open, extend)])
+
+    @classmethod
+    def linear_affine(cls, sub, indel, open, extend):
+        return cls(sub, indel, indel, [("ins", open, extend), ("del", open, extend)])
+
+    @classmethod
+    def affine_asymmetric(cls, sub, ins_open, ins_extend, del_open, del_extend):
+        return cls(sub, None, None, [("ins", ins_open, ins_extend), ("del", del_open, del_extend)])
+
+    @classmethod
+    def double_affine(cls, sub, open, extend, open2, extend2):
+        """AffineCost<4>: expressible here for completeness, refused by AffineBatch (not supported on the GPU)."""
+        return cls(sub, None, None, [("ins", open, extend), ("del", open, extend), ("ins", open2, extend2), ("del", open2, extend2)])
+
+    def ins_layer(self):
+        return next(((o, e) for k, o, e in self.layers if k == "ins"), None)
+
+    def del_layer(self):
+        return next(((o, e) for k, o, e in self.layers if k == "del"), None)
+
+    def to_c(self) -> _AffineCostC:
+        """The pa_affine_cost of this model; ValueError for what the GPU kernel does not take."""
+        if len(self.layers) > 2 or [k for k, _, _ in self.layers] not in ([], ["ins", "del"]):
+            raise ValueError(f"only AffineCost<0> and AffineCost<2> with layers [ins, del] are supported, got {self.layers}")
+        vals = [self.sub, self.ins, self.del_] + [x for _, o, e in self.layers for x in (o, e)]
+        for v in vals:
+            if v is not None and (not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= AFFINE_MAX_COST):
+                raise ValueError(f"every cost must be an integer in [1, {AFFINE_MAX_COST}], got {v!r}")
+        il, dl = self.ins_layer(), self.del_layer()
+        if self.ins is None and il is None:
+            raise ValueError("the cost model has no insertion edge")
+        if self.del_ is None and dl is None:
+            raise ValueError("the cost model has no deletion edge")
+        z = lambda v: 0 if v is None else int(v)  # noqa: E731
+        return _AffineCostC(z(self.sub), z(self.ins), z(self.del_), z(il and il[0]), z(il and il[1]), z(dl and dl[0]), z(dl and dl[1]))
+
+    def max_edge(self) -> int:
+        return max([v for v in (self.sub, self.ins, self.del_) if v is not None] + [o + e for _, o, e in self.layers])
+
+    def __repr__(self):
+        return f"AffineCost(sub={self.sub}, ins={self.ins}, del_={self.del_}, layers={self.layers})"
+
+
+class AffineBatch:
+    """Gap-affine global alignment of many pairs on the GPU (pa_affine_batch_*): NW::new(cm, false, false).align(a, b) of pa-base-algos
+    for every pair, a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align()."""
+
+    def __init__(self, pairs, cm: AffineCost, trace: bool = False):
+        pairs = list(pairs)
+        if any(not isinstance(x, bytes) or not isinstance(y, bytes) for x, y in pairs):
+            raise ValueError("pairs must be (bytes, bytes)")
+        if not isinstance(cm, AffineCost):
+            raise ValueError("cm must be an AffineCost")
+        c = cm.to_c()
+        big = cm.max_edge()
+        for p, (x, y) in enumerate(pairs):
+            if (len(x) + len(y) + 1) * big >= 1 << 30:
+                raise ValueError(f"pair {p}: (|a| + |b| + 1) * max edge cost is not below 2^30")
+        L = load()
+        self._keep = pairs
+        self.npairs = len(pairs)
+        self.trace = bool(trace)
+        n = max(len(pairs), 1)
+        ap = (C.c_char_p * n)(*[x for x, _ in pairs])
+        bp = (C.c_char_p * n)(*[y for _, y in pairs])
+        al = np.array([len(x) for x, _ in pairs] or [0], np.uint64)
+        bl = np.array([len(y) for _, y in pairs] or [0], np.uint64)
+        self._c = c
+        self._h = L.pa_affine_batch_create(ap, _p(al), bp, _p(bl), len(pairs), C.byref(c), int(self.trace))
+        if not self._h:
+            msg = last_error()
+            if msg.startswith("pa_affine_batch_create:"):
+                raise ValueError(msg)
+            raise PaError(msg)
+        self.last_kernel_ms = 0.0
+        self.last_forward_ms = 0.0
+        self.last_trace_ms = 0.0
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc == -4:
+            raise ValueError(last_error())
+        if rc != 0:
+            raise PaError(f"{what} rc={rc}: {last_error()}")
+
+    def run(self) -> np.ndarray:
+        """Costs only: int32[npairs]; the kernel time is kept in `last_kernel_ms`."""
+        costs = np.zeros(max(self.npairs, 1), np.int32)
+        ms = C.c_float(0)
+        self._check(load().pa_affine_batch_run(self._h, _p(costs), C.byref(ms)), "pa_affine_batch_run")
+        self.last_kernel_ms = float(ms.value)
+        return costs[: self.npairs]
+
+    def align(self) -> list[tuple[int, str]]:
+        """[(cost, CIGAR)] of every pair (trace batches only)."""
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        cig = (C.c_void_p * max(n, 1))()
+        f, t = C.c_float(0), C.c_float(0)
+        rc = L.pa_affine_batch_align(self._h, _p(costs), cig, C.byref(f), C.byref(t))
+        try:
+            self._check(rc, "pa_affine_batch_align")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
+        return [(int(costs[p]), cigars[p]) for p in range(n)]
+
+    def info(self) -> dict:
+        vals = [C.c_double(0) for _ in range(5)]
+        load().pa_affine_batch_info(self._h, *[C.byref(v) for v in vals])
+        return {"waves": int(vals[0].value), "packed_pairs": int(vals[1].value), "strip_pairs": int(vals[2].value), "lane_use": vals[3].value,
+                "trace_chunks": int(vals[4].value)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().pa_affine_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def align_affine(pairs, cm: AffineCost) -> list[tuple[int, str]]:
+    """[(cost, CIGAR)] of every pair under the gap-affine cost model `cm` (one traced AffineBatch)."""
+    b = AffineBatch(pairs, cm, trace=True)
+    try:
+        return b.align()
+    finally:
+        b.close()
 
 
 def read_pairs(path: str) -> list[tuple[bytes, bytes]]:

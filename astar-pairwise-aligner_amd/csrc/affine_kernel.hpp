@@ -1,0 +1,284 @@
+// affine_kernel.hpp -- the device side of the batched gap-affine global alignment (pa_affine_batch_*, affine_unit.hip).
+//
+// What it computes: NW::new(cm, false, false) of pa-base-algos over an AffineCost<0> or AffineCost<2> (layers [insert, delete]), i.e.
+// the full-matrix AffineFront DP of pa-base-algos/src/nw/affine.rs.  Per cell (i over a, j over b), the affine layers before the main
+// layer (EditGraph::iterate_layers, edge_graph.rs:82-87) and with the parents of EditGraph::iterate_parents (edit_graph.rs:96-169):
+//   I(i,j) = min(M(i,j-1) + ins_open, I(i,j-1) + ins_extend)                       (insert layer: consumes b)
+//   D(i,j) = min(M(i-1,j) + del_open, D(i-1,j) + del_extend)                       (delete layer: consumes a)
+//   M(i,j) = min(M(i-1,j-1) + (a[i-1] == b[j-1] ? 0 : sub), M(i,j-1) + ins, M(i-1,j) + del, I(i,j) + ins_extend, D(i,j) + del_extend)
+// An absent edge costs kInf.  Column 0 (AffineNwFront::first_col, nw/affine.rs:84-106) is the same recurrence with column -1 at kInf,
+// and M(0,0) = 0.  Values of unreachable states stay at or a little above kInf (the reference caps them at INF): they never tie with
+// a reachable state's cost, which is below 2^30 by the limits the host checks.
+//
+// Layout: the strip shape of strip_kernel.hpp.  Lane r of a strip owns rows j0 + 1 .. j0 + kRows (j0 = (64 s + r) kRows for strip s)
+// and handles column t - r at step t.  Per row it keeps M and D of the previous column in registers; once per step its bottom row's
+// M and I and the column's byte of a go to lane r + 1 through dpp_wave_shr1 (the insert layer is the only state carried down a
+// column).  The first lane of a strip takes row 0 instead: the row-0 recurrence (M(i,0) = min(M(i-1,0) + del, D(i,0) + del_extend))
+// on strip 0, the boundary row the previous strip left in global memory (8 B per column: M, I of its last row) on the others.
+//   * Short pairs (|b| <= 64 kRows) run in SEGMENTS of g lanes (g the smallest power of two with g kRows >= |b|), 64 / g pairs per
+//     wavefront; each segment's first lane starts its own pair.  The planner sorts by (g, |a|), like seg_kernel's.
+//   * Longer pairs take a whole wavefront that runs all their strips top to bottom, one after the other.
+// Lanes that have not reached column 0 yet compute on kInf inputs and keep kInf-ish state, so no step needs predication: only the
+// stores are guarded.
+//
+// kRows = 16: two values per row (M, D of the previous column) and the row's byte of b make 48 VGPRs of state; with the temporaries of
+// the FILL variant the kernel stays under 128 VGPRs (4+ waves per SIMD), and 16 code bytes per lane and step are one 16-byte store.
+// 32 rows would double the state (over 96 VGPRs before temporaries) for a skew (63 steps per strip) that is already short next to
+// 1000+ columns, and would pack half as many short pairs per wavefront.
+//
+// FILL: every cell also stores one traceback byte (kCode*), the first parent in iterate_parents order whose cost matches:
+//   bits 2:0  main layer: 0 diagonal, 1 linear insertion, 2 linear deletion, 3 close of the insert layer, 4 close of the delete layer
+//   bit  3    insert layer: 0 open (from M(i,j-1)), 1 extend
+//   bit  4    delete layer: 0 open (from M(i-1,j)), 1 extend
+// Codes of rows 1 .. H of column i at codes[i H + j - 1], row 0 at codes[(n + 1) H + i].  affine_walk_kernel walks them backwards from
+// (n, m, main) to (0, 0, main) (AffineNwFronts::trace / parent, nw/affine.rs:164-188, 283-305).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "strip_kernel.hpp"
+
+namespace pa {
+namespace affine {
+
+constexpr int kRows = 16;  // rows of b per lane
+constexpr int kBlockWaves = 4;
+constexpr uint32_t kInf = 1u << 30;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// Edge costs, kInf where the model has no such edge.
+struct Costs {
+    uint32_t sub, ins, del, io, ie, dopen, de;
+    uint32_t pad_;
+};
+
+// One pair.  Device pointers.
+struct Pair {
+    const uint8_t* a;
+    const uint8_t* b;
+    uint8_t* codes;  // FILL only: (n + 1) H + n + 1 bytes
+    uint32_t n, m;   // |a|, |b|
+    uint32_t H;      // rows of a code column: g kRows (segments) or strips 64 kRows
+    uint32_t out;    // index into the cost output
+};
+static_assert(kRows == 16, "the FILL store packs 16 code bytes");
+static_assert(sizeof(Pair) == 40, "Pair layout");
+
+// One wavefront: pairs [first, first + np) of the Pair array, all of segment width 1 << lg; strips > 1 only for a lone pair (lg = 6).
+struct Wave {
+    uint32_t first, np, lg, strips;
+    uint32_t nmax;  // longest a of the wave
+    uint32_t pad_;
+    uint64_t* bnd;  // strips > 1: nmax + 1 boundary values (M | I << 32) of the strip above
+};
+static_assert(sizeof(Wave) == 32, "Wave layout");
+
+__device__ __forceinline__ uint32_t umin(uint32_t x, uint32_t y) { return x < y ? x : y; }
+__device__ __forceinline__ uint32_t umin3(uint32_t x, uint32_t y, uint32_t z) { return umin(umin(x, y), z); }
+
+template <bool FILL>
+__global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __restrict__ waves, int nwaves, const Pair* __restrict__ pairs,
+                                                                  Costs C, int32_t* __restrict__ cost_out) {
+    const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
+    if (wave >= nwaves) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const Wave W = waves[wave];
+    const int g = 1 << W.lg;
+    const int seg = lane >> W.lg, r = lane & (g - 1);
+    const bool present = (uint32_t)seg < W.np;
+    const bool first = r == 0, last = r == g - 1;
+    Pair P;
+    P.a = nullptr;
+    P.b = nullptr;
+    P.codes = nullptr;
+    P.n = 0;
+    P.m = 0;
+    P.H = 0;
+    P.out = 0;
+    if (present) P = pairs[W.first + seg];
+    const int n = (int)P.n;
+    const uint32_t m = P.m;
+    const gcu8 ga = (gcu8)P.a;
+    const gcu8 gb = (gcu8)P.b;
+    const gu8 codes = (gu8)P.codes;
+    const gi32 out = (gi32)cost_out;
+    const int T = (int)W.nmax + g;  // steps per strip: the last lane reaches column nmax at step nmax + g - 1
+    for (int s = 0; s < (int)W.strips; ++s) {
+        const uint32_t j0 = (uint32_t)(64 * s + r) * kRows;
+        uint32_t bk[kRows], Mp[kRows], Dp[kRows];
+#pragma unroll
+        for (int k = 0; k < kRows; ++k) {
+            bk[k] = present && j0 + k < m ? (uint32_t)gb[j0 + k] : 0x200u;  // rows below b (never read back)
+            Mp[k] = kInf;
+            Dp[k] = kInf;
+        }
+        const bool top = first && s == 0;  // row 0 is this lane's
+        const bool from_bnd = first && s > 0;
+        const gcu64 bnd = (gcu64)W.bnd;
+        uint32_t r0M = kInf, r0D = kInf;  // row 0 of the previous column
+        uint32_t topPrev = kInf;          // M of the row above this lane's first row, previous column
+        uint32_t outM = kInf, outI = kInf, outC = 0x100u;
+        uint32_t nextC = 0x100u;  // a[t - 1] of the next step (the first lane's prefetch)
+        uint64_t nextB = (uint64_t)kInf << 32 | kInf;
+        if (from_bnd && present) nextB = bnd[0];
+        for (int t = 0; t < T; ++t) {
+            const int i = t - r;  // column
+            const bool active = present && i >= 0 && i <= n;
+            uint32_t inM = dpp_wave_shr1(kInf, outM);
+            uint32_t inI = dpp_wave_shr1(kInf, outI);
+            uint32_t inC = dpp_wave_shr1(0x100u, outC);
+            if (first) {
+                inC = nextC;
+                if (top) {
+                    const uint32_t nd = umin3(r0M + C.dopen, r0D + C.de, kInf);
+                    const uint32_t nm = t == 0 ? 0u : umin3(r0M + C.del, nd + C.de, kInf);
+                    if (FILL && active) {
+                        const uint32_t code = (nm == r0M + C.del ? 2u : 4u) | (nd == r0M + C.dopen ? 0u : 16u);
+                        codes[(size_t)(n + 1) * P.H + (size_t)i] = (uint8_t)code;
+                    }
+                    r0M = nm;
+                    r0D = nd;
+                    inM = nm;
+                    inI = kInf;
+                } else {
+                    inM = (uint32_t)nextB;
+                    inI = (uint32_t)(nextB >> 32);
+                }
+                // prefetch the next column's byte and boundary value
+                nextC = present && t + 1 <= n ? (uint32_t)ga[t] : 0x100u;
+                if (from_bnd && present && t + 1 <= n) nextB = bnd[t + 1];
+                if (top && active && i == n && m == 0) out[P.out] = (int32_t)inM;
+            }
+            uint32_t Mdiag = topPrev;
+            topPrev = inM;
+            uint32_t Mup = inM, Iup = inI;
+            uint32_t code[kRows / 4] = {0, 0, 0, 0};  // FILL: the step's 16 code bytes
+#pragma unroll
+            for (int k = 0; k < kRows; ++k) {
+                const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
+                const uint32_t iop = Mup + C.io;
+                const uint32_t I = umin(iop, Iup + C.ie);
+                const uint32_t dop = Mp[k] + C.dopen;
+                const uint32_t D = umin(dop, Dp[k] + C.de);
+                const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del, cI = I + C.ie, cD = D + C.de;
+                const uint32_t M = umin(umin3(cd, ci, cdl), umin3(cI, cD, kInf));
+                if (FILL) {
+                    uint32_t c = M == cI ? 3u : 4u;
+                    c = M == cdl ? 2u : c;
+                    c = M == ci ? 1u : c;
+                    c = M == cd ? 0u : c;
+                    c |= I == iop ? 0u : 8u;
+                    c |= D == dop ? 0u : 16u;
+                    code[k >> 2] |= c << (8 * (k & 3));
+                }
+                Mdiag = Mp[k];
+                Mp[k] = M;
+                Dp[k] = D;
+                Mup = M;
+                Iup = I;
+            }
+            if (active) {
+                if (FILL) {
+                    const u32x4 w = {code[0], code[1], code[2], code[3]};
+                    *reinterpret_cast<PA_GLOBAL u32x4*>(codes + (size_t)i * P.H + j0) = w;  // one 16-byte store
+                }
+                if (last && s + 1 < (int)W.strips) ((gu64)W.bnd)[i] = (uint64_t)Iup << 32 | Mup;
+                if (i == n && m > j0 && m <= j0 + kRows) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
+                    out[P.out] = (int32_t)v;
+                }
+            }
+            outM = Mup;
+            outI = Iup;
+            outC = inC;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the same wavefront reads the boundary row back in the next strip
+    }
+}
+
+// One traceback (AffineNwFronts::trace): from (n, m, main) back to (0, 0, main), the first matching parent of every state as the FILL
+// codes recorded it.  ops[] receives the steps from the end backwards: '=', 'X', 'I', 'D'.
+struct Walk {
+    const uint8_t* a;
+    const uint8_t* b;
+    const uint8_t* codes;
+    uint8_t* ops;
+    uint32_t n, m, H, cap;
+};
+static_assert(sizeof(Walk) == 48, "Walk layout");
+struct WalkOut {
+    int32_t status;  // 0 ok, 1 bad code, 2 ops over capacity
+    int32_t nops;
+};
+
+__global__ __launch_bounds__(64) void affine_walk_kernel(const Walk* __restrict__ walks, int nw, WalkOut* __restrict__ outs) {
+    const int t = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (t >= nw) return;
+    const Walk Q = walks[t];
+    int64_t i = Q.n, j = Q.m;
+    int layer = 0;  // 0 main, 1 insert, 2 delete
+    const size_t row0 = (size_t)(Q.n + 1) * Q.H;
+    WalkOut o;
+    o.status = 0;
+    o.nops = 0;
+    auto emit = [&](uint8_t op) {
+        if ((uint32_t)o.nops < Q.cap) Q.ops[o.nops] = op;
+        ++o.nops;
+    };
+    while (o.status == 0 && (i > 0 || j > 0 || layer != 0)) {
+        const uint32_t c = j > 0 ? Q.codes[(size_t)i * Q.H + (size_t)(j - 1)] : Q.codes[row0 + (size_t)i];
+        if (layer == 0) {
+            switch (c & 7u) {
+                case 0:
+                    if (i == 0 || j == 0) {
+                        o.status = 1;
+                        break;
+                    }
+                    emit(Q.a[i - 1] == Q.b[j - 1] ? '=' : 'X');
+                    --i;
+                    --j;
+                    break;
+                case 1:
+                    if (j == 0) o.status = 1;
+                    else {
+                        emit('I');
+                        --j;
+                    }
+                    break;
+                case 2:
+                    if (i == 0) o.status = 1;
+                    else {
+                        emit('D');
+                        --i;
+                    }
+                    break;
+                case 3: layer = 1; break;
+                case 4: layer = 2; break;
+                default: o.status = 1;
+            }
+        } else if (layer == 1) {
+            if (j == 0) {
+                o.status = 1;
+                break;
+            }
+            emit('I');
+            --j;
+            if (!(c & 8u)) layer = 0;
+        } else {
+            if (i == 0) {
+                o.status = 1;
+                break;
+            }
+            emit('D');
+            --i;
+            if (!(c & 16u)) layer = 0;
+        }
+    }
+    if (o.status == 0 && (uint32_t)o.nops > Q.cap) o.status = 2;
+    outs[t] = o;
+}
+
+}  // namespace affine
+}  // namespace pa

@@ -1,0 +1,57 @@
+/*
+ * pa_affine_hip.h -- batched gap-affine global alignment on the GPU (libastarpa_c_hip.so, MI355X / gfx950).
+ *
+ * What `NW::new(cm, false, false).align(a, b)` of pa-base-algos computes (the full-matrix AffineFront, nw/affine.rs) for many
+ * independent pairs: the cost and, optionally, the CIGAR of every pair, over the cost models AffineCost<0> and AffineCost<2> can express
+ * (pa-affine-types/src/cost_model.rs:112-190: lcs, unit, linear, linear_asymmetric, affine, linear_affine, affine_asymmetric).
+ * Sequences are any bytes, compared for equality (AffineFront builds no BitProfile); empty sequences are valid.  a and b are never
+ * swapped: I consumes b, D consumes a.
+ *
+ * CIGAR: the reference's backward walk from (|a|, |b|, main) to (0, 0, main), taking at every state the first parent in
+ * EditGraph::iterate_parents order whose cost fits (main layer: diagonal, linear ins, linear del, close of the insert layer, close of
+ * the delete layer; affine layers: open before extend), printed as AffineCigar::to_string() (= X I D, the count left out when 1).
+ *
+ * Errors follow pa_bitpacking_hip.h: 0 or a negative PA_E_* code, pa_last_error() for the message.
+ */
+#ifndef PA_AFFINE_HIP_H
+#define PA_AFFINE_HIP_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* One cost model; 0 means absent (the reference's None).  The insert layer exists when ins_open and ins_extend are both non-zero, the
+ * delete layer likewise; a gap of length L in a layer costs open + L * extend.  Every cost is in [1, 1000] or 0; a layer with only one
+ * of its two costs, or a model with no way to insert or no way to delete, is PA_E_ARG.  (AffineCost<4>, double_affine, has no
+ * representation here.) */
+typedef struct pa_affine_cost {
+    int32_t sub, ins, del, ins_open, ins_extend, del_open, del_extend;
+} pa_affine_cost;
+
+/* Pair p aligns a[p] (a_len[p] bytes) against b[p].  For every pair, (|a| + |b| + 1) * (the largest edge cost, open + extend counted
+ * as one) must be below 2^30, else PA_E_ARG naming the pair.  trace != 0 allows pa_affine_batch_align.  A failed create returns NULL.
+ * Zero pairs is valid.  Pairs with |b| <= 1024 run several to a wavefront (segments of g = 1, 2, 4 .. 64 lanes of 16 rows each); longer
+ * ones take a wavefront each, its strips of 1024 rows one after the other. */
+typedef struct pa_affine_batch pa_affine_batch;
+pa_affine_batch* pa_affine_batch_create(const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b, const size_t* b_len,
+                                        size_t npairs, const pa_affine_cost* cm, int trace);
+/* Costs only.  cost_out[p] (may be NULL), kernel_ms (optional): HIP-event time of the forward kernel.  May be called again. */
+int pa_affine_batch_run(pa_affine_batch* ab, int32_t* cost_out, float* kernel_ms);
+/* Costs and CIGARs (trace batches only, else PA_E_ARG).  cigar_out[p] is malloc'ed (release with pa_free_cigars); on error every
+ * cigar_out[p] is NULL.  The pairs run in chunks whose traceback codes (one byte per cell) stay within PA_AFFINE_TRACE_BUDGET_MB, or a
+ * quarter of the free device memory; a pair whose codes alone exceed it is PA_E_ARG.  forward_ms / trace_ms (optional): HIP-event time
+ * of the forward kernels and of the walks, summed over the chunks. */
+int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, char** cigar_out, float* forward_ms, float* trace_ms);
+/* Plan shape of run(): wavefronts launched, pairs packed into segments (|b| <= 1024), pairs on strips of their own, lanes carrying rows
+ * of b (sum of ceil(max(|b|, 1) / 16)) over lanes launched (64 per wavefront and strip), and the chunks of the last align(). */
+void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,
+                          double* trace_chunks);
+void pa_affine_batch_destroy(pa_affine_batch* ab);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,180 @@
+"""Batched gap-affine alignment (pa_affine_batch_*): kernel time, GCUPS and pairs/s, costs only and traced, for three shapes under
+affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
+
+    python tools/affine_bench.py [--shapes reads,10k,100k] [--no-trace-100k]
+
+Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import astar_pairwise_aligner_amd as pa  # noqa: E402
+from astar_pairwise_aligner_amd import AffineBatch, AffineCost  # noqa: E402
+
+GOTOH_C = r"""
+#include <stdint.h>
+#include <stdlib.h>
+/* cost of the global alignment, column by column over a; absent edge = 1 << 30 (INF) */
+int64_t gotoh(const uint8_t* a, int64_t n, const uint8_t* b, int64_t m, int64_t sub, int64_t ins, int64_t del, int64_t io, int64_t ie,
+              int64_t dop, int64_t de) {
+    const int64_t INF = 1 << 30;
+    int64_t *M = malloc((m + 1) * sizeof(int64_t)), *D = malloc((m + 1) * sizeof(int64_t));
+    M[0] = 0; D[0] = INF;
+    int64_t I = INF;
+    for (int64_t j = 1; j <= m; ++j) {
+        I = I + ie < M[j - 1] + io ? I + ie : M[j - 1] + io;
+        int64_t v = M[j - 1] + ins; if (I + ie < v) v = I + ie; M[j] = v < INF ? v : INF; D[j] = INF;
+    }
+    for (int64_t i = 1; i <= n; ++i) {
+        int64_t diag = M[0];
+        D[0] = D[0] + de < M[0] + dop ? D[0] + de : M[0] + dop;
+        int64_t v0 = M[0] + del; if (D[0] + de < v0) v0 = D[0] + de; M[0] = v0 < INF ? v0 : INF;
+        I = INF;
+        const uint8_t ai = a[i - 1];
+        for (int64_t j = 1; j <= m; ++j) {
+            I = I + ie < M[j - 1] + io ? I + ie : M[j - 1] + io;
+            D[j] = D[j] + de < M[j] + dop ? D[j] + de : M[j] + dop;
+            int64_t v = diag + (ai == b[j - 1] ? 0 : sub);
+            if (M[j - 1] + ins < v) v = M[j - 1] + ins;
+            if (M[j] + del < v) v = M[j] + del;
+            if (I + ie < v) v = I + ie;
+            if (D[j] + de < v) v = D[j] + de;
+            diag = M[j];
+            M[j] = v < INF ? v : INF;
+        }
+    }
+    int64_t r = M[m];
+    free(M); free(D);
+    return r;
+}
+"""
+
+
+def cpu_lib():
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if not cc:
+        return None
+    d = Path(tempfile.mkdtemp())
+    (d / "gotoh.c").write_text(GOTOH_C)
+    subprocess.run([cc, "-O3", "-march=native", "-shared", "-fPIC", "-o", str(d / "gotoh.so"), str(d / "gotoh.c")], check=True)
+    L = C.CDLL(str(d / "gotoh.so"))
+    L.gotoh.restype = C.c_int64
+    L.gotoh.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64] + [C.c_int64] * 7
+    return L
+
+
+def cpu_args(cm):
+    il, dl = cm.ins_layer(), cm.del_layer()
+    inf = 1 << 30
+    z = lambda v: inf if v is None else v  # noqa: E731
+    return [z(cm.sub), z(cm.ins), z(cm.del_), z(il and il[0]), z(il and il[1]), z(dl and dl[0]), z(dl and dl[1])]
+
+
+def rand_seq(rng, n):
+    return bytes(b"ACGT"[k] for k in rng.integers(0, 4, n)) if n < 5000 else np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n)].tobytes()
+
+
+def mutate(rng, s: bytes, rate: float) -> bytes:
+    x = np.frombuffer(s, np.uint8)
+    r = rng.random(len(x))
+    keep = r >= rate / 3  # deletions
+    out = x.copy()
+    subm = (r >= rate / 3) & (r < 2 * rate / 3)
+    out[subm] = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, int(subm.sum()))]
+    ins = (r >= 2 * rate / 3) & (r < rate)
+    pieces = np.where(ins[:, None], np.stack([out, np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, len(x))]], 1), out[:, None])
+    flat = [pieces[k, : 2 if ins[k] else 1] for k in range(len(x)) if keep[k]] if len(x) < 5000 else None
+    if flat is not None:
+        return b"".join(p.tobytes() for p in flat)
+    lens = np.where(keep, np.where(ins, 2, 1), 0)
+    idx = np.repeat(np.arange(len(x)), lens)
+    second = np.concatenate([[False], idx[1:] == idx[:-1]])
+    return np.where(second, pieces[idx, 1], pieces[idx, 0]).astype(np.uint8).tobytes()
+
+
+def shape(name, rng):
+    if name == "reads":
+        pairs = []
+        for _ in range(100_000):
+            w = int(rng.integers(150, 201))
+            y = rand_seq(rng, w)
+            pairs.append((mutate(rng, y[:150], 0.05), y))
+        return "100000 x 150 bp reads vs 150-200 bp windows", pairs
+    if name == "10k":
+        pairs = []
+        for _ in range(4096):
+            y = rand_seq(rng, 10_000)
+            pairs.append((mutate(rng, y, 0.05), y))
+        return "4096 x 10 kbp at 5 %", pairs
+    pairs = []
+    for _ in range(16):
+        y = rand_seq(rng, 100_000)
+        pairs.append((mutate(rng, y, 0.05), y))
+    return "16 x 100 kbp at 5 %", pairs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="reads,10k,100k")
+    ap.add_argument("--trace-100k", action="store_true", help="also trace the 100 kbp pairs (10 GB of codes each)")
+    ap.add_argument("--trace-pairs", type=int, default=512, help="traced runs of the 10 kbp shape use this many of its pairs")
+    ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
+    args = ap.parse_args()
+    pa.require_gpu()
+    L = cpu_lib()
+    rng = np.random.default_rng(1)
+    models = {"affine(4,6,2)": AffineCost.affine(4, 6, 2), "unit()": AffineCost.unit()}
+    for sname in args.shapes.split(","):
+        title, pairs = shape(sname, rng)
+        cells = float(sum(len(x) * len(y) for x, y in pairs))
+        for mname, cm in models.items():
+            trace = sname != "100k" or args.trace_100k
+            b = AffineBatch(pairs, cm)
+            info = b.info()
+            b.run()  # warm-up
+            ms = []
+            for _ in range(3):
+                b.run()
+                ms.append(b.last_kernel_ms)
+            k = min(ms)
+            line = (f"{title:44s} {mname:14s} cost-only: {k:10.2f} ms {cells / k / 1e6:8.1f} GCUPS {len(pairs) / k * 1e3:12.0f} pairs/s"
+                    f"  (waves {info['waves']}, lane use {info['lane_use']:.3f})")
+            print(line, flush=True)
+            b.close()
+            if trace:
+                tp = pairs[: args.trace_pairs] if sname == "10k" else pairs
+                tcells = float(sum(len(x) * len(y) for x, y in tp))
+                tb = AffineBatch(tp, cm, trace=True)
+                tb.align()
+                f, t = tb.last_forward_ms, tb.last_trace_ms
+                print(f"{'':44s} {mname:14s} traced:    {f + t:10.2f} ms {tcells / (f + t) / 1e6:8.1f} GCUPS {len(tp) / (f + t) * 1e3:12.0f} pairs/s"
+                      f"  (forward {f:.2f} ms = {tcells / f / 1e6:.1f} GCUPS, walks {t:.2f} ms, {tb.info()['trace_chunks']} chunks, {len(tp)} pairs)",
+                      flush=True)
+                tb.close()
+            else:
+                print(f"{'':44s} {mname:14s} traced:    not measured", flush=True)
+            if L is not None:
+                done, c0, t0 = 0, 0.0, time.perf_counter()
+                for x, y in pairs:
+                    L.gotoh(x, len(x), y, len(y), *cpu_args(cm))
+                    done += 1
+                    c0 += len(x) * len(y)
+                    if time.perf_counter() - t0 > args.cpu_seconds:
+                        break
+                dt = time.perf_counter() - t0
+                print(f"{'':44s} {mname:14s} CPU core:  {c0 / dt / 1e9:8.3f} GCUPS {done / dt:12.1f} pairs/s  ({done} pairs, scalar Gotoh, cc -O3)",
+                      flush=True)
+
+
+if __name__ == "__main__":
+    main()
