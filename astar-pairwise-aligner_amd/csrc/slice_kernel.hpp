@@ -10,13 +10,16 @@
 // above's register":
 //     eq_i  = (a0 ^ nb0_i) & (a1 ^ nb1_i)        profile.rs:141-144 on bit planes: a0 / a1 = the column's code bits over the 32 pairs,
 //                                                nb0_i / nb1_i = the NEGATED code bits of row i (the reference's negated planes)
-//     hm_i  = vp_i & (eq_i | hm_(i-1))           myers.rs:36-39  (hx, hm)
-//     hp_i  = vm_i | ~(eq_i | hm_(i-1) | vp_i)   myers.rs:38
-//     vp'_i = hm_(i-1) | ~(eq_i | vm_i | hp_(i-1))   myers.rs:33,50 with the shifted hp / hm of :44-47
-//     vm'_i = hp_(i-1) & (eq_i | vm_i)           myers.rs:51
-// 8 two- or three-input logic instructions per (row x 32 pairs x 64 lanes) = 2048 cells, all of the fast VALU class (4 v_bitop3 with three
-// VGPR sources, 4 VOP2) -- no v_add_co / v_addc, no v_alignbit, no per-row DPP -- against 11.3 mixed instructions per 2048 cells in
-// pair_kernel<8>.  tools/slice_probe.hip, profiles/r06_runs/slice_probe*.log: 196 TCUPS against 130.
+//     z_i   = eq_i | vm_i | hm_(i-1)             D(i, j) = D(i-1, j-1): myers.rs:36-39's hx = eq | hm_in and :51's eq | vm in one OR
+//                                                (vp & vm = 0 and hp & hm = 0 in every valid state, so the extra term changes no output)
+//     hm_i  = vp_i & z_i                         myers.rs:36-39  (hx, hm)
+//     hp_i  = vm_i | ~(z_i | vp_i)               myers.rs:38
+//     vp'_i = hm_(i-1) | ~(z_i | hp_(i-1))       myers.rs:33,50 with the shifted hp / hm of :44-47
+//     vm'_i = hp_(i-1) & z_i                     myers.rs:51
+// 7 two- or three-input logic instructions per (row x 32 pairs x 64 lanes) = 2048 cells, all of the fast VALU class (4 v_bitop3 with three
+// VGPR sources, 3 VOP2) -- no v_add_co / v_addc, no v_alignbit, no per-row DPP -- against 11.3 mixed instructions per 2048 cells in
+// pair_kernel<8>.  tools/slice_probe.hip, profiles/r06_runs/slice_probe*.log: 196 TCUPS against 130 (with the 8-instruction row of round 6,
+// which computed hx = eq | hm_in and eq | vm separately; the 7-instruction row: DESIGN §2).
 //
 // Shape: a lane owns R consecutive rows in registers (vp, vm, nb0, nb1: 4 R VGPRs; R = 56 at two wavefronts per SIMD).  The 64 lanes of a
 // wavefront are skewed one column per lane (lane l works on column t - l at step t), so a STRIP is 64 R rows; the bottom row's (hp, hm)
@@ -89,33 +92,37 @@ __device__ __forceinline__ void st_boundary(uint2* p, uint32_t hp, uint32_t hm) 
     __hip_atomic_store((unsigned long long*)p, (unsigned long long)hp | ((unsigned long long)hm << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Two rows (A = i, B = i + 1) of one column step, in an order in which no instruction reads the result of the one before it and the chain
-// value hm_B is ready eight instructions before the block ends.  Inline asm because the compiler's own order hoists the whole hm chain of
+// Two rows (A = i, B = i + 1) of one column step, 7 instructions a row.  z = eq | vm | hm_in ("D(i, j) = D(i - 1, j - 1)") serves all four
+// outputs, because vp & vm = 0 and hp_in & hm_in = 0 in every valid state: hm = z & vp, hp = vm | ~(z | vp), vp' = hm_in | ~(z | hp_in),
+// vm' = z & hp_in (top of this file; tests/test_slice_row_logic.py interprets this asm against the cell rule and a plain DP).  z is written as
+// v_bitop3 0xfe, not as v_or3_b32: with v_or3 (hm kept as vp & (eq | hm_in), off the z chain) the bench batch took 432 ms against 346 --
+// DESIGN §8.  The chain to the next row (hm_in -> z -> hm) is two instructions, and one pair of neighbours (zA -> hmA) has to read the
+// result of the instruction just before it: row A's z needs its eq, every other instruction of the block needs z, and row B's two
+// instructions in front (its xor and eq) fill only two of the three gaps.  Every other instruction reads nothing the one before it wrote,
+// and hm_B is ready five instructions before the block ends (zA / zB hold eq until z overwrites it).  Inline asm because the compiler's own order hoists the whole hm chain of
 // the lane in front of everything else (2 R live temporaries: spills at R >= 40) -- tools/slice_probe.hip, SLICE_ASM=0.  Every asm statement
 // costs one s_nop (the hazard recognizer assumes the worst of a register that one asm statement writes and the next reads); blocks of FOUR
 // rows halve those and run 16-20 % SLOWER all the same, whichever order the 32 instructions have (profiles/r06_runs/slice_variants.log).
 #define PA_SLICE_ROW_PAIR(vpA, vmA, vpB, vmB, nb0A, nb1A, nb0B, nb1B, a0, a1, hpp, hmp, hpo, hmo)                                      \
     do {                                                                                                                                \
-        uint32_t eA_, eB_, x_, vx_, hmA_, hpA_;                                                                                          \
+        uint32_t zA_, zB_, hmA_, hpA_;                                                                                                  \
         asm volatile(                                                                                                                   \
-            "v_xor_b32 %[eA], %[a1_], %[nb1A_]\n\t"                                                                                     \
-            "v_xor_b32 %[eB], %[a1_], %[nb1B_]\n\t"                                                                                     \
-            "v_bitop3_b32 %[eA], %[a0_], %[nb0A_], %[eA] bitop3:0x28\n\t"                                                               \
-            "v_bitop3_b32 %[eB], %[a0_], %[nb0B_], %[eB] bitop3:0x28\n\t"                                                               \
-            "v_bitop3_b32 %[hmA], %[vpA_], %[eA], %[hmp_] bitop3:0xe0\n\t"                                                              \
-            "v_or_b32 %[x], %[eA], %[hmp_]\n\t"                                                                                         \
-            "v_or_b32 %[vx], %[eA], %[vmA_]\n\t"                                                                                        \
-            "v_bitop3_b32 %[hmB], %[vpB_], %[eB], %[hmA] bitop3:0xe0\n\t"                                                               \
-            "v_bitop3_b32 %[hpA], %[vmA_], %[x], %[vpA_] bitop3:0xf1\n\t"                                                               \
-            "v_bitop3_b32 %[vpA_], %[hmp_], %[vx], %[hpp_] bitop3:0xf1\n\t"                                                             \
-            "v_and_b32 %[vmA_], %[hpp_], %[vx]\n\t"                                                                                     \
-            "v_or_b32 %[x], %[eB], %[hmA]\n\t"                                                                                          \
-            "v_or_b32 %[vx], %[eB], %[vmB_]\n\t"                                                                                        \
-            "v_bitop3_b32 %[hpB], %[vmB_], %[x], %[vpB_] bitop3:0xf1\n\t"                                                               \
-            "v_bitop3_b32 %[vpB_], %[hmA], %[vx], %[hpA] bitop3:0xf1\n\t"                                                               \
-            "v_and_b32 %[vmB_], %[hpA], %[vx]"                                                                                          \
-            : [eA] "=&v"(eA_), [eB] "=&v"(eB_), [x] "=&v"(x_), [vx] "=&v"(vx_), [hmA] "=&v"(hmA_), [hpA] "=&v"(hpA_), [hmB] "=&v"(hmo),  \
-              [hpB] "=&v"(hpo), [vpA_] "+v"(vpA), [vmA_] "+v"(vmA), [vpB_] "+v"(vpB), [vmB_] "+v"(vmB)                                  \
+            "v_xor_b32 %[zA], %[a1_], %[nb1A_]\n\t"                                                                                     \
+            "v_xor_b32 %[zB], %[a1_], %[nb1B_]\n\t"                                                                                     \
+            "v_bitop3_b32 %[zA], %[a0_], %[nb0A_], %[zA] bitop3:0x28\n\t"                                                               \
+            "v_bitop3_b32 %[zB], %[a0_], %[nb0B_], %[zB] bitop3:0x28\n\t"                                                               \
+            "v_bitop3_b32 %[zA], %[zA], %[vmA_], %[hmp_] bitop3:0xfe\n\t"                                                               \
+            "v_and_b32 %[hmA], %[zA], %[vpA_]\n\t"                                                                                      \
+            "v_bitop3_b32 %[hpA], %[vmA_], %[zA], %[vpA_] bitop3:0xf1\n\t"                                                              \
+            "v_bitop3_b32 %[zB], %[zB], %[vmB_], %[hmA] bitop3:0xfe\n\t"                                                                \
+            "v_bitop3_b32 %[vpA_], %[hmp_], %[zA], %[hpp_] bitop3:0xf1\n\t"                                                             \
+            "v_and_b32 %[hmB], %[zB], %[vpB_]\n\t"                                                                                      \
+            "v_and_b32 %[vmA_], %[hpp_], %[zA]\n\t"                                                                                     \
+            "v_bitop3_b32 %[hpB], %[vmB_], %[zB], %[vpB_] bitop3:0xf1\n\t"                                                              \
+            "v_bitop3_b32 %[vpB_], %[hmA], %[zB], %[hpA] bitop3:0xf1\n\t"                                                               \
+            "v_and_b32 %[vmB_], %[hpA], %[zB]"                                                                                          \
+            : [zA] "=&v"(zA_), [zB] "=&v"(zB_), [hmA] "=&v"(hmA_), [hpA] "=&v"(hpA_), [hmB] "=&v"(hmo), [hpB] "=&v"(hpo),              \
+              [vpA_] "+v"(vpA), [vmA_] "+v"(vmA), [vpB_] "+v"(vpB), [vmB_] "+v"(vmB)                                                    \
             : [a0_] "v"(a0), [a1_] "v"(a1), [nb0A_] "v"(nb0A), [nb1A_] "v"(nb1A), [nb0B_] "v"(nb0B), [nb1B_] "v"(nb1B), [hpp_] "v"(hpp), \
               [hmp_] "v"(hmp));                                                                                                         \
     } while (0)

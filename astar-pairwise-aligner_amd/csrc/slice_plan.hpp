@@ -32,7 +32,7 @@ int run(Plan* p, hipStream_t s, const uint32_t* d_codes, const uint64_t* d_prof,
 struct Info {
     int rows_per_lane;
     size_t groups, jobs;          // jobs = (group, strip) units
-    double valu_instructions;     // wavefront VALU instructions of the DP kernel per pass (ISA model: (8 R + kStepOverhead) per strip step)
+    double valu_instructions;     // wavefront VALU instructions of the DP kernel per pass (ISA model: (7 R + kStepOverheadInstr) per strip step)
     double computed_rows_cells;   // cells actually computed (rows padded to whole strips, columns to the group's longest a)
     double device_bytes;          // the plan's own device memory
     double boundary_bytes;        // of those, the boundary rows that are reset before every pass

@@ -28,11 +28,12 @@ struct Plan {
 
 static int strips_for(size_t m, int R) { return (int)((m + (size_t)64 * R - 1) / ((size_t)64 * R)); }
 
-// ns per row step (8 instructions) per wavefront at two wavefronts per SIMD, and per step outside the rows (24 instructions = three row
-// steps): the bench batch's 8192 jobs of 100 063 steps x (50 rows + 3) take their wave slots 4 x 95.2 ms (profiles/r06_runs/slice_variants.log);
+// ns per row step (7 instructions) per wavefront at two wavefronts per SIMD, and per step outside the rows (24 instructions, the same as with
+// the 8-instruction row of round 6, which priced them at three of its row steps: 3 x 17.9 ns): the bench batch's 8192 jobs of 100 063 steps
+// take their wave slots 4 x 86.5 ms (346 ms a launch: profiles/r07_runs/row_ab.log), 864 ns a step = 50 x 16.2 + 53.7;
 // kChainPenalty: what a strip loses per strip of its group's chain (asleep behind the strip above, filling and draining the chain) -- 36 strips
 // of 44 rows against 32 of 50 for 16 384 x 100 kbp: 789 against 760 ms where the plain count of instructions calls it a tie.
-static constexpr double kNsPerRowStep = 17.9, kNsStepOverhead = 3 * 17.9, kChainPenalty = 0.0015;
+static constexpr double kNsPerRowStep = 16.2, kNsStepOverhead = 53.7, kChainPenalty = 0.0015;
 
 int choose_rows_per_lane(const size_t* a_len, const size_t* b_len, size_t pairs, double simds, double* est_ns) {
     if (const char* e = getenv("PA_SLICE")) {
@@ -132,7 +133,7 @@ Plan* create(const size_t* a_len, const size_t* b_len, size_t pairs, const size_
         max_n = std::max(max_n, n);
         max_rows = std::max(max_rows, (size_t)grp.nstrips * 64 * R);
         for (int s = 0; s < grp.nstrips; ++s) p->jobs.push_back(SliceJob{(uint32_t)p->groups.size(), (uint32_t)s});
-        p->valu += (double)grp.nstrips * ((double)n + 63.0) * (8.0 * R + kStepOverheadInstr);
+        p->valu += (double)grp.nstrips * ((double)n + 63.0) * (7.0 * R + kStepOverheadInstr);
         p->computed += (double)grp.nstrips * 64.0 * R * (double)n * 32.0;
         p->groups.push_back(grp);
     }
