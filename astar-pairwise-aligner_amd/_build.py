@@ -10,7 +10,7 @@ PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libastarpa_c_hip.so"
 
-HIP_SOURCES = ["pa_hip.hip", "engine_hip.hip", "astarpa_c.hip", "pairs_io.hip", "apa2_simple_unit.hip", "apa2_full_unit.hip", "gcsh_build_unit.hip", "sketch_unit.hip", "slice_unit.hip", "search_batch_unit.hip", "affine_unit.hip"]
+HIP_SOURCES = ["pa_hip.hip", "runtime_unit.hip", "rect_unit.hip", "search_unit.hip", "debug_unit.hip", "engine_hip.hip", "astarpa_c.hip", "pairs_io.hip", "apa2_simple_unit.hip", "apa2_full_unit.hip", "gcsh_build_unit.hip", "sketch_unit.hip", "slice_unit.hip", "search_batch_unit.hip", "affine_unit.hip"]
 
 
 def _hipcc() -> str:
@@ -59,8 +59,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     """hipcc --offload-arch=gfx950 -> libastarpa_c_hip.so next to this file."""
     if not force and not is_stale():
         return LIB_PATH
-    # One hipcc per translation unit, side by side (they share no device symbols: no -fgpu-rdc), then one link: the four units take
-    # 2.5 minutes one after the other and as long as the slowest (pa_hip.hip) in parallel.
+    # One hipcc per translation unit, side by side (they share no device symbols: no -fgpu-rdc), then one link: the build takes as
+    # long as the slowest unit, rect_unit.hip with the strip and pair kernels' instances (about 190 s; apa2_full_unit.hip 35 s,
+    # pa_hip.hip and engine_hip.hip 20 s each, every other unit under 15 s).
     from concurrent.futures import ThreadPoolExecutor
 
     extra = os.environ.get("PA_HIPCC_EXTRA", "").split()  # experiments only (e.g. -DPA_PHASE_BARRIERS)
@@ -87,7 +88,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
 
     def compile_one(src: Path) -> Path:
         # a unit whose sources (the files its last compilation read) did not change keeps its object: editing one kernel header
-        # recompiles the units that include it, not the 100 s of pa_hip.hip
+        # recompiles the units that include it, and only an edit that reaches rect_unit.hip pays its 190 s
         obj = objdir / (src.stem + ".o")
         dep, stamp = objdir / (src.stem + ".d"), objdir / (src.stem + ".hash")
         if not force_all and obj.exists() and stamp.exists() and stamp.read_text().strip() == (unit_hash(dep) or "-"):

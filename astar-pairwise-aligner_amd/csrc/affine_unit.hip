@@ -11,7 +11,6 @@
 #include "../../include/pa_affine_hip.h"
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,22 +30,6 @@ int seg_lg(size_t m) {  // log2 of the segment width: smallest g = 2^lg with g k
     int lg = 0;
     while ((size_t(kRows) << lg) < m) ++lg;
     return lg;
-}
-
-int fail(int rc, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int rc, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    set_error("%s", buf);
-    return rc;
-}
-
-bool upload(DeviceBuf& d, const void* src, size_t bytes, hipStream_t s) {
-    if (!d.alloc(std::max<size_t>(bytes, 16))) return false;
-    return bytes == 0 || hip_ok(hipMemcpyAsync(d.ptr, src, bytes, hipMemcpyHostToDevice, s), "H2D");
 }
 
 // One launch's worth of waves over a subset of the pairs.
@@ -152,17 +135,6 @@ struct Events {
             if (x) (void)hipEventDestroy(x);
     }
 };
-
-// Device-memory budget of one traced chunk (the codes dominate): PA_AFFINE_TRACE_BUDGET_MB, else a quarter of the free memory.
-size_t trace_budget() {
-    if (const char* e = getenv("PA_AFFINE_TRACE_BUDGET_MB")) {
-        const double mb = atof(e);
-        if (mb > 0) return (size_t)(mb * 1048576.0);
-    }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b == 0) return size_t(1) << 30;
-    return free_b / 4;
-}
 
 }  // namespace
 
@@ -277,7 +249,7 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
     if (cigar_out)
         for (size_t p = 0; p < ab->np; ++p) cigar_out[p] = nullptr;
     if (!ab->trace) return fail(PA_E_ARG, "pa_affine_batch_align: the batch was created without trace");
-    const size_t budget = trace_budget();
+    const size_t budget = trace_budget("PA_AFFINE_TRACE_BUDGET_MB");  // (the traceback codes dominate a chunk)
     for (size_t p = 0; p < ab->np; ++p)
         if (code_bytes_of(ab->n[p], ab->m[p]) > budget)
             return fail(PA_E_ARG, "pa_affine_batch_align: pair %zu: %zu bytes of traceback codes exceed the budget of %zu bytes", p,
@@ -358,20 +330,7 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
     if (cost_out && ab->np) std::memcpy(cost_out, c.data(), ab->np * 4);
     if (forward_ms) *forward_ms = fwd_total;
     if (trace_ms) *trace_ms = trace_total;
-    if (cigar_out) {
-        for (size_t p = 0; p < ab->np; ++p) {
-            cigar_out[p] = (char*)std::malloc(cigars[p].size() + 1);
-            if (!cigar_out[p]) {
-                for (size_t k = 0; k < p; ++k) {
-                    std::free(cigar_out[k]);
-                    cigar_out[k] = nullptr;
-                }
-                return fail(PA_E_NOMEM, "out of memory");
-            }
-            std::memcpy(cigar_out[p], cigars[p].c_str(), cigars[p].size() + 1);
-        }
-    }
-    return 0;
+    return cigar_out ? give_cstrings(cigars, cigar_out) : 0;
 }
 
 extern "C" void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,

@@ -30,7 +30,7 @@ hipError_t launch_strip_probe_kernel(hipStream_t s, int mode, int variant, int b
                                      uint32_t patience, uint32_t* err, unsigned long long* counters);
 
 // sketch_unit.hip: found_out[pair] = how many of 64 sampled 16-mers of a occur in b near the diagonal (an estimate of (1 - e)^16 in 64ths);
-// the same layout as pa_hip.hip's PairDesc (element offsets into the concatenated sequences)
+// the same layout as pa_hip_internal.hpp's PairDesc (element offsets into the concatenated sequences)
 struct SketchDesc {
     unsigned long long a_off, b_off, code_off, prof_off;
     int n, m;

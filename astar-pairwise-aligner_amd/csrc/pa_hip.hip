@@ -1,5 +1,6 @@
-// pa_hip.hip -- host side of libastarpa_c_hip.so: device buffers, strip planning, the operator
-// C ABI (include/pa_bitpacking_hip.h) and the batched full-DP plan.  gfx950 only.
+// pa_hip.hip -- the batched plans of libastarpa_c_hip.so: struct pa_batch (full DP, banded, traced, A*PA2), how it is planned, launched
+// and reported (pa_batch_*), and the traceback and CIGAR-text kernels it launches.  The runtime layer is runtime_unit.hip, the strips
+// rect_unit.hip.  gfx950 only.
 #include "pa_hip_internal.hpp"
 #include "slice_plan.hpp"
 #include "engine_capi.hpp"
@@ -11,790 +12,17 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <atomic>
 #include <mutex>
-#include <set>
 #include <thread>
 #include <string>
 #include <vector>
 
 namespace pa {
-
-static thread_local std::string g_last_error;
-
-void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-}
-
-bool hip_ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    set_error("HIP error in %s: %s", what, hipGetErrorString(e));
-    return false;
-}
-
-// ---- device kernels: profile building ---------------------------------------------------------
-
-// rank in "ACGT" (bio RankTransform as used by BitProfile::build, profile.rs:113); -1 otherwise
-__device__ __forceinline__ int rank_acgt(uint8_t c) {
-    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
-}
-
-// One thread per 16 columns: ASCII -> packed 2-bit codes.
-__global__ void encode_a_kernel(const uint8_t* __restrict__ a, int n, uint32_t* __restrict__ codes, int nwords,
-                                uint32_t* __restrict__ bad) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nwords) return;
-    uint32_t w = 0;
-    bool invalid = false;
-    for (int k = 0; k < 16; ++k) {
-        const int c = i * 16 + k;
-        if (c < n) {
-            const int r = rank_acgt(a[c]);
-            invalid |= r < 0;
-            w |= (uint32_t)(r & 3) << (2 * k);
-        }
-    }
-    codes[i] = w;
-    if (invalid) atomicOr(bad, 1u);
-}
-
-// One wave per 64-row word: negated bit-planes via ballot; rows >= m stay (0,0) (profile.rs:127-132).
-__global__ void build_b_kernel(const uint8_t* __restrict__ b, int m, uint64_t* __restrict__ prof, int nwords,
-                               uint32_t* __restrict__ bad) {
-    const int word = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (word >= nwords) return;
-    const int lane = threadIdx.x & 63;
-    const int j = word * 64 + lane;
-    int r = 3;  // (r&1)^1 == 0 and ((r>>1)&1)^1 == 0 => pad rows contribute 0 bits
-    bool invalid = false;
-    if (j < m) {
-        r = rank_acgt(b[j]);
-        invalid = r < 0;
-        r &= 3;
-    }
-    const uint64_t nb0 = __ballot(((r & 1) ^ 1) != 0);
-    const uint64_t nb1 = __ballot((((r >> 1) & 1) ^ 1) != 0);
-    if (lane == 0) {
-        prof[2 * word] = nb0;
-        prof[2 * word + 1] = nb1;
-    }
-    if (invalid) atomicOr(bad, 1u);
-}
-
-// Batched forms (one launch for all pairs of a pa_batch): blockIdx.y = pair.
-struct PairDesc {
-    unsigned long long a_off, b_off, code_off, prof_off;  // element offsets into the concatenated buffers
-    int n, m;
-};
-
-__global__ void encode_a_batch_kernel(const uint8_t* __restrict__ a_cat, uint32_t* __restrict__ codes_cat,
-                                      const PairDesc* __restrict__ desc, uint32_t* __restrict__ bad) {
-    const PairDesc d = desc[blockIdx.y];
-    const int nwords = (d.n + 15) / 16;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nwords) return;
-    const uint8_t* a = a_cat + d.a_off;
-    uint32_t w = 0;
-    bool invalid = false;
-    for (int k = 0; k < 16; ++k) {
-        const int c = i * 16 + k;
-        if (c < d.n) {
-            const int r = rank_acgt(a[c]);
-            invalid |= r < 0;
-            w |= (uint32_t)(r & 3) << (2 * k);
-        }
-    }
-    codes_cat[d.code_off + i] = w;
-    if (invalid) atomicOr(bad, 1u);
-}
-
-__global__ void build_b_batch_kernel(const uint8_t* __restrict__ b_cat, uint64_t* __restrict__ prof_cat,
-                                     const PairDesc* __restrict__ desc, uint32_t* __restrict__ bad) {
-    const PairDesc d = desc[blockIdx.y];
-    const int nwords = (d.m + 63) / 64;
-    const int word = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (word >= nwords) return;
-    const uint8_t* b = b_cat + d.b_off;
-    const int lane = threadIdx.x & 63;
-    const int j = word * 64 + lane;
-    int r = 3;
-    bool invalid = false;
-    if (j < d.m) {
-        r = rank_acgt(b[j]);
-        invalid = r < 0;
-        r &= 3;
-    }
-    const uint64_t nb0 = __ballot(((r & 1) ^ 1) != 0);
-    const uint64_t nb1 = __ballot((((r >> 1) & 1) ^ 1) != 0);
-    if (lane == 0) {
-        prof_cat[2 * (d.prof_off + word)] = nb0;
-        prof_cat[2 * (d.prof_off + word) + 1] = nb1;
-    }
-    if (invalid) atomicOr(bad, 1u);
-}
-
-template __global__ void strip_kernel<1, false, false>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<1, true, false>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<1, false, true>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<1, true, true>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<2, false, false>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<4, false, false>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<8, false, false>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<1, false, false, true>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<2, false, false, true>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<4, false, false, true>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void strip_kernel<8, false, false, true>(const StripJob*, int, uint32_t*, uint32_t*);
-template __global__ void pair_kernel<1>(const StripJob*, const int32_t*, int, uint32_t*);
-template __global__ void pair_kernel<2>(const StripJob*, const int32_t*, int, uint32_t*);
-template __global__ void pair_kernel<4>(const StripJob*, const int32_t*, int, uint32_t*);
-template __global__ void pair_kernel<8>(const StripJob*, const int32_t*, int, uint32_t*);
-template __global__ void pair_kernel<1, true>(const StripJob*, const int32_t*, int, uint32_t*);
-template __global__ void pair_kernel<2, true>(const StripJob*, const int32_t*, int, uint32_t*);
-template __global__ void pair_kernel<4, true>(const StripJob*, const int32_t*, int, uint32_t*);
-template __global__ void pair_kernel<8, true>(const StripJob*, const int32_t*, int, uint32_t*);
-
-// ---- device context -----------------------------------------------------------------------------
-
-static thread_local int g_device_props_cus = 0;  // of the device this thread last initialised (pa_set_device is per thread)
-static thread_local int g_device_props_dev = -1;
-
-bool ensure_device() {
-    static thread_local bool inited = false;
-    if (inited) {
-        int cur = 0;
-        if (hipGetDevice(&cur) == hipSuccess && cur == g_device_props_dev) return true;
-    }
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0) {
-        set_error("no HIP device available: the MI355X path is required (there is no CPU fallback)");
-        return false;
-    }
-    int dev = 0;
-    if (!hip_ok(hipGetDevice(&dev), "hipGetDevice")) return false;
-    hipDeviceProp_t prop;
-    if (!hip_ok(hipGetDeviceProperties(&prop, dev), "hipGetDeviceProperties")) return false;
-    g_device_props_cus = prop.multiProcessorCount;
-    g_device_props_dev = dev;
-    inited = true;
-    return true;
-}
-
-// ---- device memory -----------------------------------------------------------------------------------------------------------
-// Large buffers are CACHED: hipMalloc + hipFree of the 40 GB block-column store of a 4096 x 100 kbp batch cost about a second, seven
-// times the alignment of the pairs it holds, and pa_align_file / the work queue create a batch per chunk.  A buffer of at least
-// kCacheMin bytes goes to a free list when its owner lets go of it and is handed to the next request on the same device that it fits
-// (at most a quarter larger than asked for).  Nothing in this library reads device memory it has not written, and a cached block is
-// as undefined as a fresh one.  The list is bounded per device (cache_limit, oldest out first), emptied when an allocation fails, and
-// returned to the driver by pa_release_pools().  PA_NO_ALLOC_CACHE=1 switches it off; PA_POISON_ALLOC=1 fills every buffer handed
-// out with 0xA5 (tests: nothing may depend on fresh memory being zero).
-namespace {
-constexpr size_t kCacheMin = size_t(16) << 20, kCacheMaxDefault = size_t(16) << 30;
-// The bound is PER DEVICE: PA_ALLOC_CACHE_MAX (bytes, or with a K / M / G suffix) if set, else half of the device's memory, at most 16 GB
-// (round 4: with band-proportional block columns a 4096 x 100 kbp A*PA2 batch holds 5 GB, not 40)
-// -- other users of the device in the same process (torch, RCCL) cannot make this library let go of what it caches.
-size_t cache_limit(int dev) {
-    static std::mutex mu;
-    static std::vector<size_t> lim;
-    std::lock_guard<std::mutex> lk(mu);
-    if ((size_t)dev < lim.size() && lim[(size_t)dev]) return lim[(size_t)dev];
-    size_t v = 0;
-    if (const char* e = getenv("PA_ALLOC_CACHE_MAX")) {
-        char* end = nullptr;
-        double x = std::strtod(e, &end);
-        if (end && (*end == 'G' || *end == 'g')) x *= double(size_t(1) << 30);
-        else if (end && (*end == 'M' || *end == 'm')) x *= double(size_t(1) << 20);
-        else if (end && (*end == 'K' || *end == 'k')) x *= 1024.0;
-        v = x > 0 ? (size_t)x : 1;
-    } else {
-        size_t free_b = 0, total_b = 0;
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        if (cur != dev) (void)hipSetDevice(dev);
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = 0;
-        if (cur != dev) (void)hipSetDevice(cur);
-        v = total_b ? std::min(kCacheMaxDefault, total_b / 2) : kCacheMaxDefault;
-    }
-    if ((size_t)dev >= lim.size()) lim.resize((size_t)dev + 1, 0);
-    lim[(size_t)dev] = v;
-    return v;
-}
-struct CachedBlock {
-    int dev;
-    void* ptr;
-    size_t size;
-};
-// (never destroyed: buffers of thread-local pools are released after the statics of this file at process exit)
-std::mutex& g_cache_mu = *new std::mutex;
-std::vector<CachedBlock>& g_cache = *new std::vector<CachedBlock>;  // oldest first
-size_t g_cache_bytes = 0;
-std::atomic<uint64_t> g_cache_hits{0}, g_cache_misses{0};
-
-bool cache_on() {
-    static const bool off = getenv("PA_NO_ALLOC_CACHE") != nullptr;
-    return !off;
-}
-void* cache_take(int dev, size_t bytes, size_t* got) {
-    std::lock_guard<std::mutex> lk(g_cache_mu);
-    size_t best = g_cache.size();
-    for (size_t i = 0; i < g_cache.size(); ++i)
-        if (g_cache[i].dev == dev && g_cache[i].size >= bytes && g_cache[i].size <= bytes + bytes / 4 &&
-            (best == g_cache.size() || g_cache[i].size < g_cache[best].size))
-            best = i;
-    if (best == g_cache.size()) return nullptr;
-    void* p = g_cache[best].ptr;
-    *got = g_cache[best].size;
-    g_cache_bytes -= g_cache[best].size;
-    g_cache.erase(g_cache.begin() + (long)best);
-    return p;
-}
-// -> blocks the caller has to hipFree (outside the lock)
-std::vector<CachedBlock> cache_put(int dev, void* ptr, size_t size) {
-    std::vector<CachedBlock> out;
-    const size_t limit = cache_limit(dev);
-    std::lock_guard<std::mutex> lk(g_cache_mu);
-    g_cache.push_back({dev, ptr, size});
-    g_cache_bytes += size;
-    size_t on_dev = 0;
-    for (const CachedBlock& b : g_cache)
-        if (b.dev == dev) on_dev += b.size;
-    for (size_t i = 0; i < g_cache.size() && on_dev > limit;) {  // this device's oldest blocks go first
-        if (g_cache[i].dev != dev) {
-            ++i;
-            continue;
-        }
-        out.push_back(g_cache[i]);
-        g_cache_bytes -= g_cache[i].size;
-        on_dev -= g_cache[i].size;
-        g_cache.erase(g_cache.begin() + (long)i);
-    }
-    return out;
-}
-void free_blocks(const std::vector<CachedBlock>& blocks) {
-    if (blocks.empty()) return;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (const CachedBlock& b : blocks) {
-        if (b.dev != cur) (void)hipSetDevice(b.dev);
-        (void)hipFree(b.ptr);
-        if (b.dev != cur) (void)hipSetDevice(cur);
-    }
-}
-}  // namespace
-
-// PA_POISON_ALLOC: on a stream of its own that does not synchronise with the null stream (persistent kernels may be in flight)
-static bool poison_fill(void* ptr, size_t size) {
-    static thread_local hipStream_t st = nullptr;
-    if (!st && !hip_ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "poison stream")) return false;
-    return hip_ok(hipMemsetAsync(ptr, 0xA5, size, st), "poison") && hip_ok(hipStreamSynchronize(st), "poison sync");
-}
-
-void pinned_release_all();
-void release_alloc_cache() {
-    pinned_release_all();
-    std::vector<CachedBlock> all;
-    {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        all.swap(g_cache);
-        g_cache_bytes = 0;
-    }
-    free_blocks(all);
-}
-
-extern "C" void pa_alloc_cache_stats(uint64_t* hits, uint64_t* misses, uint64_t* cached_bytes) {
-    if (hits) *hits = g_cache_hits.load();
-    if (misses) *misses = g_cache_misses.load();
-    if (cached_bytes) {
-        std::lock_guard<std::mutex> lk(g_cache_mu);
-        *cached_bytes = g_cache_bytes;
-    }
-}
-
-bool DeviceBuf::alloc(size_t bytes) {
-    release();
-    if (bytes < 64) bytes = 64;
-    static const bool poison = getenv("PA_POISON_ALLOC") != nullptr;
-    int dev = 0;
-    if (!hip_ok(hipGetDevice(&dev), "hipGetDevice")) return false;
-    // Small buffers are cached too (round 5), in size classes (2^k and 1.5 x 2^k): a batch of a few pairs -- what the call combiner behind
-    // pa_align creates a thousand times a second -- made some thirty hipMalloc / hipFree calls of 50-100 us each, every hipFree a device wait.
-    const bool big = cache_on();
-    if (big && bytes < kCacheMin) {
-        size_t c = 64;
-        while (c < bytes) c = (c + c / 2 >= bytes && (c & (c - 1)) == 0) ? c + c / 2 : ((c & (c - 1)) == 0 ? c * 2 : (c / 3) * 4);
-        bytes = c;
-    }
-    if (big) {
-        if (bytes >= kCacheMin) bytes = (bytes + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);  // (2 MB steps: requests of almost the same size meet)
-        size_t got = 0;
-        if (void* p = cache_take(dev, bytes, &got)) {
-            ptr = p;
-            size = got;
-            device = dev;
-            g_cache_hits += 1;
-            if (poison && !poison_fill(ptr, size)) return false;
-            return true;
-        }
-        g_cache_misses += 1;
-    }
-    hipError_t e = hipMalloc(&ptr, bytes);
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {  // give the cached blocks back and try once more
-        (void)hipGetLastError();
-        release_alloc_cache();
-        e = hipMalloc(&ptr, bytes);
-    }
-    if (!hip_ok(e, "hipMalloc")) {
-        ptr = nullptr;
-        return false;
-    }
-    size = bytes;
-    device = dev;
-    if (poison && !poison_fill(ptr, size)) return false;
-    return true;
-}
-bool DeviceBuf::reserve(size_t bytes, bool* grew) {
-    if (grew) *grew = false;
-    if (ptr && size >= bytes) return true;
-    const size_t want = bytes + bytes / 4 + 256;  // geometric growth: a pool of buffers reused from call to call
-    if (!alloc(want)) return false;
-    if (grew) *grew = true;
-    return true;
-}
-// Pinned host buffers (the packed CIGAR text of a batch, its per-pair lengths) are POOLED for the life of the process: hipHostMalloc /
-// hipHostFree of a few tens of megabytes cost 5-25 ms each, which a batch that lives for one alignment (the work queue's chunks, pa_align_file)
-// paid twice (round 4: `close` of the C4 batch 12-50 ms).  At most kPinnedPoolMax bytes are kept; pa_release_pools() frees them.
-namespace {
-constexpr size_t kPinnedPoolMax = size_t(1) << 30;
-struct PinnedBlock {
-    void* ptr;
-    size_t size;
-};
-std::mutex& g_pin_mu = *new std::mutex;
-std::vector<PinnedBlock>& g_pin = *new std::vector<PinnedBlock>;
-size_t g_pin_bytes = 0;
-}  // namespace
-void* pinned_take(size_t bytes, size_t* got) {
-    {  // size classes (2^k and 1.5 x 2^k from 64 KB up): batches of slightly different sizes -- the call combiner's -- meet in the pool
-        size_t c = size_t(64) << 10;
-        while (c < bytes) c = ((c & (c - 1)) == 0 && c + c / 2 >= bytes) ? c + c / 2 : ((c & (c - 1)) == 0 ? c * 2 : (c / 3) * 4);
-        bytes = c;
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        size_t best = g_pin.size();
-        for (size_t i = 0; i < g_pin.size(); ++i)
-            // (best fit, and never a block more than twice the request + 64 KB: a 100 KB request must not take the pooled 30 MB text
-            //  buffer and send the next text request back to hipHostMalloc)
-            if (g_pin[i].size >= bytes && g_pin[i].size <= 2 * bytes + 65536 && (best == g_pin.size() || g_pin[i].size < g_pin[best].size)) best = i;
-        if (best != g_pin.size()) {
-            void* p = g_pin[best].ptr;
-            *got = g_pin[best].size;
-            g_pin_bytes -= g_pin[best].size;
-            g_pin.erase(g_pin.begin() + (long)best);
-            return p;
-        }
-    }
-    void* hp = nullptr;
-    if (!hip_ok(hipHostMalloc(&hp, bytes, hipHostMallocDefault), "hipHostMalloc(pinned pool)")) return nullptr;
-    *got = bytes;
-    return hp;
-}
-void pinned_give(void* ptr, size_t size) {
-    if (!ptr) return;
-    std::vector<PinnedBlock> drop;
-    {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        g_pin.push_back({ptr, size});
-        g_pin_bytes += size;
-        while (g_pin_bytes > kPinnedPoolMax && !g_pin.empty()) {
-            drop.push_back(g_pin.front());
-            g_pin_bytes -= g_pin.front().size;
-            g_pin.erase(g_pin.begin());
-        }
-    }
-    for (const PinnedBlock& b : drop) (void)hipHostFree(b.ptr);
-}
-// ... and so are the chunk streams of pa_batch_align (hipStreamDestroy costs ~3 ms each: a C4 batch of four chunks spent 12 ms of its
-// `close` there); per device, idle when they are handed back (the batch's destructor has waited for the device).
-namespace {
-std::vector<std::pair<int, hipStream_t>>& g_streams = *new std::vector<std::pair<int, hipStream_t>>;
-}
-hipStream_t stream_take() {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        for (size_t i = 0; i < g_streams.size(); ++i)
-            if (g_streams[i].first == dev) {
-                hipStream_t s = g_streams[i].second;
-                g_streams.erase(g_streams.begin() + (long)i);
-                return s;
-            }
-    }
-    hipStream_t s = nullptr;
-    if (!hip_ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate")) return nullptr;
-    return s;
-}
-// The batch's own stream (a default, blocking stream: its work orders with the synchronous copies of the creation) is pooled as well:
-// hipStreamCreate costs 2 ms, a quarter of what a batch of sixteen short pairs takes from creation to destruction (round 5: the call
-// combiner behind pa_align creates such batches a hundred times a second).  A stream goes back only after its batch has waited for the device.
-namespace {
-std::vector<std::pair<int, hipStream_t>>& g_bstreams = *new std::vector<std::pair<int, hipStream_t>>;
-}
-hipStream_t bstream_take() {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        for (size_t i = 0; i < g_bstreams.size(); ++i)
-            if (g_bstreams[i].first == dev) {
-                hipStream_t s = g_bstreams[i].second;
-                g_bstreams.erase(g_bstreams.begin() + (long)i);
-                return s;
-            }
-    }
-    hipStream_t s = nullptr;
-    if (!hip_ok(hipStreamCreate(&s), "hipStreamCreate")) return nullptr;
-    return s;
-}
-void bstream_give(hipStream_t s, int dev) {
-    if (!s) return;
-    {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        if (g_bstreams.size() < 32) {
-            g_bstreams.emplace_back(dev, s);
-            return;
-        }
-    }
-    (void)hipStreamDestroy(s);
-}
-void stream_give(hipStream_t s, int dev) {  // dev: the device the stream was created on (a batch may be destroyed from a thread bound to another)
-    if (!s) return;
-    {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        if (g_streams.size() < 64) {
-            g_streams.emplace_back(dev, s);
-            return;
-        }
-    }
-    (void)hipStreamDestroy(s);
-}
-void pinned_release_all() {
-    {
-        std::vector<std::pair<int, hipStream_t>> st;
-        {
-            std::lock_guard<std::mutex> lk(g_pin_mu);
-            st.swap(g_streams);
-        }
-        for (auto& x : st) (void)hipStreamDestroy(x.second);
-    }
-    std::vector<PinnedBlock> all;
-    {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        all.swap(g_pin);
-        g_pin_bytes = 0;
-    }
-    for (const PinnedBlock& b : all) (void)hipHostFree(b.ptr);
-}
-
-// A batch lets go of a dozen buffers at once: its destructor waits for the device ONCE and the releases that follow skip their wait.
-static thread_local bool g_release_synced = false;
-void release_scope_begin() {
-    (void)hipDeviceSynchronize();
-    g_release_synced = true;
-}
-// ... or the owner waited for everything that ever touched its buffers itself (a batch: its own streams) and only declares the scope:
-// a device-wide wait also waits for every OTHER batch in flight -- eight batches of the call combiner side by side each waited for the
-// other seven's kernels (round 5: 40 ms per call at 64 callers instead of 8)
-void release_scope_begin_waited() { g_release_synced = true; }
-void release_scope_end() { g_release_synced = false; }
-
-void DeviceBuf::release() {
-    if (ptr) {
-        if (cache_on() && g_release_synced) {  // (inside a release scope the device has been waited for: any size goes to the cache)
-            int cur = device;
-            (void)hipGetDevice(&cur);
-            if (cur == device) {
-                free_blocks(cache_put(device, ptr, size));
-                ptr = nullptr;
-                size = 0;
-                return;
-            }
-        }
-        if (size >= kCacheMin && cache_on()) {
-            // hipFree waits for the device before it lets a buffer go; a cached block may be handed to another thread at once, so
-            // this waits too (whoever must not wait -- the sweep's pool while passes are in flight -- never frees, engine_hip.hip)
-            int cur = device;
-            (void)hipGetDevice(&cur);
-            if (cur != device) (void)hipSetDevice(device);  // (a batch destroyed from a thread bound to another GPU)
-            (void)hipDeviceSynchronize();
-            if (cur != device) (void)hipSetDevice(cur);
-            free_blocks(cache_put(device, ptr, size));
-        } else {
-            (void)hipFree(ptr);
-        }
-    }
-    ptr = nullptr;
-    size = 0;
-}
-
-// Both encodings of ONE pair in one launch (the single-pair engine's per-call set-up, round 6: eight stream operations were four): the
-// first blocks pack a -- every word of `codes` up to code_words, so the padding the kernels read past the last column is zeroed here --,
-// the others build b's profile.  `bad` may be host-mapped: every writer stores the same 1.
-__global__ void encode_pair_kernel(const uint8_t* __restrict__ a, int n, uint32_t* __restrict__ codes, int code_words, int a_blocks,
-                                   const uint8_t* __restrict__ b, int m, uint64_t* __restrict__ prof, int prof_words, uint32_t* bad) {
-    if ((int)blockIdx.x < a_blocks) {
-        const int i = blockIdx.x * blockDim.x + threadIdx.x;
-        if (i >= code_words) return;
-        uint32_t w = 0;
-        bool invalid = false;
-        for (int k = 0; k < 16; ++k) {
-            const int c = i * 16 + k;
-            if (c < n) {
-                const int r = rank_acgt(a[c]);
-                invalid |= r < 0;
-                w |= (uint32_t)(r & 3) << (2 * k);
-            }
-        }
-        codes[i] = w;
-        if (invalid) __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
-    }
-    const int word = ((int)blockIdx.x - a_blocks) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (word >= prof_words) return;
-    const int lane = threadIdx.x & 63;
-    const int j = word * 64 + lane;
-    int r = 3;
-    bool invalid = false;
-    if (j < m) {
-        r = rank_acgt(b[j]);
-        invalid = r < 0;
-        r &= 3;
-    }
-    const uint64_t nb0 = __ballot(((r & 1) ^ 1) != 0);
-    const uint64_t nb1 = __ballot((((r >> 1) & 1) ^ 1) != 0);
-    if (lane == 0) {
-        prof[2 * word] = nb0;
-        prof[2 * word + 1] = nb1;
-    }
-    if (invalid) __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-bool encode_pair_device(const uint8_t* d_a, int n, uint32_t* d_codes, int code_words, const uint8_t* d_b, int m, uint64_t* d_prof, uint32_t* bad,
-                        hipStream_t s) {
-    const int a_blocks = (code_words + 255) / 256, prof_words = (m + 63) / 64, b_blocks = (prof_words + 3) / 4;
-    if (a_blocks + b_blocks == 0) return true;
-    hipLaunchKernelGGL(encode_pair_kernel, dim3((unsigned)(a_blocks + b_blocks)), dim3(256), 0, s, d_a, n, d_codes, code_words, a_blocks, d_b, m, d_prof,
-                       prof_words, bad);
-    return hip_ok(hipGetLastError(), "encode_pair_kernel");
-}
-
-bool encode_a_device(const uint8_t* d_a, int n, uint32_t* d_codes, uint32_t* d_bad, hipStream_t s) {
-    const int nwords = (n + 15) / 16;
-    if (nwords == 0) return true;
-    hipLaunchKernelGGL(encode_a_kernel, dim3((nwords + 255) / 256), dim3(256), 0, s, d_a, n, d_codes, nwords, d_bad);
-    return hip_ok(hipGetLastError(), "encode_a_kernel");
-}
-
-bool build_b_device(const uint8_t* d_b, int m, uint64_t* d_prof, uint32_t* d_bad, hipStream_t s) {
-    const int nwords = (m + 63) / 64;
-    if (nwords == 0) return true;
-    hipLaunchKernelGGL(build_b_kernel, dim3((nwords + 3) / 4), dim3(256), 0, s, d_b, m, d_prof, nwords, d_bad);
-    return hip_ok(hipGetLastError(), "build_b_kernel");
-}
-
-// How a rectangle of w words is cut into strips.  Chained strips all have the kernel's height (32*k words).  A sequential
-// pair may finish with up to kMaxTail1[k] short strips of 32 words when that is cheaper than one mostly empty tall strip
-// (a k = 1 step costs about 0.67 / 0.43 / 0.25 of a k = 2 / 4 / 8 step).
-StripPlan strip_plan(int w, int k, bool sequential) {
-    StripPlan p;
-    const int wps = kWordsPerStrip * k;
-    p.full = w / wps;
-    const int r = w - p.full * wps;
-    if (r == 0) return p;
-    const int max_tail1 = !sequential ? 0 : (k == 2 ? 1 : (k == 4 ? 2 : (k >= 8 ? 3 : 0)));
-    const int t1 = (r + kWordsPerStrip - 1) / kWordsPerStrip;
-    if (t1 <= max_tail1) p.tail1 = t1;
-    else p.full += 1;
-    return p;
-}
-
-// Plan the strips of one rectangle: words [w0, w1) x n columns, r.k subwords per lane.
-void plan_rect(std::vector<StripJob>& jobs, const RectPlan& r) {
-    const int w = r.w1 - r.w0;
-    const int wps = kWordsPerStrip * r.k;
-    const StripPlan sp = strip_plan(w, r.k, r.pingpong);
-    const int S = sp.strips();
-    int word = 0;
-    for (int s = 0; s < S; ++s) {
-        StripJob j;
-        std::memset(&j, 0, sizeof j);
-        const bool tall = s < sp.full;
-        j.k = tall ? r.k : 1;
-        j.a_codes = r.a_codes;
-        j.b_prof = r.b_prof;
-        j.v = r.v;
-        j.n = r.n;
-        j.col0 = r.col0;
-        j.word0 = r.w0 + word;
-        const int words = std::min(tall ? wps : kWordsPerStrip, w - word);
-        j.nlanes = 2 * words;
-        j.flags = r.v_init_one ? kJobVInitOne : 0;
-        j.tail_rows = -1;
-        if (s == 0) {
-            j.hin_arr = r.hin_arr;  // nullptr => +1
-        } else {
-            j.hin_gran = r.gran + (size_t)(r.pingpong ? ((s - 1) & 1) : (s - 1)) * r.gran_stride;
-        }
-        if (s + 1 < S) {
-            j.hout_gran = r.gran + (size_t)(r.pingpong ? (s & 1) : s) * r.gran_stride;
-            j.exact_tail = 1;  // full strips anyway
-        } else {
-            j.hout_arr = r.hout_arr;
-            j.sum_out = r.sum_out;
-            j.tail_rows = r.tail_rows;
-            j.exact_tail = (r.exact_end || r.hout_arr) ? 1 : 0;
-        }
-        if (r.values) {
-            j.values = r.values;
-            j.fill_stride = r.fill_stride;
-            j.fill_word0 = r.fill_word0 + word;
-        }
-        j.ckpt = r.ckpt;
-        j.ckpt_stride = r.ckpt_stride;
-        word += words;
-        jobs.push_back(j);
-    }
-}
-
-size_t rect_granules(int n, int w, int k, bool pingpong) {
-    const int S = strip_plan(w, k, pingpong).strips();
-    const size_t G = (size_t)(n + 31) / 32;  // one 8-byte granule per 32 columns per strip boundary
-    const int rows = pingpong ? std::min(S - 1, 2) : S - 1;
-    return S > 1 ? (size_t)rows * G : 0;
-}
-
-// Residency cap.  Every strip of a rectangle advances at the pace of the most crowded SIMD it touches, and the
-// dispatcher does not balance SIMDs by itself.  Blocks are 4 wavefronts (one per SIMD of a CU); an unused dynamic-LDS
-// request sized so that only `W = ceil(blocks / CUs)` blocks fit in a CU's 160 KB makes W the hard maximum of
-// wavefronts per SIMD instead of an average.
-static unsigned residency_lds_bytes(int blocks) {
-    static const bool off = getenv("PA_STRIP_NO_LDS_CAP") != nullptr;
-    if (off) return 0;
-    const int cus = g_device_props_cus > 0 ? g_device_props_cus : 256;
-    const int W = (blocks + cus - 1) / cus;
-    if (W > 7) return 0;  // beyond the register-file limit nothing is gained
-    const unsigned lds_total = 160u * 1024u;
-    return ((lds_total / (unsigned)(W + 1)) + 1024u) & ~1023u;  // W blocks fit, W + 1 do not
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: set it once per (kernel, device), from any
-// thread (the library is re-entrant; pa_set_device selects the device per thread).
-static bool ensure_max_lds(const void* kern) {
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> done;
-    int dev = 0;
-    if (!hip_ok(hipGetDevice(&dev), "hipGetDevice")) return false;
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.count({kern, dev})) return true;
-    if (!hip_ok(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "hipFuncSetAttribute(max dynamic LDS)")) return false;
-    done.insert({kern, dev});
-    return true;
-}
-
-template <class Kern>
-static bool launch_one(Kern kern, int grid, int block_waves, unsigned lds, hipStream_t s, const StripJob* d_jobs, int njobs,
-                       uint32_t* d_ticket_err) {
-    if (!ensure_max_lds(reinterpret_cast<const void*>(kern))) return false;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * block_waves), lds, s, d_jobs, njobs, d_ticket_err, d_ticket_err + 1);
-    return hip_ok(hipGetLastError(), "strip_kernel launch");
-}
-
-bool launch_strips(const StripJob* d_jobs, int njobs, bool fill, uint32_t* d_ticket_err, hipStream_t s, bool zero_ticket, bool scatter,
-                   int k, int block_waves, bool ckpt) {
-    if (njobs == 0) return true;
-    // d_ticket_err[0] = ticket, [1] = err
-    if (zero_ticket && !hip_ok(hipMemsetAsync(d_ticket_err, 0, 2 * sizeof(uint32_t), s), "memset ticket")) return false;
-    if (block_waves < 1 || block_waves > kStripMaxBlockWaves) block_waves = kStripBlockWaves;
-    if (const char* e = getenv("PA_STRIP_BLOCK_WAVES")) block_waves = std::min(std::max(atoi(e), 1), kStripMaxBlockWaves);  // experiments
-    if (k < 4 && block_waves > kStripBlockWaves) block_waves = kStripBlockWaves;  // (the k = 1, 2 kernels are built for 256 threads)
-    const int grid = (njobs + block_waves - 1) / block_waves;  // one wave per job; jobs beyond residency queue behind their
-                                                               // producers (ticket order)
-    const unsigned lds = block_waves >= kStripBlockWaves ? residency_lds_bytes(grid) : 0;
-    if ((scatter || fill) && (k != 1 || ckpt)) {
-        set_error("fill / scatter strips are built for k = 1 without checkpoints only");
-        return false;
-    }
-    // tall cost-only strips take their eq words from LDS: one slice per wavefront of the block
-    static const bool no_ldseq = getenv("PA_STRIP_NO_LDSEQ") != nullptr;
-    if (!no_ldseq && !scatter && !fill && (k == 4 || k == 8)) {
-        const unsigned need = (unsigned)block_waves * (k == 8 ? LdsEq<8>::kWaveBytes : LdsEq<4>::kWaveBytes);
-        const unsigned l = std::max(lds, need);
-        if (ckpt && k == 4) return launch_one(strip_kernel<4, false, false, true, true>, grid, block_waves, l, s, d_jobs, njobs, d_ticket_err);
-        if (ckpt && k == 8) return launch_one(strip_kernel<8, false, false, true, true>, grid, block_waves, l, s, d_jobs, njobs, d_ticket_err);
-        if (k == 4) return launch_one(strip_kernel<4, false, false, false, true>, grid, block_waves, l, s, d_jobs, njobs, d_ticket_err);
-        return launch_one(strip_kernel<8, false, false, false, true>, grid, block_waves, l, s, d_jobs, njobs, d_ticket_err);
-    }
-    if (ckpt) {
-        if (k == 1) return launch_one(strip_kernel<1, false, false, true>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-        if (k == 2) return launch_one(strip_kernel<2, false, false, true>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-        if (k == 4) return launch_one(strip_kernel<4, false, false, true>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-        if (k == 8) return launch_one(strip_kernel<8, false, false, true>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-    }
-    if (scatter && fill) return launch_one(strip_kernel<1, true, true>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-    if (scatter) return launch_one(strip_kernel<1, false, true>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-    if (fill) return launch_one(strip_kernel<1, true, false>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-    if (k == 1) return launch_one(strip_kernel<1, false, false>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-    if (k == 2) return launch_one(strip_kernel<2, false, false>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-    if (k == 4) return launch_one(strip_kernel<4, false, false>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-    if (k == 8) return launch_one(strip_kernel<8, false, false>, grid, block_waves, lds, s, d_jobs, njobs, d_ticket_err);
-    set_error("unsupported strip height k=%d", k);
-    return false;
-}
-
-template <int K, bool CKPT>
-static bool launch_pairs_k(const StripJob* d_jobs, const int32_t* d_first, int npairs, uint32_t* d_err, hipStream_t s, int grid, unsigned lds) {
-    // tall strips take their eq words from LDS (strip_kernel.hpp LdsEq): one slice per wavefront of the block
-    static const bool no_ldseq = getenv("PA_PAIR_NO_LDSEQ") != nullptr;
-    if (K >= 4 && !no_ldseq) {
-        constexpr bool L = K >= 4;  // (keeps the K < 4 instantiations out of the binary)
-        const unsigned need = (unsigned)kStripBlockWaves * LdsEq<K>::kWaveBytes;
-        if (!ensure_max_lds(reinterpret_cast<const void*>(pair_kernel<K, CKPT, L>))) return false;
-        hipLaunchKernelGGL((pair_kernel<K, CKPT, L>), dim3(grid), dim3(64 * kStripBlockWaves), std::max(lds, need), s, d_jobs, d_first, npairs, d_err);
-        return hip_ok(hipGetLastError(), "pair_kernel launch");
-    }
-    if (!ensure_max_lds(reinterpret_cast<const void*>(pair_kernel<K, CKPT, false>))) return false;
-    hipLaunchKernelGGL((pair_kernel<K, CKPT, false>), dim3(grid), dim3(64 * kStripBlockWaves), lds, s, d_jobs, d_first, npairs, d_err);
-    return hip_ok(hipGetLastError(), "pair_kernel launch");
-}
-
-bool launch_pairs(const StripJob* d_jobs, const int32_t* d_first, int npairs, uint32_t* d_ticket_err, hipStream_t s, int k, bool ckpt) {
-    if (npairs == 0) return true;
-    const int grid = (npairs + kStripBlockWaves - 1) / kStripBlockWaves;
-    const unsigned lds = residency_lds_bytes(grid);
-    uint32_t* e = d_ticket_err + 1;
-    if (!ckpt) {
-        if (k == 1) return launch_pairs_k<1, false>(d_jobs, d_first, npairs, e, s, grid, lds);
-        if (k == 2) return launch_pairs_k<2, false>(d_jobs, d_first, npairs, e, s, grid, lds);
-        if (k == 4) return launch_pairs_k<4, false>(d_jobs, d_first, npairs, e, s, grid, lds);
-        if (k == 8) return launch_pairs_k<8, false>(d_jobs, d_first, npairs, e, s, grid, lds);
-        if (k == 16) return launch_pairs_k<16, false>(d_jobs, d_first, npairs, e, s, grid, 0);
-    } else {
-        if (k == 1) return launch_pairs_k<1, true>(d_jobs, d_first, npairs, e, s, grid, lds);
-        if (k == 2) return launch_pairs_k<2, true>(d_jobs, d_first, npairs, e, s, grid, lds);
-        if (k == 4) return launch_pairs_k<4, true>(d_jobs, d_first, npairs, e, s, grid, lds);
-        if (k == 8) return launch_pairs_k<8, true>(d_jobs, d_first, npairs, e, s, grid, lds);
-    }
-    set_error("unsupported strip height k=%d", k);
-    return false;
-}
 
 // CIGAR text on the GPU.  trace_kernel leaves each pair's elements (count << 2 | op) from the END of the alignment to its
 // start; one wavefront per pair turns them into the reference's string form (count omitted when 1, ops "=XID",
@@ -870,488 +98,6 @@ __global__ __launch_bounds__(64) void format_pack_kernel(const uint32_t* __restr
 }  // namespace pa
 
 using namespace pa;
-
-// ================================================================================================
-// C ABI
-// ================================================================================================
-
-extern "C" const char* pa_last_error(void) { return g_last_error.c_str(); }
-
-extern "C" int pa_device_count(void) {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess) return 0;
-    return cnt;
-}
-
-extern "C" int pa_set_device(int device) {
-    if (!hip_ok(hipSetDevice(device), "hipSetDevice")) return PA_E_HIP;
-    return 0;
-}
-
-extern "C" int pa_bp_profile_build(const uint8_t* a, size_t n, const uint8_t* b, size_t m, uint64_t* a2,
-                                   uint64_t* b2) {
-    if (!ensure_device()) return PA_E_HIP;
-    const size_t w = (m + 63) / 64, cw = (n + 15) / 16;
-    DeviceBuf d_a, d_b, d_codes, d_prof, d_bad;
-    if (!d_a.alloc(n) || !d_b.alloc(m) || !d_codes.alloc(cw * 4) || !d_prof.alloc(w * 16) || !d_bad.alloc(4))
-        return PA_E_HIP;
-    hipStream_t s = 0;
-    if (n && !hip_ok(hipMemcpyAsync(d_a.ptr, a, n, hipMemcpyHostToDevice, s), "H2D a")) return PA_E_HIP;
-    if (m && !hip_ok(hipMemcpyAsync(d_b.ptr, b, m, hipMemcpyHostToDevice, s), "H2D b")) return PA_E_HIP;
-    if (!hip_ok(hipMemsetAsync(d_bad.ptr, 0, 4, s), "memset")) return PA_E_HIP;
-    if (!encode_a_device(d_a.as<uint8_t>(), (int)n, d_codes.as<uint32_t>(), d_bad.as<uint32_t>(), s)) return PA_E_HIP;
-    if (!build_b_device(d_b.as<uint8_t>(), (int)m, d_prof.as<uint64_t>(), d_bad.as<uint32_t>(), s)) return PA_E_HIP;
-    std::vector<uint32_t> codes(cw);
-    uint32_t bad = 0;
-    if (cw && !hip_ok(hipMemcpyAsync(codes.data(), d_codes.ptr, cw * 4, hipMemcpyDeviceToHost, s), "D2H codes")) return PA_E_HIP;
-    if (w && !hip_ok(hipMemcpyAsync(b2, d_prof.ptr, w * 16, hipMemcpyDeviceToHost, s), "D2H prof")) return PA_E_HIP;
-    if (!hip_ok(hipMemcpyAsync(&bad, d_bad.ptr, 4, hipMemcpyDeviceToHost, s), "D2H bad")) return PA_E_HIP;
-    if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
-    if (bad) {
-        set_error("sequence contains a base outside ACGT");
-        return PA_E_INVALID_BASE;
-    }
-    for (size_t i = 0; i < n; ++i) {  // exploded Bits of a (profile.rs:116-125)
-        const uint32_t r = (codes[i / 16] >> (2 * (i % 16))) & 3u;
-        a2[2 * i] = 0ull - (uint64_t)(r & 1);
-        a2[2 * i + 1] = 0ull - (uint64_t)((r >> 1) & 1);
-    }
-    return 0;
-}
-
-// Shared implementation of pa_bp_compute / pa_bp_fill on host buffers.
-static int32_t rect_host(const uint64_t* a2, size_t n, const uint64_t* b2, size_t w, uint64_t* h2, uint64_t* v2,
-                         int exact_end, uint64_t* values) {
-    if (!ensure_device()) return INT32_MIN;
-    if (n > (size_t)INT32_MAX / 2 || w > (size_t)INT32_MAX / 64) {
-        set_error("rectangle too large");
-        return INT32_MIN;
-    }
-    if (n == 0) return 0;
-    if (w == 0) {  // no rows: bottom == top
-        int32_t s = 0;
-        for (size_t i = 0; i < n; ++i) s += (int32_t)h2[2 * i] - (int32_t)h2[2 * i + 1];
-        return s;
-    }
-    const size_t cw = (n + 15) / 16;
-    std::vector<uint32_t> codes(cw, 0);
-    std::vector<uint8_t> hin(n, 0);
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t r = (uint32_t)(a2[2 * i] & 1) | ((uint32_t)(a2[2 * i + 1] & 1) << 1);
-        codes[i / 16] |= r << (2 * (i % 16));
-        hin[i] = (uint8_t)((h2[2 * i] & 1) | ((h2[2 * i + 1] & 1) << 1));
-    }
-    const size_t ngran = rect_granules((int)n, (int)w);
-    DeviceBuf d_codes, d_prof, d_v, d_hin, d_hout, d_gran, d_jobs, d_misc, d_values;
-    if (!d_codes.alloc(cw * 4) || !d_prof.alloc(w * 16) || !d_v.alloc(w * 16) || !d_hin.alloc(n) ||
-        !d_hout.alloc(n) || !d_gran.alloc(ngran * 8) || !d_misc.alloc(16))
-        return INT32_MIN;
-    if (values && !d_values.alloc(n * w * 16)) return INT32_MIN;
-    hipStream_t s = 0;
-    bool ok = hip_ok(hipMemcpyAsync(d_codes.ptr, codes.data(), cw * 4, hipMemcpyHostToDevice, s), "H2D") &&
-              hip_ok(hipMemcpyAsync(d_prof.ptr, b2, w * 16, hipMemcpyHostToDevice, s), "H2D") &&
-              hip_ok(hipMemcpyAsync(d_v.ptr, v2, w * 16, hipMemcpyHostToDevice, s), "H2D") &&
-              hip_ok(hipMemcpyAsync(d_hin.ptr, hin.data(), n, hipMemcpyHostToDevice, s), "H2D") &&
-              hip_ok(hipMemsetAsync(d_gran.ptr, 0, std::max<size_t>(ngran * 8, 16), s), "memset gran") &&
-              hip_ok(hipMemsetAsync(d_misc.ptr, 0, 16, s), "memset misc");
-    if (!ok) return INT32_MIN;
-
-    std::vector<StripJob> jobs;
-    RectPlan r;
-    r.a_codes = d_codes.as<uint32_t>();
-    r.b_prof = d_prof.as<uint32_t>();
-    r.v = d_v.as<uint32_t>();
-    r.n = (int)n;
-    r.w0 = 0;
-    r.w1 = (int)w;
-    r.hin_arr = d_hin.as<uint8_t>();
-    r.hout_arr = d_hout.as<uint8_t>();
-    r.gran = d_gran.as<uint64_t>();
-    r.gran_stride = (n + 31) / 32;
-    r.sum_out = d_misc.as<int32_t>() + 2;
-    r.exact_end = exact_end != 0 || values != nullptr;
-    if (!exact_end && !values) r.hout_arr = nullptr;  // padded-tail path: the bottom row itself is not an output
-    r.values = values ? d_values.as<uint32_t>() : nullptr;
-    r.fill_stride = (int)w;
-    r.fill_word0 = 0;
-    plan_rect(jobs, r);
-    if (!d_jobs.alloc(jobs.size() * sizeof(StripJob))) return INT32_MIN;
-    ok = hip_ok(hipMemcpyAsync(d_jobs.ptr, jobs.data(), jobs.size() * sizeof(StripJob), hipMemcpyHostToDevice, s), "H2D jobs") &&
-         launch_strips(d_jobs.as<StripJob>(), (int)jobs.size(), values != nullptr, d_misc.as<uint32_t>(), s);
-    if (!ok) return INT32_MIN;
-    uint32_t misc[4] = {0, 0, 0, 0};
-    std::vector<uint8_t> hout(n, 0);
-    ok = hip_ok(hipMemcpyAsync(misc, d_misc.ptr, 16, hipMemcpyDeviceToHost, s), "D2H") &&
-         hip_ok(hipMemcpyAsync(v2, d_v.ptr, w * 16, hipMemcpyDeviceToHost, s), "D2H") &&
-         (r.hout_arr == nullptr || hip_ok(hipMemcpyAsync(hout.data(), d_hout.ptr, n, hipMemcpyDeviceToHost, s), "D2H")) &&
-         (!values || hip_ok(hipMemcpyAsync(values, d_values.ptr, n * w * 16, hipMemcpyDeviceToHost, s), "D2H values")) &&
-         hip_ok(hipStreamSynchronize(s), "sync");
-    if (!ok) return INT32_MIN;
-    if (misc[1] != PA_ERR_NONE) {
-        set_error("device spin timeout (err=%u)", misc[1]);
-        return INT32_MIN;
-    }
-    if (r.hout_arr) {
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t x = hout[i] & 3u;
-            h2[2 * i] = x & 1;
-            h2[2 * i + 1] = x >> 1;
-        }
-    }
-    // exact_end == 0: the reference leaves h unspecified (simd.rs:184-225); h2 is left untouched.
-    return (int32_t)misc[2];
-}
-
-extern "C" int32_t pa_bp_compute(const uint64_t* a2, size_t n, const uint64_t* b2, size_t w, uint64_t* h2, uint64_t* v2,
-                                 int exact_end) {
-    return rect_host(a2, n, b2, w, h2, v2, exact_end, nullptr);
-}
-
-extern "C" int32_t pa_bp_fill(const uint64_t* a2, size_t n, const uint64_t* b2, size_t w, uint64_t* h2, uint64_t* v2,
-                              uint64_t* values) {
-    return rect_host(a2, n, b2, w, h2, v2, 1, values);
-}
-
-// ---- semi-global search (pa_bitpacking::search, pa-bitpacking/src/search.rs:46-120) ------------------------------
-
-// One thread per 16 columns: text ASCII -> packed CC codes (A0 C1 T2 G3, either case; profile.rs:30-38).
-__global__ void encode_text_cc_kernel(const uint8_t* __restrict__ a, int n, uint32_t* __restrict__ codes, int nwords,
-                                      uint32_t* __restrict__ bad) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nwords) return;
-    uint32_t w = 0;
-    bool invalid = false;
-    for (int k = 0; k < 16; ++k) {
-        const int c = i * 16 + k;
-        if (c < n) {
-            const uint8_t ch = a[c] & 0xDF;  // upper-case
-            const int r = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'T' ? 2 : ch == 'G' ? 3 : -1;
-            invalid |= r < 0;
-            w |= (uint32_t)(r & 3) << (2 * k);
-        }
-    }
-    codes[i] = w;
-    if (invalid) atomicOr(bad, 1u);
-}
-
-// ---- semi-global search (pa-bitpacking/src/search.rs) ------------------------------------------------------------
-
-// ScatterProfile of the pattern (profile.rs:39-63: wildcards N/* (any), Y (C|T), R (A|G); padding rows match everything)
-// and the left column of the search (every ceil(i / unmatched_cost)-th row costs 1, search.rs:57-65).
-int pa::search_profile(const uint8_t* pattern, size_t plen, float unmatched_cost, std::vector<uint64_t>& prof, std::vector<uint64_t>& v0) {
-    const size_t w = (plen + 63) / 64;
-    prof.assign(4 * std::max<size_t>(w, 1), 0);
-    for (size_t j = 0; j < plen; ++j) {
-        int mask;
-        switch (pattern[j]) {
-            case 'a': case 'A': mask = 1; break;
-            case 'c': case 'C': mask = 2; break;
-            case 't': case 'T': mask = 4; break;
-            case 'g': case 'G': mask = 8; break;
-            case 'n': case 'N': case '*': mask = 15; break;
-            case 'y': case 'Y': mask = 6; break;
-            case 'r': case 'R': mask = 9; break;
-            default: set_error("Unknown base in pattern"); return PA_E_INVALID_BASE;
-        }
-        for (int c = 0; c < 4; ++c)
-            if (mask & (1 << c)) prof[4 * (j / 64) + c] |= 1ull << (j % 64);
-    }
-    for (size_t j = plen; j < w * 64; ++j)
-        for (int c = 0; c < 4; ++c) prof[4 * (j / 64) + c] |= 1ull << (j % 64);
-    v0.assign(2 * std::max<size_t>(w, 1), 0);
-    if (unmatched_cost > 0.0f) {
-        for (size_t i = 0;; ++i) {
-            const size_t idx = (size_t)std::ceil((float)i / unmatched_cost);
-            if (idx >= plen) break;
-            v0[2 * (idx / 64)] |= 1ull << (idx % 64);
-        }
-    }
-    return 0;
-}
-
-namespace {
-
-// scatter_profile::compute::<2, _, 4, FILL>(text[0..n), pattern profile, h = zeros, v, exact_end = true, values)
-// (search.rs:71,152) on the GPU: v is updated in place, hrow[n] receives the bottom-row deltas (bit0 = +1, bit1 = -1),
-// values (optional) the V of every word after every column (values[col * w + word], two u64 each).
-int search_rect(const uint8_t* text, size_t n, const std::vector<uint64_t>& prof, size_t w, std::vector<uint64_t>& v,
-                std::vector<uint8_t>& hrow, std::vector<uint64_t>* values) {
-    hrow.assign(std::max<size_t>(n, 1), 0);
-    if (values) values->assign(n * w * 2, 0);
-    if (n == 0 || w == 0) return 0;
-    const bool fill = values != nullptr;
-    const size_t cw = (n + 15) / 16 + 2, ngran = rect_granules((int)n, (int)w);
-    DeviceBuf d_text, d_codes, d_prof, d_v, d_hin, d_hout, d_gran, d_jobs, d_misc, d_values;
-    if (!d_text.alloc(n) || !d_codes.alloc(cw * 4) || !d_prof.alloc(w * 32) || !d_v.alloc(w * 16) || !d_hin.alloc(n) ||
-        !d_hout.alloc(n) || !d_gran.alloc(ngran * 8) || !d_misc.alloc(16) || (fill && !d_values.alloc(n * w * 16)))
-        return PA_E_HIP;
-    hipStream_t s = 0;
-    bool ok = hip_ok(hipMemcpyAsync(d_text.ptr, text, n, hipMemcpyHostToDevice, s), "H2D") &&
-              hip_ok(hipMemsetAsync(d_codes.ptr, 0, cw * 4, s), "memset") && hip_ok(hipMemsetAsync(d_misc.ptr, 0, 16, s), "memset") &&
-              hip_ok(hipMemsetAsync(d_hin.ptr, 0, n, s), "memset h") &&  // zeros along the top: start anywhere in the text
-              hip_ok(hipMemsetAsync(d_gran.ptr, 0, std::max<size_t>(ngran * 8, 16), s), "memset gran") &&
-              hip_ok(hipMemcpyAsync(d_prof.ptr, prof.data(), w * 32, hipMemcpyHostToDevice, s), "H2D") &&
-              hip_ok(hipMemcpyAsync(d_v.ptr, v.data(), w * 16, hipMemcpyHostToDevice, s), "H2D");
-    if (!ok) return PA_E_HIP;
-    const int nwords = (int)((n + 15) / 16);
-    hipLaunchKernelGGL(encode_text_cc_kernel, dim3((nwords + 255) / 256), dim3(256), 0, s, d_text.as<uint8_t>(), (int)n,
-                       d_codes.as<uint32_t>(), nwords, d_misc.as<uint32_t>() + 3);
-    std::vector<StripJob> jobs;
-    RectPlan r;
-    r.a_codes = d_codes.as<uint32_t>();
-    r.b_prof = d_prof.as<uint32_t>();
-    r.v = d_v.as<uint32_t>();
-    r.n = (int)n;
-    r.w0 = 0;
-    r.w1 = (int)w;
-    r.hin_arr = d_hin.as<uint8_t>();
-    r.hout_arr = d_hout.as<uint8_t>();
-    r.gran = d_gran.as<uint64_t>();
-    r.gran_stride = (n + 31) / 32;
-    r.sum_out = d_misc.as<int32_t>() + 2;
-    r.exact_end = true;
-    if (fill) {
-        r.values = d_values.as<uint32_t>();
-        r.fill_stride = (int)w;
-        r.fill_word0 = 0;
-    }
-    plan_rect(jobs, r);
-    if (!d_jobs.alloc(jobs.size() * sizeof(StripJob))) return PA_E_HIP;
-    uint32_t misc[4] = {0, 0, 0, 0};
-    ok = hip_ok(hipMemcpyAsync(d_jobs.ptr, jobs.data(), jobs.size() * sizeof(StripJob), hipMemcpyHostToDevice, s), "H2D jobs") &&
-         launch_strips(d_jobs.as<StripJob>(), (int)jobs.size(), fill, d_misc.as<uint32_t>(), s, false, /*scatter=*/true) &&
-         hip_ok(hipMemcpyAsync(misc, d_misc.ptr, 16, hipMemcpyDeviceToHost, s), "D2H") &&
-         hip_ok(hipMemcpyAsync(v.data(), d_v.ptr, w * 16, hipMemcpyDeviceToHost, s), "D2H") &&
-         hip_ok(hipMemcpyAsync(hrow.data(), d_hout.ptr, n, hipMemcpyDeviceToHost, s), "D2H") &&
-         (!fill || hip_ok(hipMemcpyAsync(values->data(), d_values.ptr, n * w * 16, hipMemcpyDeviceToHost, s), "D2H values")) &&
-         hip_ok(hipStreamSynchronize(s), "sync");
-    if (!ok) return PA_E_HIP;
-    if (misc[3]) {
-        set_error("text must be actgACTG only");
-        return PA_E_INVALID_BASE;
-    }
-    if (misc[1] != PA_ERR_NONE) {
-        set_error("device spin timeout (err=%u)", misc[1]);
-        return PA_E_TIMEOUT;
-    }
-    return 0;
-}
-
-int32_t v_value(uint64_t p, uint64_t m) { return (int32_t)__builtin_popcountll(p) - (int32_t)__builtin_popcountll(m); }
-int32_t v_suffix(uint64_t p, uint64_t m, int j) {  // V::value_of_suffix, encoding.rs:35-40
-    const uint64_t mask = ~((1ull << (64 - j)) - 1);
-    return (int32_t)__builtin_popcountll(p & mask) - (int32_t)__builtin_popcountll(m & mask);
-}
-int32_t vec_value_to(const uint64_t* v, int64_t j) {  // V::value_to, encoding.rs:57-66
-    int32_t s = 0;
-    for (int64_t k = 0; k < j / 64; ++k) s += v_value(v[2 * k], v[2 * k + 1]);
-    if (j % 64 != 0) {
-        const uint64_t mask = (1ull << (j % 64)) - 1;
-        s += (int32_t)__builtin_popcountll(v[2 * (j / 64)] & mask) - (int32_t)__builtin_popcountll(v[2 * (j / 64) + 1] & mask);
-    }
-    return s;
-}
-int32_t vec_value_from(const uint64_t* v, size_t w, int64_t j) {  // V::value_from, encoding.rs:67-76
-    int32_t s = 0;
-    if (j % 64 != 0) s += v_suffix(v[2 * (j / 64)], v[2 * (j / 64) + 1], (int)(64 - j % 64));
-    for (size_t k = (size_t)((j + 63) / 64); k < w; ++k) s += v_value(v[2 * k], v[2 * k + 1]);
-    return s;
-}
-
-int search_out(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t tlen, float unmatched_cost, std::vector<int32_t>& out,
-               std::vector<uint64_t>& prof, std::vector<uint64_t>& v0) {
-    if (!ensure_device()) return PA_E_HIP;
-    if (!(unmatched_cost >= 0.0f && unmatched_cost <= 1.0f) || plen > (size_t)(1u << 30) || tlen > (size_t)(1u << 30)) {
-        set_error("pa_search: bad argument");
-        return PA_E_ARG;
-    }
-    const size_t w = (plen + 63) / 64, n = tlen;
-    if (const int rc = search_profile(pattern, plen, unmatched_cost, prof, v0)) return rc;
-    if (w == 0) {  // no rows: search_rect launches nothing, so the text is checked here (profile.rs:29-38 rejects it as well)
-        for (size_t i = 0; i < n; ++i) {
-            const uint8_t ch = text[i] & 0xDF;
-            if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') {
-                set_error("text must be actgACTG only");
-                return PA_E_INVALID_BASE;
-            }
-        }
-    }
-    std::vector<uint64_t> v(v0);
-    std::vector<uint8_t> hrow;
-    if (const int rc = search_rect(text, n, prof, w, v, hrow, nullptr)) return rc;
-    // Assemble the bottom row then the right column in reverse (search.rs:73-100).
-    out.clear();
-    const size_t padding = w * 64 - plen;
-    int32_t bsum = 0;
-    for (size_t j = 0; j < w; ++j) bsum += v_value(v0[2 * j], v0[2 * j + 1]);
-    size_t skipped = 0;
-    out.push_back(bsum);
-    for (size_t i = 0; i < n; ++i) {
-        bsum += (int32_t)(hrow[i] & 1) - (int32_t)((hrow[i] >> 1) & 1);
-        if (skipped < padding) skipped++;
-        else out.push_back(bsum);
-    }
-    for (size_t jj = w; jj-- > 0;) {
-        for (int j = 1; j <= 64; ++j) {
-            const int32_t val = bsum - v_suffix(v[2 * jj], v[2 * jj + 1], j) + v_suffix(v0[2 * jj], v0[2 * jj + 1], j);
-            if (skipped < padding) skipped++;
-            else out.push_back(val);
-        }
-        bsum -= v_value(v[2 * jj], v[2 * jj + 1]);
-        bsum += v_value(v0[2 * jj], v0[2 * jj + 1]);
-    }
-    if (out.size() != plen + tlen + 1) {
-        set_error("pa_search: internal length mismatch");
-        return PA_E_INTERNAL;
-    }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" int pa_search(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t tlen, float unmatched_cost,
-                         int32_t* out) {
-    std::vector<int32_t> o;
-    std::vector<uint64_t> prof, v0;
-    if (const int rc = search_out(pattern, plen, text, tlen, unmatched_cost, o, prof, v0)) return rc;
-    std::memcpy(out, o.data(), o.size() * sizeof(int32_t));
-    return 0;
-}
-
-// SearchResult::trace(idx), search.rs:104-228.
-extern "C" int pa_search_trace(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t tlen, float unmatched_cost, size_t idx,
-                               char** cigar_out, int32_t** path_out, size_t* npos_out) {
-    if (cigar_out) *cigar_out = nullptr;
-    if (path_out) *path_out = nullptr;
-    if (npos_out) *npos_out = 0;
-    std::vector<int32_t> out;
-    std::vector<uint64_t> prof, v0;
-    if (const int rc = search_out(pattern, plen, text, tlen, unmatched_cost, out, prof, v0)) return rc;
-    const size_t w = (plen + 63) / 64;
-    if (idx >= out.size()) {
-        set_error("pa_search_trace: idx out of range");
-        return PA_E_ARG;
-    }
-    // An empty pattern (w == 0) goes through the general path as in the reference: width 0, an empty re-fill whose cost 0 is
-    // the target, no step -- "" and [(idx, 0)].
-    // idx_to_pos, search.rs:105-115
-    int64_t pi, pj;
-    if (idx <= tlen) {
-        pi = (int64_t)idx;
-        pj = (int64_t)plen;
-    } else {
-        pi = (int64_t)tlen;
-        pj = (int64_t)plen - ((int64_t)idx - (int64_t)tlen);
-    }
-    int32_t target = out[idx];
-    if ((size_t)pi == tlen) target -= vec_value_from(v0.data(), w, pj);
-    // re-fill text[start..end) x pattern, doubling the width until the cost at `pos` is reproduced (search.rs:132-177)
-    size_t width = 2 * plen, start = 0;
-    const size_t end = (size_t)pi;
-    std::vector<uint64_t> values, first;
-    for (;;) {
-        start = end > width ? end - width : 0;
-        first = start == 0 ? v0 : std::vector<uint64_t>();
-        if (start != 0) {
-            first.assign(2 * w, 0);
-            for (size_t k = 0; k < w; ++k) first[2 * k] = ~0ull;
-        }
-        std::vector<uint64_t> v(first);
-        std::vector<uint8_t> hrow;
-        if (const int rc = search_rect(text + start, end - start, prof, w, v, hrow, &values)) return rc;
-        const int32_t cost = vec_value_to(v.data(), pj);
-        if (cost < target) {
-            set_error("pa_search_trace: found a path cheaper than the target cost");
-            return PA_E_INTERNAL;
-        }
-        if (cost == target) break;
-        if (start == 0) {
-            set_error("pa_search_trace: the full text does not reproduce the target cost");
-            return PA_E_INTERNAL;
-        }
-        width *= 2;
-    }
-    auto column = [&](int64_t i) -> const uint64_t* {  // fill[i - start]
-        return (size_t)i == start ? first.data() : values.data() + ((size_t)i - start - 1) * w * 2;
-    };
-    auto cost_at = [&](int64_t i, int64_t j) { return vec_value_to(column(i), j); };
-    auto tcode = [&](int64_t i) {  // CC order A C T G (profile.rs:23)
-        switch (text[i]) {
-            case 'a': case 'A': return 0;
-            case 'c': case 'C': return 1;
-            case 't': case 'T': return 2;
-            default: return 3;
-        }
-    };
-    engine::Cigar cigar;
-    std::vector<int32_t> path{(int32_t)pi, (int32_t)pj};
-    int32_t g = target;
-    while (pi > (int64_t)start && pj > 0) {  // search.rs:185-224
-        engine::I cnt = 0;
-        while (pi > (int64_t)start && pj > 0 && ((prof[4 * ((pj - 1) / 64) + tcode(pi - 1)] >> ((pj - 1) % 64)) & 1)) {
-            ++cnt;
-            --pi;
-            --pj;
-            path.push_back((int32_t)pi);
-            path.push_back((int32_t)pj);
-        }
-        if (cnt > 0) {
-            cigar.push_elem(engine::CigarElem{engine::CigarOp::Match, cnt});
-            continue;
-        }
-        if (cost_at(pi - 1, pj) == g - 1) {
-            --g;
-            --pi;
-            cigar.push_elem(engine::CigarElem{engine::CigarOp::Del, 1});
-        } else if (cost_at(pi, pj - 1) == g - 1) {
-            --g;
-            --pj;
-            cigar.push_elem(engine::CigarElem{engine::CigarOp::Ins, 1});
-        } else if (cost_at(pi - 1, pj - 1) == g - 1) {
-            --g;
-            --pi;
-            --pj;
-            cigar.push_elem(engine::CigarElem{engine::CigarOp::Sub, 1});
-        } else {
-            set_error("pa_search_trace: bad trace, stuck at (%lld, %lld)", (long long)pi, (long long)pj);
-            return PA_E_INTERNAL;
-        }
-        path.push_back((int32_t)pi);
-        path.push_back((int32_t)pj);
-    }
-    if (!(pi == 0 || g == 0)) {
-        set_error("pa_search_trace: trace ended inside the text with cost left");
-        return PA_E_INTERNAL;
-    }
-    cigar.reverse();
-    const std::string text_cigar = cigar.to_string();
-    const size_t np = path.size() / 2;
-    if (cigar_out) {
-        *cigar_out = (char*)std::malloc(text_cigar.size() + 1);
-        if (!*cigar_out) {
-            set_error("out of memory");
-            return PA_E_NOMEM;
-        }
-        std::memcpy(*cigar_out, text_cigar.c_str(), text_cigar.size() + 1);
-    }
-    if (path_out) {
-        *path_out = (int32_t*)std::malloc(std::max<size_t>(np, 1) * 2 * sizeof(int32_t));
-        if (!*path_out) {
-            if (cigar_out) {  // nothing half-delivered: the caller owns outputs only on success
-                std::free(*cigar_out);
-                *cigar_out = nullptr;
-            }
-            set_error("out of memory");
-            return PA_E_NOMEM;
-        }
-        for (size_t k = 0; k < np; ++k) {
-            (*path_out)[2 * k] = path[2 * (np - 1 - k)];
-            (*path_out)[2 * k + 1] = path[2 * (np - 1 - k) + 1];
-        }
-    }
-    if (npos_out) *npos_out = np;
-    return 0;
-}
 
 // ---- batched full DP ----------------------------------------------------------------------------
 
@@ -1513,7 +259,7 @@ static BatchShape choose_batch_shape(const size_t* a_len, const size_t* b_len, s
     static const double kLone[4] = {52.9, 76.5, 121.0, 200.0}, kFair[4] = {40.0, 66.0, 82.0, 138.0}, kSatChain[4] = {50.8, 65.0, 100.0, 150.0};
     static const double kShare[4] = {1.0, 0.85, 0.80, 0.78};  // per-wavefront step cost at 1, 2, 3, >= 4 wavefronts per SIMD
     static const int kK[4] = {1, 2, 4, 8};
-    const double simds = (double)(g_device_props_cus > 0 ? g_device_props_cus : 256) * 4.0;
+    const double simds = (double)device_cus() * 4.0;
     int env_k = 0, env_mode = 0;
     if (const char* e = getenv("PA_STRIP_K")) {
         const int k = atoi(e);
@@ -1643,7 +389,7 @@ static void plan_banded_pair(pa_batch* p, size_t i, int32_t t, std::vector<Strip
 static void choose_band_shape(pa_batch* p) {
     static const double kLone[4] = {52.9, 76.5, 103.0, 178.0};  // (k = 4, 8: eq words from LDS, 50 / 90 instead of 59 / 107 instructions)
     static const int kK[4] = {1, 2, 4, 8};
-    const double simds = (double)(g_device_props_cus > 0 ? g_device_props_cus : 256) * 4.0;
+    const double simds = (double)device_cus() * 4.0;
     size_t live = 0;
     for (size_t i = 0; i < p->pairs; ++i) live += (p->n[i] > 0 && p->m[i] > 0) ? 1 : 0;
     p->sequential = (double)live >= simds;
@@ -2082,7 +828,7 @@ static bool astar_full_jobs(pa_batch* p, const uint8_t* const* a, const uint8_t*
     if (launch_build) {
         // The matches of GCSH are part of the batch like the sequences they are derived from: found here, once, by the GPU (one wavefront
         // per pair, 12.8 KB of LDS each: twelve to a CU), on the batch's stream -- the first alignment call queues behind it.
-        const int cus = g_device_props_cus > 0 ? g_device_props_cus : 256;
+        const int cus = device_cus();
         static const int per_cu = getenv("PA_BUILD_WAVES_PER_CU") ? std::max(1, atoi(getenv("PA_BUILD_WAVES_PER_CU"))) : 12;
         const int grid = (int)std::min<size_t>(P, (size_t)cus * (size_t)per_cu);
         if (!hip_ok(hipMemsetAsync(p->d_bticket.ptr, 0, 64, p->stream), "memset") || !hip_ok(hipEventRecord(p->evB0, p->stream), "event")) return false;
@@ -2140,7 +886,7 @@ static pa_batch* batch_create(const uint8_t* const* a, const size_t* a_len, cons
         p->block_waves = sh.block_waves;
         if (!astar && !trace) {  // a cost-only batch big enough for groups of 32 pairs: the bit-sliced kernel, when its estimate is the lower one
             double est = -1;
-            const double simds = (double)(g_device_props_cus > 0 ? g_device_props_cus : 256) * 4.0;
+            const double simds = (double)device_cus() * 4.0;
             const int R = slice::choose_rows_per_lane(a_len, b_len, pairs, simds, &est);
             const bool forced = getenv("PA_SLICE") && atoi(getenv("PA_SLICE")) > 0;
             if (R > 0 && (forced || sh.est_ns < 0 || est < sh.est_ns)) slice_rows = R;
@@ -2418,7 +1164,7 @@ static pa_batch* batch_create(const uint8_t* const* a, const size_t* a_len, cons
         // order and only the priority rotation is kept.
         static const bool no_pace = getenv("PA_STRIP_NO_PACE") != nullptr;
         static const bool no_rotate = getenv("PA_STRIP_NO_ROTATE") != nullptr;
-        const size_t simds = (size_t)(g_device_props_cus > 0 ? g_device_props_cus : 256) * 4;
+        const size_t simds = (size_t)device_cus() * 4;
         int tops = 0;
         for (const StripJob& j : p->jobs) tops += j.hin_gran == nullptr;
         for (StripJob& j : p->jobs) {
@@ -2521,7 +1267,7 @@ static int launch_astar(pa_batch* p, hipStream_t s, size_t lo, size_t cnt, uint3
     // (apa2_full_kernel fits five wavefronts per SIMD, apa2_kernel -- four strip heights, 128 VGPRs -- four)
     const int per_cu = getenv("PA_APA2_BLOCKS_PER_CU") ? std::max(1, atoi(getenv("PA_APA2_BLOCKS_PER_CU"))) : (p->astar_full ? 5 : 4);
     static const bool probe_stats = getenv("PA_APA2_PROBE_STATS") != nullptr;
-    const int cus = g_device_props_cus > 0 ? g_device_props_cus : 256;
+    const int cus = device_cus();
     const int grid = (int)std::min<size_t>((cnt + kStripBlockWaves - 1) / kStripBlockWaves, (size_t)cus * per_cu);
     const int32_t* ord = p->d_order.as<int32_t>() + lo;
     // Two half-wave blocks of one workgroup run as one strip (strip2_kernel.hpp).  PA_APA2_RDV=0 turns the rendezvous off (every strip alone,
@@ -2531,7 +1277,7 @@ static int launch_astar(pa_batch* p, hipStream_t s, size_t lo, size_t cnt, uint3
     const double rdv_us = getenv("PA_APA2_RDV_PATIENCE_US") ? std::max(0.0, atof(getenv("PA_APA2_RDV_PATIENCE_US"))) : 20.0;
     // A block that waits for a partner is a wavefront that does nothing: worth it when the SIMDs have other wavefronts to run, not when a
     // batch leaves most of them with one or none (512 x 100 kbp: 38.3 against 36.4 ms).  PA_APA2_RDV=0: never; =2: whatever the batch size.
-    const size_t simds = (size_t)(g_device_props_cus > 0 ? g_device_props_cus : 256) * 4;
+    const size_t simds = (size_t)device_cus() * 4;
     RdvParams rp;
     rp.enabled = cnt >= 2 * simds ? 1u : 0u;
     if (rdv_env && rdv_env[0] == '0') rp.enabled = 0u;
@@ -2557,21 +1303,9 @@ static int batch_forward(pa_batch* p, bool launch = true) {
     if (!hip_ok(hipMemsetAsync(p->d_misc.ptr, 0, 32, s), "memset")) return PA_E_HIP;  // (+ the pace counter of chained batches)
     if (p->astar && !p->d_rdv.ptr && !p->d_rdv.alloc(64)) return PA_E_HIP;
     if (p->d_rdv.ptr && !hip_ok(hipMemsetAsync(p->d_rdv.ptr, 0, 64, s), "memset rendezvous counters")) return PA_E_HIP;
-    for (size_t base = 0; base < p->pairs; base += 32768) {  // gridDim.y limit
-        const unsigned ny = (unsigned)std::min<size_t>(32768, p->pairs - base);
-        const PairDesc* dd = p->d_desc.as<PairDesc>() + base;
-        if (p->max_n) {
-            const unsigned nx = (unsigned)(((p->max_n + 15) / 16 + 255) / 256);
-            hipLaunchKernelGGL(encode_a_batch_kernel, dim3(nx, ny), dim3(256), 0, s, p->d_a.as<uint8_t>(), p->d_codes.as<uint32_t>(), dd,
-                               p->d_misc.as<uint32_t>() + 3);
-        }
-        if (p->max_m) {
-            const unsigned nx = (unsigned)(((p->max_m + 63) / 64 + 3) / 4);
-            hipLaunchKernelGGL(build_b_batch_kernel, dim3(nx, ny), dim3(256), 0, s, p->d_b.as<uint8_t>(), p->d_prof.as<uint64_t>(), dd,
-                               p->d_misc.as<uint32_t>() + 3);
-        }
-        if (!hip_ok(hipGetLastError(), "profile kernels")) return PA_E_HIP;
-    }
+    if (!encode_batch_device(p->d_a.as<uint8_t>(), p->max_n, p->d_codes.as<uint32_t>(), p->d_b.as<uint8_t>(), p->max_m, p->d_prof.as<uint64_t>(),
+                             p->d_desc.as<PairDesc>(), p->pairs, p->d_misc.as<uint32_t>() + 3, s))
+        return PA_E_HIP;
     // (2) clear hand-off granules, (3) strips
     // every strip hands the granules it consumed back zeroed, so the buffer is cleared only before the first pass (and
     // after a pass that did not finish)
@@ -2815,33 +1549,21 @@ static int batch_align_small(pa_batch* p, int32_t* cost_out, char** cigar_out, f
     const auto t0 = std::chrono::steady_clock::now();
     p->pair_stats.assign(P, pa_astarpa2_stats{});
     p->apa2_strip_instr = 0;
-    for (size_t i = 0; i < P; ++i) cigar_out[i] = nullptr;
-    auto fail_out = [&](int code) {
-        for (size_t k = 0; k < P; ++k) {
-            std::free(cigar_out[k]);
-            cigar_out[k] = nullptr;
-        }
-        return code;
-    };
+    for (size_t i = 0; i < P; ++i) cigar_out[i] = nullptr;  // (and they stay so unless every pair succeeds)
+    std::vector<std::string> texts(P);
     // one after another: two sweeps of long pairs at once get in each other's way (measured: 2 pairs 69 ms side by side, 29 ms in a row)
     for (size_t i = 0; i < P; ++i) {
         std::vector<uint8_t> ba(p->n[i]), bb(p->m[i]);
         if (!hip_ok(hipMemcpy(ba.data(), p->d_a.as<uint8_t>() + p->a_off[i], p->n[i], hipMemcpyDeviceToHost), "D2H a") ||
             !hip_ok(hipMemcpy(bb.data(), p->d_b.as<uint8_t>() + p->b_off[i], p->m[i], hipMemcpyDeviceToHost), "D2H b"))
-            return fail_out(PA_E_HIP);
-        std::string text;
+            return PA_E_HIP;
         int32_t c = 0;
-        int rc = align_hip(ba.data(), p->n[i], bb.data(), p->m[i], p->aparams_c, true, false, &c, &text, &p->pair_stats[i]);
-        if (rc == PA_E_TIMEOUT) rc = align_hip(ba.data(), p->n[i], bb.data(), p->m[i], p->aparams_c, true, false, &c, &text, &p->pair_stats[i]);
-        if (rc != 0) return fail_out(rc);
+        int rc = align_hip(ba.data(), p->n[i], bb.data(), p->m[i], p->aparams_c, true, false, &c, &texts[i], &p->pair_stats[i]);
+        if (rc == PA_E_TIMEOUT) rc = align_hip(ba.data(), p->n[i], bb.data(), p->m[i], p->aparams_c, true, false, &c, &texts[i], &p->pair_stats[i]);
+        if (rc != 0) return rc;
         cost_out[i] = c;
-        cigar_out[i] = (char*)std::malloc(text.size() + 1);
-        if (!cigar_out[i]) {
-            set_error("out of memory");
-            return fail_out(PA_E_NOMEM);
-        }
-        std::memcpy(cigar_out[i], text.c_str(), text.size() + 1);
     }
+    if (const int rc = give_cstrings(texts, cigar_out)) return rc;
     if (forward_ms) *forward_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (trace_ms) *trace_ms = 0.f;  // (the engine's traceback is inside the figure above)
     return 0;
@@ -3187,276 +1909,6 @@ extern "C" int pa_batch_align(pa_batch* p, int32_t* cost_out, char** cigar_out, 
         std::memcpy(cigar_out[i], text.c_str(), text.size() + 1);
     }
     mark("pairs handed back");
-    return 0;
-}
-
-// Diagnostics / tests: the matches of GCSH (seed length k, local pruning p_local) of one pair AS THE GPU FINDS THEM (gcsh_build_kernel.hpp),
-// by start: out_ij[2 t], out_ij[2 t + 1] for t < min(count, cap_out).  Returns the count, or -(100 + status) when the kernel gave up.
-extern "C" long pa_debug_gcsh_matches(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int32_t k, int32_t p_local, int32_t* out_ij, size_t cap_out) {
-    if (!ensure_device()) return PA_E_HIP;
-    if (!a || !b || a_len == 0 || b_len == 0 || k < 1 || k > 31 || p_local < 0 || p_local > apa2::kBuildMaxP) return PA_E_ARG;
-    const size_t ns = a_len >= (size_t)k ? (a_len - k) / k + 1 : 0, cap = ns + ns / 2 + 2048;
-    size_t tsz = 64;
-    while (tsz < 2 * ns + 1) tsz *= 2;
-    DeviceBuf d_a, d_b, d_w, d_mi, d_mj, d_win, d_job, d_out;
-    const size_t words = 4 * ns + 1 + tsz + 4 * cap;
-    if (!d_a.alloc(a_len + 64) || !d_b.alloc(b_len + 64) || !d_w.alloc(words * 4 + 2 * cap + 64) || !d_mi.alloc(cap * 4) || !d_mj.alloc(cap * 4) ||
-        !d_win.alloc(std::max<size_t>(ns, 1) * sizeof(apa2::GcshSeedWindow)) || !d_job.alloc(sizeof(apa2::GcshBuildJob)) || !d_out.alloc(64))
-        return PA_E_NOMEM;
-    apa2::GcshBuildJob x;
-    std::memset(&x, 0, sizeof x);
-    int32_t* w32 = d_w.as<int32_t>();
-    size_t o = 0;
-    x.a = d_a.as<uint8_t>();
-    x.b = d_b.as<uint8_t>();
-    x.keys = (uint32_t*)(w32 + o), o += ns;
-    x.next_same = w32 + o, o += ns;
-    x.cnt = w32 + o, o += ns + 1;
-    x.fill = w32 + o, o += ns;
-    x.slot = w32 + o, o += tsz;
-    x.tmp_s = w32 + o, o += cap;
-    x.tmp_j = w32 + o, o += cap;
-    x.gpos = w32 + o, o += cap;
-    x.cj = w32 + o, o += cap;
-    x.flag = (uint8_t*)(w32 + words);
-    x.keptg = x.flag + cap;
-    x.mi = d_mi.as<int32_t>();
-    x.mj = d_mj.as<int32_t>();
-    x.win0 = d_win.as<apa2::GcshSeedWindow>();
-    x.nmatch_out = d_out.as<int32_t>();
-    x.status = d_out.as<uint32_t>() + 1;
-    x.n = (int32_t)a_len;
-    x.m = (int32_t)b_len;
-    x.k = k;
-    x.p = p_local;
-    x.nseeds = (int32_t)ns;
-    x.tsize = (int32_t)tsz;
-    x.cap = (int32_t)cap;
-    DeviceBuf d_clk;
-    static const bool clocks = getenv("PA_BUILD_CLOCKS") != nullptr;
-    if (clocks) {
-        if (!d_clk.alloc(128) || !hip_ok(hipMemset(d_clk.ptr, 0, 128), "memset")) return PA_E_HIP;
-        x.clocks = d_clk.as<unsigned long long>();
-    }
-    int32_t res[4] = {0, 0, 0, 0};
-    if (!hip_ok(hipMemcpy(d_a.ptr, a, a_len, hipMemcpyHostToDevice), "H2D") || !hip_ok(hipMemcpy(d_b.ptr, b, b_len, hipMemcpyHostToDevice), "H2D") ||
-        !hip_ok(hipMemset(d_out.ptr, 0, 64), "memset") || !hip_ok(hipMemcpy(d_job.ptr, &x, sizeof x, hipMemcpyHostToDevice), "H2D"))
-        return PA_E_HIP;
-    if (!hip_ok(apa2::launch_gcsh_build_kernel(1, 0, d_job.as<apa2::GcshBuildJob>(), 1, d_out.as<uint32_t>() + 8), "gcsh_build_kernel") || !hip_ok(hipDeviceSynchronize(), "sync") || !hip_ok(hipMemcpy(res, d_out.ptr, 16, hipMemcpyDeviceToHost), "D2H"))
-        return PA_E_HIP;
-    if (clocks) {
-        unsigned long long c[16] = {0};
-        (void)hipMemcpy(c, d_clk.ptr, 128, hipMemcpyDeviceToHost);
-        std::fprintf(stderr, "[gcsh build] n %zu m %zu k %d p %d: A %.3f  B %.3f  C %.3f  D %.3f  E %.3f  F %.3f ms; %llu candidates, %llu kept alone, %llu searches in E; D: %llu search levels of %llu that its rounds last (deepest lane x lanes); status %d\n", a_len, b_len,
-                     k, p_local, c[0] * 1e-5, c[1] * 1e-5, c[2] * 1e-5, c[3] * 1e-5, c[4] * 1e-5, c[5] * 1e-5, c[6], c[7], c[8], c[9], c[10], res[1]);
-    }
-    if (res[1] != 0) return -(100 + (long)res[1]);
-    const size_t cnt = (size_t)std::max(res[0], 0), take = std::min(cnt, cap_out);
-    if (take && out_ij) {
-        std::vector<int32_t> mi(take), mj(take);
-        if (!hip_ok(hipMemcpy(mi.data(), d_mi.ptr, take * 4, hipMemcpyDeviceToHost), "D2H") || !hip_ok(hipMemcpy(mj.data(), d_mj.ptr, take * 4, hipMemcpyDeviceToHost), "D2H"))
-            return PA_E_HIP;
-        for (size_t t = 0; t < take; ++t) {
-            out_ij[2 * t] = mi[t];
-            out_ij[2 * t + 1] = mj[t];
-        }
-    }
-    return (long)cnt;
-}
-
-// Diagnostics / tests: the DEVICE form of GCSH alone.  The matches are found on the host (csrc/gcsh.hpp), one wavefront derives the contours
-// and evaluates h at nq positions (queries[2 t], queries[2 t + 1]); out[t] = h, out[nq] = number of contour layers (incl. layer 0).
-extern "C" int pa_debug_gcsh_probe(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int32_t k, int32_t p_local, const int32_t* queries,
-                                   size_t nq, int32_t* out) {
-    if (!ensure_device()) return PA_E_HIP;
-    if (!a || !b || a_len == 0 || b_len == 0 || k < 1 || k > 31 || (!queries && nq) || !out) return PA_E_ARG;
-    engine::GcshHeuristic gh(a, (engine::I)a_len, b, (engine::I)b_len, k, p_local, false, false);
-    const size_t M = gh.by_start.size();
-    std::vector<int32_t> mi(M), mj(M);
-    for (size_t t = 0; t < M; ++t) {
-        mi[t] = gh.by_start[t].i;
-        mj[t] = gh.by_start[t].j;
-    }
-    DeviceBuf d_mi, d_mj, d_act, d_lrec, d_cell, d_job, d_q, d_out, d_err;
-    if (!d_mi.alloc(std::max<size_t>(M, 1) * 4) || !d_mj.alloc(std::max<size_t>(M, 1) * 4) || !d_act.alloc(std::max<size_t>(M, 64)) ||
-        !d_lrec.alloc((M + 2) * sizeof(apa2::GcshCell)) || !d_cell.alloc(std::max<size_t>(M, 1) * sizeof(apa2::GcshCell)) || !d_job.alloc(sizeof(apa2::FullJob)) ||
-        !d_q.alloc(std::max<size_t>(nq, 1) * 8) || !d_out.alloc((nq + 1) * 4) || !d_err.alloc(64))
-        return PA_E_NOMEM;
-    apa2::FullJob j;
-    std::memset(&j, 0, sizeof j);
-    j.n = (int32_t)a_len;
-    j.m = (int32_t)b_len;
-    j.heur = apa2::kFullHeurGcsh;
-    j.g.mi = d_mi.as<int32_t>();
-    j.g.mj = d_mj.as<int32_t>();
-    j.g.active = d_act.as<uint8_t>();
-    j.g.lrec = d_lrec.as<apa2::GcshCell>();
-    j.g.cell = d_cell.as<apa2::GcshCell>();
-    j.g.nmatch = (int32_t)M;
-    j.g.nlayers = 1;
-    j.g.n = j.n;
-    j.g.m = j.m;
-    j.g.k = k;
-    j.g.nseeds = gh.nseeds;
-    if ((M && (!hip_ok(hipMemcpy(d_mi.ptr, mi.data(), M * 4, hipMemcpyHostToDevice), "H2D") || !hip_ok(hipMemcpy(d_mj.ptr, mj.data(), M * 4, hipMemcpyHostToDevice), "H2D"))) ||
-        !hip_ok(hipMemset(d_act.ptr, 1, std::max<size_t>(M, 64)), "memset") || !hip_ok(hipMemset(d_err.ptr, 0, 64), "memset") ||
-        !hip_ok(hipMemcpy(d_job.ptr, &j, sizeof j, hipMemcpyHostToDevice), "H2D") ||
-        (nq && !hip_ok(hipMemcpy(d_q.ptr, queries, nq * 8, hipMemcpyHostToDevice), "H2D")))
-        return PA_E_HIP;
-    if (!hip_ok(apa2::launch_gcsh_probe_kernel(0, d_job.as<apa2::FullJob>(), d_q.as<int32_t>(), (int)nq, d_out.as<int32_t>(), d_err.as<uint32_t>()), "gcsh_probe_kernel") || !hip_ok(hipDeviceSynchronize(), "sync") ||
-        !hip_ok(hipMemcpy(out, d_out.ptr, (nq + 1) * 4, hipMemcpyDeviceToHost), "D2H"))
-        return PA_E_HIP;
-    return 0;
-}
-
-// Diagnostics / tests: strip jobs of the band-search kernels through the instances those kernels use (apa2_full_unit.hip,
-// strip_probe_kernel).  Every job gets buffers of its own in one device arena; a and b are encoded by the batch profile kernels.
-extern "C" int pa_debug_strip(int mode, int variant, int nwaves, uint32_t patience, pa_strip_probe_job* jobs, size_t njobs, uint64_t* counters4) {
-    using apa2::kStripProbeDual;
-    using apa2::kStripProbeRdv;
-    using apa2::kStripProbeSingle;
-    if (!ensure_device()) return PA_E_HIP;
-    auto bad_arg = [](const char* what, size_t t) {
-        set_error("pa_debug_strip: job %zu: %s", t, what);
-        return PA_E_ARG;
-    };
-    if (!jobs || njobs == 0 || njobs > (1u << 20)) return bad_arg("no jobs, or too many", 0);
-    if (mode == kStripProbeDual) {
-        if ((variant != 0 && variant != 1) || njobs % 2 != 0) return bad_arg("dual: variant 0 or 1, an even number of jobs", 0);
-    } else if (mode == kStripProbeSingle) {
-        if (variant < 0 || variant > 3) return bad_arg("single: variant 0 .. 3", 0);
-    } else if (mode == kStripProbeRdv) {
-        if ((variant != 0 && variant != 1) || nwaves < 2 || nwaves > 4 || njobs % (size_t)nwaves != 0)
-            return bad_arg("rdv: variant 0 or 1, 2 .. 4 waves, whole workgroups", 0);
-    } else {
-        return bad_arg("mode 0, 1 or 2", 0);
-    }
-    const bool tap_variant = mode == kStripProbeSingle ? variant >= 1 : variant == 1;
-    const int k = mode == kStripProbeSingle && variant == 3 ? 2 : 1;
-    const int max_lanes = mode == kStripProbeSingle ? (variant == 3 ? 128 : (variant == 2 ? 64 : 32)) : 32;
-    // arena layout: per job a, b, codes, profile, v, hin, values, hout, sum; then the descriptors (all regions 256-byte aligned)
-    struct Off {
-        size_t a, b, codes, prof, v, hin, values, hout, sum, nwb;
-    };
-    std::vector<Off> off(njobs);
-    size_t top = 0, max_a = 0, max_b = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = top;
-        top += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    for (size_t t = 0; t < njobs; ++t) {
-        const pa_strip_probe_job& J = jobs[t];
-        if (!J.a || !J.b || !J.v || !J.hout || J.a_len == 0 || J.b_len == 0 || J.a_len > (1u << 30) || J.b_len > (1u << 30))
-            return bad_arg("a, b, v and hout are required, 1 <= |a|, |b| <= 2^30", t);
-        const size_t nwb = (J.b_len + 63) / 64;
-        if (J.n < 1 || J.col0 < 0 || (size_t)J.col0 + (size_t)J.n > J.a_len) return bad_arg("columns outside a (n >= 1, col0 + n <= |a|)", t);
-        if (J.nlanes < 2 || J.nlanes % 2 != 0 || J.nlanes > max_lanes) return bad_arg("nlanes odd or out of range for the mode", t);
-        if (J.word0 < 0 || (size_t)J.word0 + (size_t)(J.nlanes / 2) > nwb) return bad_arg("rows beyond b's profile", t);
-        if (tap_variant ? (J.tap < -1 || J.tap >= (k == 2 ? J.nlanes / 2 : J.nlanes)) : J.tap != -1) return bad_arg("tap out of range (-1 without TAP)", t);
-        if (J.values && !tap_variant) return bad_arg("values without TAP", t);
-        if ((J.hin_is_hout != 0 && J.hin_is_hout != 1) || (J.hin_is_hout && J.hin)) return bad_arg("hin_is_hout is 0 or 1, and 1 takes no hin", t);
-        Off& o = off[t];
-        o.nwb = nwb;
-        o.a = take(J.a_len);
-        o.b = take(J.b_len);
-        o.codes = take((J.a_len + 15) / 16 * 4);
-        o.prof = take(nwb * 16);
-        o.v = take(nwb * 16);
-        o.hin = J.hin ? take(J.a_len) : 0;
-        o.values = J.values ? take(nwb * 16) : 0;
-        o.hout = take(J.a_len);
-        o.sum = take(4);
-        max_a = std::max(max_a, J.a_len);
-        max_b = std::max(max_b, J.b_len);
-    }
-    const size_t o_desc = take(njobs * sizeof(PairDesc)), o_jobs = take(njobs * sizeof(StripJob)), o_taps = take(njobs * 4), o_misc = take(64);
-    DeviceBuf d;
-    if (!d.alloc(top)) return PA_E_HIP;
-    uint8_t* base = d.as<uint8_t>();
-    std::vector<uint8_t> h(top, 0);
-    PairDesc* desc = (PairDesc*)(h.data() + o_desc);
-    StripJob* sj = (StripJob*)(h.data() + o_jobs);
-    int32_t* taps = (int32_t*)(h.data() + o_taps);
-    for (size_t t = 0; t < njobs; ++t) {
-        const pa_strip_probe_job& J = jobs[t];
-        const Off& o = off[t];
-        std::memcpy(h.data() + o.a, J.a, J.a_len);
-        std::memcpy(h.data() + o.b, J.b, J.b_len);
-        std::memcpy(h.data() + o.v, J.v, o.nwb * 16);
-        if (J.hin) std::memcpy(h.data() + o.hin, J.hin, J.a_len);
-        if (J.values) std::memcpy(h.data() + o.values, J.values, o.nwb * 16);
-        std::memcpy(h.data() + o.hout, J.hout, J.a_len);
-        desc[t].a_off = o.a;
-        desc[t].b_off = o.b;
-        desc[t].code_off = o.codes / 4;
-        desc[t].prof_off = o.prof / 16;
-        desc[t].n = (int)J.a_len;
-        desc[t].m = (int)J.b_len;
-        // as apa2_kernel.hpp / apa2_full_kernel.hpp build a block's strip: the last (only) strip of the block, no granules
-        StripJob j;
-        std::memset(&j, 0, sizeof j);
-        j.a_codes = (const uint32_t*)(base + o.codes);
-        j.b_prof = (const uint32_t*)(base + o.prof);
-        j.v = (uint32_t*)(base + o.v);
-        j.hin_gran = nullptr;
-        j.hin_arr = J.hin_is_hout ? base + o.hout : (J.hin ? base + o.hin : nullptr);
-        j.hout_gran = nullptr;
-        j.hout_arr = tap_variant ? base + o.hout : nullptr;
-        j.values = J.values ? (uint32_t*)(base + o.values) : nullptr;
-        j.sum_out = (int32_t*)(base + o.sum);
-        j.n = J.n;
-        j.word0 = J.word0;
-        j.nlanes = J.nlanes;
-        j.fill_stride = J.fill_stride;
-        j.fill_word0 = J.fill_word0;
-        j.exact_tail = 0;
-        j.flags = 0;
-        j.col0 = J.col0;
-        j.tail_rows = -1;
-        j.k = k;
-        j.ckpt = nullptr;
-        j.ckpt_stride = 0;
-        j.hin_n = 0;
-        j.vsum_out = nullptr;
-        if (mode != kStripProbeSingle && !apa2::strip_probe_dual_ok(j, tap_variant)) return bad_arg("dual_ok refuses the job", t);
-        sj[t] = j;
-        taps[t] = J.tap;
-    }
-    uint32_t* misc = (uint32_t*)(base + o_misc);  // [0] err, [1] invalid base, [8..16) counters
-    hipStream_t s = 0;
-    if (!hip_ok(hipMemcpy(base, h.data(), top, hipMemcpyHostToDevice), "H2D strip probe")) return PA_E_HIP;
-    for (size_t b0 = 0; b0 < njobs; b0 += 32768) {  // gridDim.y limit
-        const unsigned ny = (unsigned)std::min<size_t>(32768, njobs - b0);
-        const PairDesc* dd = (const PairDesc*)(base + o_desc) + b0;
-        hipLaunchKernelGGL(encode_a_batch_kernel, dim3((unsigned)(((max_a + 15) / 16 + 255) / 256), ny), dim3(256), 0, s, base, (uint32_t*)base, dd, misc + 1);
-        hipLaunchKernelGGL(build_b_batch_kernel, dim3((unsigned)(((max_b + 63) / 64 + 3) / 4), ny), dim3(256), 0, s, base, (uint64_t*)base, dd, misc + 1);
-        if (!hip_ok(hipGetLastError(), "profile kernels")) return PA_E_HIP;
-    }
-    uint32_t bad = 0;
-    if (!hip_ok(hipMemcpy(&bad, misc + 1, 4, hipMemcpyDeviceToHost), "D2H")) return PA_E_HIP;
-    if (bad) {
-        set_error("pa_debug_strip: a sequence holds a character outside ACGT");
-        return PA_E_INVALID_BASE;
-    }
-    const int blocks = (int)(mode == kStripProbeDual ? njobs / 2 : (mode == kStripProbeRdv ? njobs / (size_t)nwaves : njobs));
-    if (!hip_ok(apa2::launch_strip_probe_kernel(s, mode, variant, blocks, nwaves, (const StripJob*)(base + o_jobs), (const int32_t*)(base + o_taps), patience,
-                                                misc, (unsigned long long*)(misc + 8)),
-                "strip_probe_kernel") ||
-        !hip_ok(hipDeviceSynchronize(), "sync") || !hip_ok(hipMemcpy(h.data(), base, top, hipMemcpyDeviceToHost), "D2H strip probe"))
-        return PA_E_HIP;
-    const uint32_t* hm = (const uint32_t*)(h.data() + o_misc);
-    if (counters4) std::memcpy(counters4, hm + 8, 32);
-    if (hm[0] != PA_ERR_NONE) {
-        set_error("pa_debug_strip: the device reported error %u", hm[0]);
-        return PA_E_TIMEOUT;
-    }
-    for (size_t t = 0; t < njobs; ++t) {
-        const Off& o = off[t];
-        std::memcpy(jobs[t].v, h.data() + o.v, o.nwb * 16);
-        std::memcpy(jobs[t].hout, h.data() + o.hout, jobs[t].a_len);
-        std::memcpy(&jobs[t].sum, h.data() + o.sum, 4);
-    }
     return 0;
 }
 

@@ -18,6 +18,18 @@ constexpr int kWordsPerStrip = 32;  // per subword-per-lane: a strip of k subwor
 void set_error(const char* fmt, ...);
 bool hip_ok(hipError_t e, const char* what);
 bool ensure_device();
+int device_cus();  // compute units of the device this thread last initialised (ensure_device), 256 if none
+// set_error + return rc
+int fail(int rc, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// runtime_unit.hip's pools, for the life of the process: pinned host blocks, the chunk streams (non-blocking) and the batches' own
+// (blocking) streams; a stream goes back with the device it was created on, after its owner has waited for it
+void* pinned_take(size_t bytes, size_t* got);
+void pinned_give(void* ptr, size_t size);
+hipStream_t stream_take();
+void stream_give(hipStream_t s, int dev);
+hipStream_t bstream_take();
+void bstream_give(hipStream_t s, int dev);
 
 void release_alloc_cache();  // the cached device blocks back to the driver (pa_release_pools)
 void release_scope_begin();  // one device wait now; DeviceBuf::release calls of this thread skip theirs until release_scope_end()
@@ -39,6 +51,13 @@ struct DeviceBuf {
     template <class T>
     T* as() const { return reinterpret_cast<T*>(ptr); }
 };
+// d.alloc(max(bytes, 16)), then the copy queued on s
+bool upload(DeviceBuf& d, const void* src, size_t bytes, hipStream_t s);
+// Device-memory budget of one traced chunk: the megabytes in the environment variable `env_mb`, else a quarter of the free memory.
+size_t trace_budget(const char* env_mb);
+// A malloc'ed copy of every text into out[0 .. texts.size()).  If one malloc fails, the copies made so far are freed and nulled again
+// (the caller owns outputs only on success): "out of memory", PA_E_NOMEM.
+int give_cstrings(const std::vector<std::string>& texts, char** out);
 
 // One rectangle = words [w0,w1) x n columns of one pair, split into chained strips.
 struct RectPlan {
@@ -85,5 +104,13 @@ bool build_b_device(const uint8_t* d_b, int m, uint64_t* d_prof, uint32_t* d_bad
 // both in one launch; all `code_words` words of d_codes are written (zero beyond the sequence); `bad` may be host-mapped memory
 bool encode_pair_device(const uint8_t* d_a, int n, uint32_t* d_codes, int code_words, const uint8_t* d_b, int m, uint64_t* d_prof, uint32_t* bad,
                         hipStream_t s);
+// Batched forms (all pairs of a pa_batch): where each pair's sequences, codes and profile lie in the concatenated buffers.
+struct PairDesc {
+    unsigned long long a_off, b_off, code_off, prof_off;  // element offsets into the concatenated buffers
+    int n, m;
+};
+// codes of every a (skipped when max_n == 0) and profile of every b (skipped when max_m == 0) of `pairs` descriptors
+bool encode_batch_device(const uint8_t* d_a_cat, size_t max_n, uint32_t* d_codes_cat, const uint8_t* d_b_cat, size_t max_m, uint64_t* d_prof_cat,
+                         const PairDesc* d_desc, size_t pairs, uint32_t* d_bad, hipStream_t s);
 
 }  // namespace pa

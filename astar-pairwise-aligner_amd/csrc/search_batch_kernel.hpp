@@ -171,7 +171,7 @@ __device__ __forceinline__ int32_t vrow(const gcu32 v, uint32_t r) {  // vertica
 }
 
 // out = bsum0 (sum of v0), then bsum0 + bottom-row prefix sums, then the right column upwards (B - sums of (v - v0) from the bottom),
-// the first `rows - plen` values after out[0] skipped: the arithmetic of search_out in pa_hip.hip.  best = min, lowest index.
+// the first `rows - plen` values after out[0] skipped: the arithmetic of search_out in search_unit.hip.  best = min, lowest index.
 __global__ __launch_bounds__(64 * kSegBlockWaves) void search_best_kernel(const RedQuery* __restrict__ queries, int nq, int32_t* best_cost,
                                                                          uint64_t* best_idx, const uint64_t* want, int32_t* want_val) {
     const int wave = (int)(blockIdx.x * kSegBlockWaves + (threadIdx.x >> 6));

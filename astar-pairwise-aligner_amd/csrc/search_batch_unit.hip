@@ -13,7 +13,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -98,22 +97,6 @@ __global__ void copy_v0_kernel(const uint64_t* __restrict__ desc, int n, const u
     if (q >= n) return;
     const uint64_t src = desc[3 * q], dst = desc[3 * q + 1], words = desc[3 * q + 2];
     for (uint64_t i = threadIdx.x; i < 2 * words; i += blockDim.x) v[2 * dst + i] = v0[2 * src + i];
-}
-
-int fail(int rc, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int rc, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    set_error("%s", buf);
-    return rc;
-}
-
-bool upload(DeviceBuf& d, const void* src, size_t bytes, hipStream_t s) {
-    if (!d.alloc(std::max<size_t>(bytes, 16))) return false;
-    return bytes == 0 || hip_ok(hipMemcpyAsync(d.ptr, src, bytes, hipMemcpyHostToDevice, s), "H2D");
 }
 
 int check_device_error(const DeviceBuf& d_misc, hipStream_t s) {
@@ -349,18 +332,6 @@ int forward(pa_search_batch& sb, float* kernel_ms) {
     return 0;
 }
 
-// Device-memory budget of one traceback chunk (the re-filled columns dominate): PA_SEARCH_TRACE_BUDGET_MB, else a quarter of the free
-// memory.
-size_t trace_budget() {
-    if (const char* e = getenv("PA_SEARCH_TRACE_BUDGET_MB")) {
-        const double mb = atof(e);
-        if (mb > 0) return (size_t)(mb * 1048576.0);
-    }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b == 0) return size_t(1) << 30;
-    return free_b / 4;
-}
-
 struct TraceItem {
     uint32_t q;
     size_t pi, pj, start, end, w;
@@ -449,7 +420,7 @@ extern "C" int pa_search_batch_run(pa_search_batch* sb, int32_t* best_cost, uint
 }
 
 // out + offsets[q] receives query q's plen + tlen + 1 values (offsets[q] == UINT64_MAX: skip query q).  Assembled on the host from the
-// device's bottom rows and final columns with the arithmetic of search_out (pa_hip.hip).
+// device's bottom rows and final columns with the arithmetic of search_out (search_unit.hip).
 extern "C" int pa_search_batch_rows(const pa_search_batch* sb, int32_t* out, const uint64_t* offsets) {
     if (!sb) return fail(PA_E_ARG, "pa_search_batch_rows: NULL batch");
     if (!sb->ran) return fail(PA_E_ARG, "pa_search_batch_rows: call pa_search_batch_run first");
@@ -548,7 +519,7 @@ extern "C" int pa_search_batch_trace(pa_search_batch* sb, const uint64_t* idx, c
         it.gran_words = (it.w && n) ? rect_granules((int)n, (int)it.w) : 0;
         it.ops = n + it.pj + 1;
     }
-    const size_t budget = trace_budget();
+    const size_t budget = trace_budget("PA_SEARCH_TRACE_BUDGET_MB");  // (the re-filled columns dominate a chunk)
     std::vector<std::string> cigars(nq);
     std::vector<int64_t> starts(2 * nq);
     DeviceBuf d_values, d_vend, d_gran, d_ops, d_jobs, d_walk, d_wout, d_misc;
@@ -656,19 +627,8 @@ extern "C" int pa_search_batch_trace(pa_search_batch* sb, const uint64_t* idx, c
         }
         c0 = c1;
     }
-    if (cigars_out) {
-        for (size_t q = 0; q < nq; ++q) {
-            cigars_out[q] = (char*)std::malloc(cigars[q].size() + 1);
-            if (!cigars_out[q]) {
-                for (size_t k = 0; k < q; ++k) {
-                    std::free(cigars_out[k]);
-                    cigars_out[k] = nullptr;
-                }
-                return fail(PA_E_NOMEM, "out of memory");
-            }
-            std::memcpy(cigars_out[q], cigars[q].c_str(), cigars[q].size() + 1);
-        }
-    }
+    if (cigars_out)
+        if (const int rc = give_cstrings(cigars, cigars_out)) return rc;
     if (start_out) std::memcpy(start_out, starts.data(), 2 * nq * sizeof(int64_t));
     return 0;
 }

@@ -182,13 +182,7 @@ int run(Plan* p, hipStream_t s, const uint32_t* d_codes, const uint64_t* d_prof,
     if (!hip_ok(hipMemsetAsync(p->d_V.ptr, 0, p->b_elems * 8, s), "memset slice V")) return PA_E_HIP;  // captured columns are OR-ed in
     // boundary rows: "not written yet" = hp = hm = ~0 in every pair
     if (p->h_elems && !hip_ok(hipMemsetAsync(p->d_H.ptr, 0xFF, p->h_elems * 8, s), "memset slice boundaries")) return PA_E_HIP;
-    int cus = 256;
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    }
-    const int grid = (int)std::min<size_t>(p->jobs.size(), (size_t)cus * 8);  // two wavefronts per SIMD, one wavefront per workgroup
+    const int grid = (int)std::min<size_t>(p->jobs.size(), (size_t)device_cus() * 8);  // two wavefronts per SIMD, one wavefront per workgroup
     // diagnostics: PA_SLICE_JOBTIMES=1 prints, per pass, how long the (group, strip) jobs took their wavefronts and how much of that they slept
     static const bool jobtimes = getenv("PA_SLICE_JOBTIMES") != nullptr;
     unsigned long long* dbg = nullptr;

@@ -23,6 +23,14 @@ def test_library_exports_every_declared_symbol():
     assert set(pa.capi.EXPORTED_SYMBOLS) <= declared | {"pa_align"}
 
 
+def test_build_lists_every_hip_source():
+    """_build.sources() skips a listed file that does not exist: a misspelt or forgotten unit would surface only as a link error."""
+    import astar_pairwise_aligner_amd as pa
+
+    assert set(pa._build.HIP_SOURCES) == {p.name for p in pa._build.CSRC.glob("*.hip")}
+    assert len(pa._build.HIP_SOURCES) == len(set(pa._build.HIP_SOURCES))
+
+
 def test_no_gpu_fails_loudly():
     import astar_pairwise_aligner_amd as pa
 

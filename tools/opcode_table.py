@@ -1,6 +1,6 @@
 """Per-opcode VALU count of the headline kernel's interior chunk (32 unrolled K = 8 steps of pa::pair_kernel<8, false, true>), from the ISA.
-Usage:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I include -c astar-pairwise-aligner_amd/csrc/pa_hip.hip -o /tmp/pa.o -save-temps
-        python tools/opcode_table.py pa_hip-hip-amdgcn-amd-amdhsa-gfx950.s > profiles/r05_headline_opcodes.json
+Usage:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I include -c astar-pairwise-aligner_amd/csrc/rect_unit.hip -o /tmp/pa.o -save-temps
+        python tools/opcode_table.py rect_unit-hip-amdgcn-amd-amdhsa-gfx950.s > profiles/r05_headline_opcodes.json
 Classes (measured, DESIGN.md 2 "Roofline", tools/issue_probe.py): FAST = unbroken VOP2 logic / add without carry, v_lshrrev imm, v_mov,
 3-VGPR v_bitop3 / v_and_or (2.3-3 clocks per wave64 instruction per SIMD); SLOW = v_alignbit, v_bfe, v_lshl_or, v_add_co / v_addc, DPP,
 v_readlane, anything with an SGPR / VCC source operand (4.1-4.3 clocks)."""
