@@ -99,6 +99,28 @@ __global__ __launch_bounds__(64) void format_pack_kernel(const uint32_t* __restr
 
 using namespace pa;
 
+// PA_ALIGN_PROFILE (diagnostics: where the time of a creation, an alignment call and a destruction goes), read once per process.
+static bool align_profile() {
+    static const bool on = getenv("PA_ALIGN_PROFILE") != nullptr;
+    return on;
+}
+
+// The marks of PA_ALIGN_PROFILE on stderr: "[tag] what  ms since the mark before".  lap() is the figure alone.
+struct PhaseClock {
+    const char* tag;
+    double t_mark = now();
+    explicit PhaseClock(const char* tag_) : tag(tag_) {}
+    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    double lap() {
+        const double t = now(), ms = t - t_mark;
+        t_mark = t;
+        return ms;
+    }
+    void mark(const char* what) {
+        if (align_profile()) std::fprintf(stderr, "[%s] %-28s %8.3f ms\n", tag, what, lap());
+    }
+};
+
 // ---- batched full DP ----------------------------------------------------------------------------
 
 struct pa_batch {
@@ -106,7 +128,7 @@ struct pa_batch {
         std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
         ~ReleaseScope() {
             release_scope_end();
-            if (getenv("PA_ALIGN_PROFILE"))
+            if (align_profile())
                 std::fprintf(stderr, "[pa_batch_destroy] buffers released %.3f ms after the batch was created\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         }
     } release_scope_;
@@ -198,7 +220,7 @@ struct pa_batch {
     // only and hands the buffers to the cache, where another thread may take them at once.  PA_POISON_ALLOC runs keep it honest.
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     ~pa_batch() {
-        static const bool prof = getenv("PA_ALIGN_PROFILE") != nullptr;
+        const bool prof = align_profile();
         const auto t0 = std::chrono::steady_clock::now();
         if (prof) {  // (diagnostics: which of the batch's streams is still busy)
             std::fprintf(stderr, "[pa_batch_destroy] busy: batch stream %d", stream && hipStreamQuery(stream) == hipErrorNotReady);
@@ -236,6 +258,43 @@ struct pa_batch {
         if (waited) bstream_give(stream, d_a.device);  // (the batch waited for its streams above: nothing of it is queued on the stream any more)
         else if (stream) (void)hipStreamDestroy(stream);
         slice::destroy(sliced);
+    }
+};
+
+// Pair i's two sequences, back from the device (an empty one is not copied).
+static bool fetch_pair(const pa_batch* p, size_t i, std::vector<uint8_t>& a, std::vector<uint8_t>& b) {
+    a.resize(p->n[i]);
+    b.resize(p->m[i]);
+    return (!p->n[i] || hip_ok(hipMemcpy(a.data(), p->d_a.as<uint8_t>() + p->a_off[i], p->n[i], hipMemcpyDeviceToHost), "D2H a")) &&
+           (!p->m[i] || hip_ok(hipMemcpy(b.data(), p->d_b.as<uint8_t>() + p->b_off[i], p->m[i], hipMemcpyDeviceToHost), "D2H b"));
+}
+
+// trace_kernel<dt, astar>: DT-trace keeps one DtLds per wavefront of the workgroup in LDS.
+static void launch_trace(bool dt, bool astar, dim3 grid, dim3 block, hipStream_t s, const TraceJob* jobs, const int32_t* list, int cnt, uint32_t* err) {
+    const size_t lds = dt ? (block.x / 64) * sizeof(DtLds) : 0;
+    if (dt && astar) hipLaunchKernelGGL((trace_kernel<true, true>), grid, block, lds, s, jobs, list, cnt, err);
+    else if (dt) hipLaunchKernelGGL((trace_kernel<true, false>), grid, block, lds, s, jobs, list, cnt, err);
+    else if (astar) hipLaunchKernelGGL((trace_kernel<false, true>), grid, block, lds, s, jobs, list, cnt, err);
+    else hipLaunchKernelGGL((trace_kernel<false, false>), grid, block, lds, s, jobs, list, cnt, err);
+}
+
+// The strings of one pa_batch_align call: the caller owns outputs only on success.  From the point where they are nulled until commit(),
+// leaving the call frees them all again (a view pointer into the plan's text buffer is not the caller's to free) and nulls the entries.
+struct CigarGuard {
+    const pa_batch* p;
+    char** out;  // (may be nullptr: costs only)
+    bool committed = false;
+    CigarGuard(const pa_batch* p_, char** out_) : p(p_), out(out_) {
+        for (size_t i = 0; out && i < p->pairs; ++i) out[i] = nullptr;
+    }
+    CigarGuard(const CigarGuard&) = delete;
+    void release(size_t i) {  // entry i is about to be replaced
+        if (!(p->view_mode && p->in_text(out[i]))) std::free(out[i]);
+        out[i] = nullptr;
+    }
+    void commit() { committed = true; }
+    ~CigarGuard() {
+        for (size_t i = 0; out && !committed && i < p->pairs; ++i) release(i);
     }
 };
 
@@ -455,8 +514,7 @@ static bool astar_start_order(pa_batch* p, std::vector<int32_t>& order) {
     order.resize(P);
     for (size_t i = 0; i < P; ++i) order[i] = (int32_t)i;
     if (getenv("PA_APA2_ORDER_INPUT") || P < 2) return true;
-    static const bool cprof = getenv("PA_ALIGN_PROFILE") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
+    PhaseClock clock("pa_batch_create");
     static_assert(sizeof(apa2::SketchDesc) == sizeof(PairDesc), "the sketch reads the batch's pair descriptors");
     std::vector<uint8_t> found(P, 64);
     const bool sketch = !getenv("PA_APA2_ORDER_LENGTH");
@@ -467,7 +525,7 @@ static bool astar_start_order(pa_batch* p, std::vector<int32_t>& order) {
             !hip_ok(hipMemcpyAsync(found.data(), p->d_sketch.ptr, P, hipMemcpyDeviceToHost, p->stream), "D2H sketch") || !hip_ok(hipStreamSynchronize(p->stream), "sync"))
             return false;
     }
-    const auto t1 = std::chrono::steady_clock::now();
+    const double sketch_ms = clock.lap();
     // e from found / 64 = (1 - e)^16, by table (nothing found: as if half a sample had been)
     double e_of[65];
     for (int f = 0; f <= 64; ++f) e_of[f] = 1.0 - std::pow(std::max(0.5, (double)f) / 64.0, 1.0 / 16.0);
@@ -482,9 +540,7 @@ static bool astar_start_order(pa_batch* p, std::vector<int32_t>& order) {
     }
     std::sort(keyed.begin(), keyed.end(), std::greater<uint64_t>());
     for (size_t i = 0; i < P; ++i) order[i] = (int32_t)(0xFFFFFFFFu - (uint32_t)(keyed[i] & 0xFFFFFFFFu));
-    if (cprof)
-        std::fprintf(stderr, "[pa_batch_create]   start order: sketch %.3f ms, sort %.3f ms\n", std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+    if (align_profile()) std::fprintf(stderr, "[%s]   start order: sketch %.3f ms, sort %.3f ms\n", clock.tag, sketch_ms, clock.lap());
     return true;
 }
 
@@ -603,7 +659,7 @@ static void parallel_pairs(size_t P, F&& f) {
 static bool astar_full_jobs(pa_batch* p, const uint8_t* const* a, const uint8_t* const* b, std::vector<TraceJob>& tjobs) {
     const engine::AstarPa2Params ap = engine::params_from_c(p->aparams_c);
     const size_t P = p->pairs;
-    static const bool cprof = getenv("PA_ALIGN_PROFILE") != nullptr;  // diagnostics: where the creation time goes
+    const bool cprof = align_profile();  // diagnostics: where the creation time goes
     auto cnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double c_mark = cnow();
     auto cmark = [&](const char* what) {
@@ -837,36 +893,39 @@ static bool astar_full_jobs(pa_batch* p, const uint8_t* const* a, const uint8_t*
     return true;
 }
 
-static pa_batch* batch_create(const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b, const size_t* b_len, size_t pairs,
-                              bool trace, float band_hint = -1.f, int dt_max_g = 0, int dt_fr_drop = 0, const pa_astarpa2_params* astar = nullptr,
-                              int window_override = -1) {
-    if (!ensure_device()) return nullptr;
-    static const bool cprof = getenv("PA_ALIGN_PROFILE") != nullptr;  // diagnostics: where the creation time goes
-    auto cnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double c_mark = cnow();
-    auto cmark = [&](const char* what) {
-        if (!cprof) return;
-        const double t = cnow();
-        std::fprintf(stderr, "[pa_batch_create] %-28s %8.3f ms\n", what, t - c_mark);
-        c_mark = t;
-    };
-    auto p = std::make_unique<pa_batch>();
-    p->pairs = pairs;
-    p->trace = trace;
+// The caller's pairs, as every pa_batch_create* entry point receives them.
+struct BatchInput {
+    const uint8_t* const* a;
+    const size_t* a_len;
+    const uint8_t* const* b;
+    const size_t* b_len;
+    size_t pairs;
+};
+
+// What the phases of batch_create share: the plan under construction, the input, and what layout_pairs summed up.
+struct CreateRun {
+    pa_batch* p;
+    const BatchInput& in;
+    const pa_astarpa2_params* astar;
     int slice_rows = 0;  // > 0: the batch runs bit-sliced with that many rows per lane (slice_plan.hpp)
-    if (astar) {
+    size_t ta = 0, tb = 0, tc = 0, tp = 0, tg = 0;  // device layout: bytes of a and b, code words, profile words, hand-off granules
+};
+
+// A*PA2: the windows of the column store.  Else the shape of the strips: banded (thresholds first), or chained / sequential / bit-sliced.
+static void choose_shape(CreateRun& cr, float band_hint, int window_override) {
+    pa_batch* p = cr.p;
+    const size_t *a_len = cr.in.a_len, *b_len = cr.in.b_len, pairs = cr.in.pairs;
+    if (cr.astar) {
         p->astar = true;
-        p->aparams_c = *astar;
-        p->astar_full = !apa2_supported(engine::params_from_c(*astar));  // GCSH / pruning / incremental doubling: apa2_full_kernel.hpp
+        p->aparams_c = *cr.astar;
+        p->astar_full = !apa2_supported(engine::params_from_c(*cr.astar));  // GCSH / pruning / incremental doubling: apa2_full_kernel.hpp
         p->window_override = window_override;
-        const bool gcsh = engine::params_from_c(*astar).heuristic == engine::HeuristicKind::GCSH;
+        const bool gcsh = engine::params_from_c(*cr.astar).heuristic == engine::HeuristicKind::GCSH;
         for (size_t i = 0; i < pairs; ++i) {
             p->win_words.push_back((uint32_t)window_words(a_len[i], b_len[i], gcsh, window_override));
             p->slot_ratio.push_back(a_len[i] ? (uint32_t)std::min<uint64_t>(((uint64_t)b_len[i] << 20) / (uint64_t)a_len[i], 0xFFFFFFFFull) : 0u);
         }
     }
-    p->dt_max_g = dt_max_g;
-    p->dt_fr_drop = dt_fr_drop;
     p->banded = band_hint >= 0.f;
     if (p->banded) {
         for (size_t i = 0; i < pairs; ++i) {
@@ -876,163 +935,177 @@ static pa_batch* batch_create(const uint8_t* const* a, const size_t* a_len, cons
             const long d = std::labs((long)a_len[i] - (long)b_len[i]);
             p->band_t.push_back((int32_t)std::min<double>(d + std::ceil(band_hint * len) + 32, (double)a_len[i] + (double)b_len[i] + 64));
         }
-        choose_band_shape(p.get());
+        choose_band_shape(p);
         p->n.clear();
         p->m.clear();
-    } else {
-        const BatchShape sh = astar ? BatchShape() : choose_batch_shape(a_len, b_len, pairs);
-        p->k = sh.k;
-        p->sequential = sh.sequential;
-        p->block_waves = sh.block_waves;
-        if (!astar && !trace) {  // a cost-only batch big enough for groups of 32 pairs: the bit-sliced kernel, when its estimate is the lower one
-            double est = -1;
-            const double simds = (double)device_cus() * 4.0;
-            const int R = slice::choose_rows_per_lane(a_len, b_len, pairs, simds, &est);
-            const bool forced = getenv("PA_SLICE") && atoi(getenv("PA_SLICE")) > 0;
-            if (R > 0 && (forced || sh.est_ns < 0 || est < sh.est_ns)) slice_rows = R;
-        }
+        return;
     }
-    size_t ta = 0, tb = 0, tc = 0, tp = 0, tg = 0;
-    for (size_t i = 0; i < pairs; ++i) {
+    const BatchShape sh = cr.astar ? BatchShape() : choose_batch_shape(a_len, b_len, pairs);
+    p->k = sh.k;
+    p->sequential = sh.sequential;
+    p->block_waves = sh.block_waves;
+    if (!cr.astar && !p->trace) {  // a cost-only batch big enough for groups of 32 pairs: the bit-sliced kernel, when its estimate is the lower one
+        double est = -1;
+        const double simds = (double)device_cus() * 4.0;
+        const int R = slice::choose_rows_per_lane(a_len, b_len, pairs, simds, &est);
+        const bool forced = getenv("PA_SLICE") && atoi(getenv("PA_SLICE")) > 0;
+        if (R > 0 && (forced || sh.est_ns < 0 || est < sh.est_ns)) cr.slice_rows = R;
+    }
+}
+
+// Every pair's offsets into the device layout, the totals, and the sums the plan reports (pa_batch_stats).
+static bool layout_pairs(CreateRun& cr) {
+    pa_batch* p = cr.p;
+    const size_t *a_len = cr.in.a_len, *b_len = cr.in.b_len;
+    for (size_t i = 0; i < cr.in.pairs; ++i) {
         if (a_len[i] > (size_t)(1u << 30) || b_len[i] > (size_t)(1u << 30)) {
             set_error("sequence too long");
-            return nullptr;
+            return false;
         }
         p->n.push_back(a_len[i]);
         p->m.push_back(b_len[i]);
-        p->a_off.push_back(ta);
-        p->b_off.push_back(tb);
-        p->code_off.push_back(tc);
-        p->prof_off.push_back(tp);
-        p->gran_off.push_back(tg);
+        p->a_off.push_back(cr.ta);
+        p->b_off.push_back(cr.tb);
+        p->code_off.push_back(cr.tc);
+        p->prof_off.push_back(cr.tp);
+        p->gran_off.push_back(cr.tg);
         const size_t w = (b_len[i] + 63) / 64;
-        ta += (a_len[i] + 15) & ~size_t(15);
-        tb += (b_len[i] + 15) & ~size_t(15);
-        tc += (a_len[i] + 15) / 16;
-        tp += w;
-        tg += (astar || slice_rows) ? 0
-              : p->banded ? (size_t)(p->sequential ? 2 : std::max(1, strip_plan((int)w, p->k, false).strips() - 1)) * (a_len[i] / 32 + 2)
-                          : rect_granules((int)a_len[i], (int)w, p->k, p->sequential);
+        cr.ta += (a_len[i] + 15) & ~size_t(15);
+        cr.tb += (b_len[i] + 15) & ~size_t(15);
+        cr.tc += (a_len[i] + 15) / 16;
+        cr.tp += w;
+        cr.tg += (cr.astar || cr.slice_rows) ? 0
+                 : p->banded ? (size_t)(p->sequential ? 2 : std::max(1, strip_plan((int)w, p->k, false).strips() - 1)) * (a_len[i] / 32 + 2)
+                             : rect_granules((int)a_len[i], (int)w, p->k, p->sequential);
         p->cells += (double)a_len[i] * (double)b_len[i];
         p->word_updates += (double)a_len[i] * (double)w;
         // algorithmic HBM bytes, cost-only rectangle: 0.75 B/column + 48 B/word
         p->algo_bytes += 0.75 * (double)a_len[i] + 48.0 * (double)w;
     }
-    p->total_gran = tg;
-    if (trace) {
-        size_t tck = 0, tcg = 0, tw = 0;
-        for (size_t i = 0; i < pairs; ++i) {
-            const size_t w = (b_len[i] + 63) / 64;
-            p->ckpt_off.push_back(tck);
-            p->cigar_off.push_back(tcg);
-            p->word_off.push_back(tw);
-            tw += std::min<size_t>(std::max<size_t>(w, 1), (size_t)kTraceScratchWords);
-            // u32: one V column per 256 columns of a (slot 0 unused); A*PA2 mode: slots 0 .. ceil(n / 256)
-            tck += astar ? ((a_len[i] + 255) / 256 + 1) * (size_t)p->win_words[i] * 4 : (a_len[i] / 256 + 1) * w * 4;
-            tcg += a_len[i] + b_len[i] + 2;
-        }
-        if (tcg >= (size_t(1) << 62) || !p->d_ckpt.alloc(tck * 4) || !p->d_cigar.alloc(tcg * 4) || !p->d_packed.alloc(tcg) ||
-            !p->d_tlen_pos.alloc(std::max<size_t>(pairs * 4, 16)) || !p->d_dst_pos.alloc(std::max<size_t>(pairs * 8, 16)) || !p->d_cmeta.alloc(256) ||
-            !p->d_cigar_len.alloc(std::max<size_t>(pairs * 4, 16)) || !p->d_costs.alloc(std::max<size_t>(pairs * 4, 16)) ||
-            // re-fill scratch: 256 columns x min(w, kTraceScratchWords) words of V per pair
-            !p->d_scratch_v.alloc(std::max<size_t>(tw, 1) * 16) || !p->d_scratch_vals.alloc(std::max<size_t>(tw, 1) * 256 * 16) ||
-            !p->d_scratch_gran.alloc(std::max<size_t>(pairs, 1) * 16 * 8) ||
-            !p->d_tjobs.alloc(std::max<size_t>(pairs, 1) * sizeof(TraceJob)) || !p->d_cig_src_off.alloc(std::max<size_t>(pairs, 1) * 8))
-            return nullptr;
+    p->total_gran = cr.tg;
+    return true;
+}
+
+// Traced batches: checkpoints (A*PA2: the block-column store), CIGAR elements and text, the traceback's scratch and jobs.
+static bool alloc_trace_buffers(CreateRun& cr) {
+    pa_batch* p = cr.p;
+    const size_t *a_len = cr.in.a_len, *b_len = cr.in.b_len, pairs = cr.in.pairs;
+    size_t tck = 0, tcg = 0, tw = 0;
+    for (size_t i = 0; i < pairs; ++i) {
+        const size_t w = (b_len[i] + 63) / 64;
+        p->ckpt_off.push_back(tck);
+        p->cigar_off.push_back(tcg);
+        p->word_off.push_back(tw);
+        tw += std::min<size_t>(std::max<size_t>(w, 1), (size_t)kTraceScratchWords);
+        // u32: one V column per 256 columns of a (slot 0 unused); A*PA2 mode: slots 0 .. ceil(n / 256)
+        tck += cr.astar ? ((a_len[i] + 255) / 256 + 1) * (size_t)p->win_words[i] * 4 : (a_len[i] / 256 + 1) * w * 4;
+        tcg += a_len[i] + b_len[i] + 2;
     }
-    if (!p->d_a.alloc(ta) || !p->d_b.alloc(tb) || !p->d_codes.alloc(tc * 4) || !p->d_prof.alloc(tp * 16) ||
-        !p->d_v.alloc(tp * 16) || !p->d_gran.alloc(tg * 8) || !p->d_sums.alloc(std::max<size_t>(pairs * 4, 16)) || !p->d_misc.alloc(32))
-        return nullptr;
-    cmark("host layout + hipMalloc");
-    if (!(p->stream = bstream_take()) || !hip_ok(hipEventCreate(&p->ev0), "event") ||
-        !hip_ok(hipEventCreate(&p->ev1), "event") || !hip_ok(hipEventCreate(&p->ev2), "event"))
-        return nullptr;
-    cmark("stream + events");
-    // Upload: the sequences are gathered into the device layout through two pinned staging buffers, so that the copy of one
-    // chunk overlaps the gathering of the next and runs at link speed (a pageable H2D of 800 MB costs 5x as much).
-    {
-        const size_t kChunk = size_t(32) << 20;
-        // the two pinned buffers are kept for the life of the process (pinning 64 MB costs more than uploading 200 MB);
-        // one creation at a time uses them
-        static std::mutex stage_mutex;
-        static uint8_t* stage_cache[2] = {nullptr, nullptr};
-        std::lock_guard<std::mutex> stage_lock(stage_mutex);
-        uint8_t* stage[2] = {nullptr, nullptr};
-        hipEvent_t done[2] = {nullptr, nullptr};
-        bool ok = true;
-        for (int k = 0; k < 2 && ok; ++k) {
-            if (!stage_cache[k]) {
-                void* hp = nullptr;
-                ok = hip_ok(hipHostMalloc(&hp, kChunk, hipHostMallocDefault), "hipHostMalloc(upload staging)");
-                stage_cache[k] = (uint8_t*)hp;
-            }
-            ok = ok && hip_ok(hipEventCreate(&done[k]), "event");
-            stage[k] = stage_cache[k];
+    return !(tcg >= (size_t(1) << 62) || !p->d_ckpt.alloc(tck * 4) || !p->d_cigar.alloc(tcg * 4) || !p->d_packed.alloc(tcg) ||
+             !p->d_tlen_pos.alloc(std::max<size_t>(pairs * 4, 16)) || !p->d_dst_pos.alloc(std::max<size_t>(pairs * 8, 16)) || !p->d_cmeta.alloc(256) ||
+             !p->d_cigar_len.alloc(std::max<size_t>(pairs * 4, 16)) || !p->d_costs.alloc(std::max<size_t>(pairs * 4, 16)) ||
+             // re-fill scratch: 256 columns x min(w, kTraceScratchWords) words of V per pair
+             !p->d_scratch_v.alloc(std::max<size_t>(tw, 1) * 16) || !p->d_scratch_vals.alloc(std::max<size_t>(tw, 1) * 256 * 16) ||
+             !p->d_scratch_gran.alloc(std::max<size_t>(pairs, 1) * 16 * 8) ||
+             !p->d_tjobs.alloc(std::max<size_t>(pairs, 1) * sizeof(TraceJob)) || !p->d_cig_src_off.alloc(std::max<size_t>(pairs, 1) * 8));
+}
+
+static bool alloc_batch_buffers(CreateRun& cr) {
+    pa_batch* p = cr.p;
+    return p->d_a.alloc(cr.ta) && p->d_b.alloc(cr.tb) && p->d_codes.alloc(cr.tc * 4) && p->d_prof.alloc(cr.tp * 16) && p->d_v.alloc(cr.tp * 16) &&
+           p->d_gran.alloc(cr.tg * 8) && p->d_sums.alloc(std::max<size_t>(cr.in.pairs * 4, 16)) && p->d_misc.alloc(32);
+}
+
+// Upload: the sequences are gathered into the device layout through two pinned staging buffers, so that the copy of one
+// chunk overlaps the gathering of the next and runs at link speed (a pageable H2D of 800 MB costs 5x as much).
+static bool upload_sequences(CreateRun& cr) {
+    pa_batch* p = cr.p;
+    const size_t pairs = cr.in.pairs;
+    const size_t kChunk = size_t(32) << 20;
+    // the two pinned buffers are kept for the life of the process (pinning 64 MB costs more than uploading 200 MB);
+    // one creation at a time uses them
+    static std::mutex stage_mutex;
+    static uint8_t* stage_cache[2] = {nullptr, nullptr};
+    std::lock_guard<std::mutex> stage_lock(stage_mutex);
+    uint8_t* stage[2] = {nullptr, nullptr};
+    hipEvent_t done[2] = {nullptr, nullptr};
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; ++k) {
+        if (!stage_cache[k]) {
+            void* hp = nullptr;
+            ok = hip_ok(hipHostMalloc(&hp, kChunk, hipHostMallocDefault), "hipHostMalloc(upload staging)");
+            stage_cache[k] = (uint8_t*)hp;
         }
-        bool used[2] = {false, false};  // a staging buffer is reused only after its previous copy has finished
-        int buf = 0;
-        auto upload = [&](uint8_t* dev, const std::vector<size_t>& off, const uint8_t* const* src, const size_t* len, size_t total) {
-            // walk the device image [0, total) in chunks; every chunk is assembled from the pairs that intersect it
-            size_t pair = 0;
-            for (size_t base = 0; base < total && ok; base += kChunk, buf ^= 1) {
-                const size_t end = std::min(total, base + kChunk);
-                if (used[buf]) ok = hip_ok(hipEventSynchronize(done[buf]), "event sync");
-                while (pair < pairs && off[pair] + len[pair] <= base) ++pair;
-                // the pieces of this chunk: (pair, first byte, end, end of the piece before) -- only the padding between two sequences
-                // needs zeroing.  A big chunk is gathered by several threads (round 5: one thread copies 12-16 GB/s, less than the link
-                // takes; the C4 batch's 200 MB: 12.5 ms of its 16 ms creation)
-                struct Piece {
-                    size_t q, lo, hi, prev;
-                };
-                std::vector<Piece> pieces;
-                size_t cur = base;
-                for (size_t q = pair; q < pairs && off[q] < end; ++q) {
-                    const size_t lo = std::max(off[q], base), hi = std::min(off[q] + len[q], end);
-                    if (lo >= hi) continue;
-                    pieces.push_back(Piece{q, lo, hi, cur});
-                    cur = hi;
-                }
-                uint8_t* const dst = stage[buf];
-                auto gather = [&, dst, base](size_t p0, size_t p1) {
-                    for (size_t t = p0; t < p1; ++t) {
-                        const Piece& pc = pieces[t];
-                        if (pc.lo > pc.prev) std::memset(dst + (pc.prev - base), 0, pc.lo - pc.prev);
-                        std::memcpy(dst + (pc.lo - base), src[pc.q] + (pc.lo - off[pc.q]), pc.hi - pc.lo);
-                    }
-                };
-                const size_t nthreads = (end - base >= (size_t(8) << 20) && pieces.size() >= 8) ? std::min<size_t>(4, host_threads()) : 1;
-                if (nthreads > 1) {
-                    std::vector<std::thread> th;
-                    for (size_t t = 1; t < nthreads; ++t) th.emplace_back(gather, pieces.size() * t / nthreads, pieces.size() * (t + 1) / nthreads);
-                    gather(0, pieces.size() / nthreads);
-                    for (auto& x : th) x.join();
-                } else {
-                    gather(0, pieces.size());
-                }
-                if (end > cur) std::memset(stage[buf] + (cur - base), 0, end - cur);
-                ok = ok && hip_ok(hipMemcpyAsync(dev + base, stage[buf], end - base, hipMemcpyHostToDevice, p->stream), "H2D sequences") &&
-                     hip_ok(hipEventRecord(done[buf], p->stream), "event");
-                used[buf] = true;
-            }
-        };
-        if (ok) upload(p->d_a.as<uint8_t>(), p->a_off, a, a_len, ta);
-        if (ok) upload(p->d_b.as<uint8_t>(), p->b_off, b, b_len, tb);
-        ok = ok && hip_ok(hipStreamSynchronize(p->stream), "sync");
-        for (int k = 0; k < 2; ++k)
-            if (done[k]) (void)hipEventDestroy(done[k]);
-        if (!ok) return nullptr;
+        ok = ok && hip_ok(hipEventCreate(&done[k]), "event");
+        stage[k] = stage_cache[k];
     }
-    cmark("upload of the sequences");
-    // Jobs: pair-major, strips of a pair consecutive (ticket order == dependency order).
+    bool used[2] = {false, false};  // a staging buffer is reused only after its previous copy has finished
+    int buf = 0;
+    auto upload = [&](uint8_t* dev, const std::vector<size_t>& off, const uint8_t* const* src, const size_t* len, size_t total) {
+        // walk the device image [0, total) in chunks; every chunk is assembled from the pairs that intersect it
+        size_t pair = 0;
+        for (size_t base = 0; base < total && ok; base += kChunk, buf ^= 1) {
+            const size_t end = std::min(total, base + kChunk);
+            if (used[buf]) ok = hip_ok(hipEventSynchronize(done[buf]), "event sync");
+            while (pair < pairs && off[pair] + len[pair] <= base) ++pair;
+            // the pieces of this chunk: (pair, first byte, end, end of the piece before) -- only the padding between two sequences
+            // needs zeroing.  A big chunk is gathered by several threads (round 5: one thread copies 12-16 GB/s, less than the link
+            // takes; the C4 batch's 200 MB: 12.5 ms of its 16 ms creation)
+            struct Piece {
+                size_t q, lo, hi, prev;
+            };
+            std::vector<Piece> pieces;
+            size_t cur = base;
+            for (size_t q = pair; q < pairs && off[q] < end; ++q) {
+                const size_t lo = std::max(off[q], base), hi = std::min(off[q] + len[q], end);
+                if (lo >= hi) continue;
+                pieces.push_back(Piece{q, lo, hi, cur});
+                cur = hi;
+            }
+            uint8_t* const dst = stage[buf];
+            auto gather = [&, dst, base](size_t p0, size_t p1) {
+                for (size_t t = p0; t < p1; ++t) {
+                    const Piece& pc = pieces[t];
+                    if (pc.lo > pc.prev) std::memset(dst + (pc.prev - base), 0, pc.lo - pc.prev);
+                    std::memcpy(dst + (pc.lo - base), src[pc.q] + (pc.lo - off[pc.q]), pc.hi - pc.lo);
+                }
+            };
+            const size_t nthreads = (end - base >= (size_t(8) << 20) && pieces.size() >= 8) ? std::min<size_t>(4, host_threads()) : 1;
+            if (nthreads > 1) {
+                std::vector<std::thread> th;
+                for (size_t t = 1; t < nthreads; ++t) th.emplace_back(gather, pieces.size() * t / nthreads, pieces.size() * (t + 1) / nthreads);
+                gather(0, pieces.size() / nthreads);
+                for (auto& x : th) x.join();
+            } else {
+                gather(0, pieces.size());
+            }
+            if (end > cur) std::memset(stage[buf] + (cur - base), 0, end - cur);
+            ok = ok && hip_ok(hipMemcpyAsync(dev + base, stage[buf], end - base, hipMemcpyHostToDevice, p->stream), "H2D sequences") &&
+                 hip_ok(hipEventRecord(done[buf], p->stream), "event");
+            used[buf] = true;
+        }
+    };
+    if (ok) upload(p->d_a.as<uint8_t>(), p->a_off, cr.in.a, cr.in.a_len, cr.ta);
+    if (ok) upload(p->d_b.as<uint8_t>(), p->b_off, cr.in.b, cr.in.b_len, cr.tb);
+    ok = ok && hip_ok(hipStreamSynchronize(p->stream), "sync");
+    for (int k = 0; k < 2; ++k)
+        if (done[k]) (void)hipEventDestroy(done[k]);
+    return ok;
+}
+
+// Jobs: pair-major, strips of a pair consecutive (ticket order == dependency order).  first[i]: pair i's first job (+ end).
+static void plan_strip_jobs(CreateRun& cr, std::vector<int32_t>& first) {
+    pa_batch* p = cr.p;
+    const size_t *a_len = cr.in.a_len, *b_len = cr.in.b_len, pairs = cr.in.pairs;
     p->last_job.assign(pairs, -1);
-    std::vector<int32_t> first(pairs + 1, 0);
+    first.assign(pairs + 1, 0);
     for (size_t i = 0; i < pairs; ++i) {
         first[i] = (int32_t)p->jobs.size();
         first[i + 1] = first[i];
         const int w = (int)((b_len[i] + 63) / 64);
-        if (w == 0 || a_len[i] == 0 || astar || slice_rows) continue;
+        if (w == 0 || a_len[i] == 0 || cr.astar || cr.slice_rows) continue;
         if (p->banded) {
-            plan_banded_pair(p.get(), i, p->band_t[i], p->jobs);
+            plan_banded_pair(p, i, p->band_t[i], p->jobs);
             p->last_job[i] = (int)p->jobs.size() - 1;
             first[i + 1] = (int32_t)p->jobs.size();
             continue;
@@ -1052,7 +1125,7 @@ static pa_batch* batch_create(const uint8_t* const* a, const size_t* a_len, cons
         r.tail_rows = (int)b_len[i];
         r.k = p->k;
         r.pingpong = p->sequential;
-        if (trace) {
+        if (p->trace) {
             r.ckpt = p->d_ckpt.as<uint32_t>() + p->ckpt_off[i];
             r.ckpt_stride = w;
         }
@@ -1060,136 +1133,185 @@ static pa_batch* batch_create(const uint8_t* const* a, const size_t* a_len, cons
         p->last_job[i] = (int)p->jobs.size() - 1;
         first[i + 1] = (int32_t)p->jobs.size();
     }
+}
+
+// (sequential) every pair's first job, and the pair descriptors; both come from host vectors that do not outlive the creation
+static bool upload_first_and_desc(CreateRun& cr, const std::vector<int32_t>& first) {
+    pa_batch* p = cr.p;
+    const size_t pairs = cr.in.pairs;
     if (p->sequential) {
-        if (!p->d_first.alloc(first.size() * 4)) return nullptr;
-        if (!hip_ok(hipMemcpyAsync(p->d_first.ptr, first.data(), first.size() * 4, hipMemcpyHostToDevice, p->stream), "H2D first")) return nullptr;
-        if (!hip_ok(hipStreamSynchronize(p->stream), "sync")) return nullptr;  // `first` is a local
+        if (!p->d_first.alloc(first.size() * 4)) return false;
+        if (!hip_ok(hipMemcpyAsync(p->d_first.ptr, first.data(), first.size() * 4, hipMemcpyHostToDevice, p->stream), "H2D first")) return false;
+        if (!hip_ok(hipStreamSynchronize(p->stream), "sync")) return false;  // `first` is a local
     }
-    {
-        std::vector<PairDesc> desc(pairs);
-        for (size_t i = 0; i < pairs; ++i) {
-            desc[i] = PairDesc{p->a_off[i], p->b_off[i], p->code_off[i], p->prof_off[i], (int)a_len[i], (int)b_len[i]};
-            p->max_n = std::max(p->max_n, a_len[i]);
-            p->max_m = std::max(p->max_m, b_len[i]);
-        }
-        if (!p->d_desc.alloc(pairs * sizeof(PairDesc))) return nullptr;
-        if (pairs && !hip_ok(hipMemcpyAsync(p->d_desc.ptr, desc.data(), pairs * sizeof(PairDesc), hipMemcpyHostToDevice, p->stream), "H2D desc"))
-            return nullptr;
-        if (!hip_ok(hipStreamSynchronize(p->stream), "sync")) return nullptr;  // desc is a local
+    std::vector<PairDesc> desc(pairs);
+    for (size_t i = 0; i < pairs; ++i) {
+        desc[i] = PairDesc{p->a_off[i], p->b_off[i], p->code_off[i], p->prof_off[i], (int)cr.in.a_len[i], (int)cr.in.b_len[i]};
+        p->max_n = std::max(p->max_n, cr.in.a_len[i]);
+        p->max_m = std::max(p->max_m, cr.in.b_len[i]);
     }
-    if (trace && pairs) {
-        std::vector<TraceJob> tjobs(pairs);
-        std::vector<uint64_t> src_off(pairs);
-        for (size_t i = 0; i < pairs; ++i) {
-            TraceJob& t = tjobs[i];
-            t.a = p->d_a.as<uint8_t>() + p->a_off[i];
-            t.b = p->d_b.as<uint8_t>() + p->b_off[i];
-            t.a_codes = p->d_codes.as<uint32_t>() + p->code_off[i];
-            t.b_prof = p->d_prof.as<uint32_t>() + p->prof_off[i] * 4;
-            t.ckpt = p->d_ckpt.as<uint32_t>() + p->ckpt_off[i];
-            t.final_v = p->d_v.as<uint32_t>() + p->prof_off[i] * 4;
-            t.sum = p->d_sums.as<int32_t>() + i;
-            t.cigar = p->d_cigar.as<uint32_t>() + p->cigar_off[i];
-            t.cigar_len = p->d_cigar_len.as<uint32_t>() + i;
-            t.cost_out = p->d_costs.as<int32_t>() + i;
-            t.scratch_v = p->d_scratch_v.as<uint32_t>() + p->word_off[i] * 4;
-            t.scratch_vals = p->d_scratch_vals.as<uint32_t>() + p->word_off[i] * 256 * 4;
-            t.scratch_gran = p->d_scratch_gran.as<uint64_t>() + i * 16;
-            t.scratch_words = (int32_t)std::min<size_t>(std::max<size_t>((b_len[i] + 63) / 64, 1), (size_t)kTraceScratchWords);
-            t.n = (int32_t)a_len[i];
-            t.m = (int32_t)b_len[i];
-            t.w = (int32_t)((b_len[i] + 63) / 64);
-            t.cigar_cap = (uint32_t)std::min<size_t>(a_len[i] + b_len[i] + 2, 0xFFFFFFF0u);
-            t.dt_max_g = dt_max_g;
-            t.dt_fr_drop = dt_fr_drop;
-            t.win = t.w;
-            t.slot_ratio = 0;
-            src_off[i] = p->cigar_off[i];
-        }
-        if (astar && !(p->astar_full ? astar_full_jobs(p.get(), a, b, tjobs) : astar_jobs(p.get(), a, b, tjobs))) return nullptr;
-        if (!astar) {  // (the plain traced batch: chunks of the pairs as they come)
-            p->order_host.resize(pairs);
-            for (size_t i = 0; i < pairs; ++i) p->order_host[i] = (int32_t)i;
-            if (!p->d_order.alloc(pairs * 4) || !hip_ok(hipMemcpy(p->d_order.ptr, p->order_host.data(), pairs * 4, hipMemcpyHostToDevice), "H2D order")) return nullptr;
-        }
-        {
-            // chunks of pa_batch_align.  ONE by default: measured in round 4 (profiles/README.md), chunks on streams of their own do not
-            // shorten the call -- band search and traceback are both bound by instruction issue, so running the traceback of one chunk
-            // beside the band search of the next gains nothing (C4: 24.65 against 25.0 ms at the C ABI with four chunks), and chunks too
-            // small to fill the chip lose (4096 x 100 kbp in three chunks: 135 against 120 ms).  PA_ALIGN_CHUNKS=n for experiments.
-            static const int env_chunks = getenv("PA_ALIGN_CHUNKS") ? atoi(getenv("PA_ALIGN_CHUNKS")) : 0;
-            // (Until the traceback started its expensive pairs first, four chunks paid for many SHORT pairs -- C4: 24.1 against 26.0 ms --
-            //  by cutting the traceback's tail; with the ordering one chunk is ahead there too: 22.3 against 22.9 ms.)
-            int C = 1;
-            if (env_chunks > 0) C = std::min<int>(env_chunks, pa_batch::kMaxChunks);
-            C = (int)std::max<size_t>(1, std::min<size_t>((size_t)C, pairs));
-            p->chunk_lo.assign((size_t)C + 1, 0);
-            p->chunk_base.assign((size_t)C + 1, 0);
-            for (int c = 0; c <= C; ++c) p->chunk_lo[(size_t)c] = pairs * (size_t)c / (size_t)C;
-            uint64_t acc = 0;
-            for (int c = 0; c < C; ++c) {
-                p->chunk_base[(size_t)c] = acc;
-                for (size_t q = p->chunk_lo[(size_t)c]; q < p->chunk_lo[(size_t)c + 1]; ++q) {
-                    const size_t i = (size_t)p->order_host[q];
-                    acc += a_len[i] + b_len[i] + 2;
-                }
-            }
-            p->chunk_base[(size_t)C] = acc;
-            p->torder_host = p->order_host;
-            for (int c = 0; c < C; ++c) std::sort(p->torder_host.begin() + (long)p->chunk_lo[(size_t)c], p->torder_host.begin() + (long)p->chunk_lo[(size_t)c + 1]);
-            if (!p->d_torder.alloc(std::max<size_t>(pairs, 1) * 4) || !p->d_tlist.alloc(std::max<size_t>(pairs, 1) * 4) ||
-                !hip_ok(hipMemcpy(p->d_torder.ptr, p->torder_host.data(), pairs * 4, hipMemcpyHostToDevice), "H2D trace order"))
-                return nullptr;
-            for (size_t i = 0; i < pairs; ++i) p->max_nm = (uint32_t)std::max<size_t>(p->max_nm, std::min<size_t>(a_len[i] + b_len[i], 0x7FFFFFFFu));
-            p->h_meta = (uint8_t*)pinned_take(64 + pairs * 12 + 64, &p->h_meta_size);
-            if (!p->h_meta) return nullptr;
-            if (!hip_ok(hipEventCreate(&p->ev_pre), "event")) return nullptr;
-            for (int c = 0; c < C; ++c)
-                if (!(p->cstream[c] = stream_take()) || !hip_ok(hipEventCreate(&p->evF0[c]), "event") ||
-                    !hip_ok(hipEventCreate(&p->evF1[c]), "event") || !hip_ok(hipEventCreate(&p->evT1[c]), "event"))
-                    return nullptr;
-        }
-        if (!hip_ok(hipMemsetAsync(p->d_scratch_gran.ptr, 0, pairs * 16 * 8, p->stream), "memset trace granules") ||
-            !hip_ok(hipMemcpyAsync(p->d_tjobs.ptr, tjobs.data(), pairs * sizeof(TraceJob), hipMemcpyHostToDevice, p->stream), "H2D trace jobs") ||
-            !hip_ok(hipMemcpyAsync(p->d_cig_src_off.ptr, src_off.data(), pairs * 8, hipMemcpyHostToDevice, p->stream), "H2D offsets") ||
-            !hip_ok(hipStreamSynchronize(p->stream), "sync"))
-            return nullptr;
+    if (!p->d_desc.alloc(pairs * sizeof(PairDesc))) return false;
+    if (pairs && !hip_ok(hipMemcpyAsync(p->d_desc.ptr, desc.data(), pairs * sizeof(PairDesc), hipMemcpyHostToDevice, p->stream), "H2D desc"))
+        return false;
+    return hip_ok(hipStreamSynchronize(p->stream), "sync");  // desc is a local
+}
+
+// The traceback's per-pair jobs; A*PA2 completes them (and decides the start order), a plain traced batch takes the pairs as they come.
+static bool make_trace_jobs(CreateRun& cr, std::vector<TraceJob>& tjobs, std::vector<uint64_t>& src_off) {
+    pa_batch* p = cr.p;
+    const size_t *a_len = cr.in.a_len, *b_len = cr.in.b_len, pairs = cr.in.pairs;
+    for (size_t i = 0; i < pairs; ++i) {
+        TraceJob& t = tjobs[i];
+        t.a = p->d_a.as<uint8_t>() + p->a_off[i];
+        t.b = p->d_b.as<uint8_t>() + p->b_off[i];
+        t.a_codes = p->d_codes.as<uint32_t>() + p->code_off[i];
+        t.b_prof = p->d_prof.as<uint32_t>() + p->prof_off[i] * 4;
+        t.ckpt = p->d_ckpt.as<uint32_t>() + p->ckpt_off[i];
+        t.final_v = p->d_v.as<uint32_t>() + p->prof_off[i] * 4;
+        t.sum = p->d_sums.as<int32_t>() + i;
+        t.cigar = p->d_cigar.as<uint32_t>() + p->cigar_off[i];
+        t.cigar_len = p->d_cigar_len.as<uint32_t>() + i;
+        t.cost_out = p->d_costs.as<int32_t>() + i;
+        t.scratch_v = p->d_scratch_v.as<uint32_t>() + p->word_off[i] * 4;
+        t.scratch_vals = p->d_scratch_vals.as<uint32_t>() + p->word_off[i] * 256 * 4;
+        t.scratch_gran = p->d_scratch_gran.as<uint64_t>() + i * 16;
+        t.scratch_words = (int32_t)std::min<size_t>(std::max<size_t>((b_len[i] + 63) / 64, 1), (size_t)kTraceScratchWords);
+        t.n = (int32_t)a_len[i];
+        t.m = (int32_t)b_len[i];
+        t.w = (int32_t)((b_len[i] + 63) / 64);
+        t.cigar_cap = (uint32_t)std::min<size_t>(a_len[i] + b_len[i] + 2, 0xFFFFFFF0u);
+        t.dt_max_g = p->dt_max_g;
+        t.dt_fr_drop = p->dt_fr_drop;
+        t.win = t.w;
+        t.slot_ratio = 0;
+        src_off[i] = p->cigar_off[i];
     }
-    if (!p->sequential && !p->trace && !p->banded && !p->jobs.empty()) {
-        // Chained batches beyond one wavefront per SIMD: a SIMD serves its OLDEST wavefront first, the younger ones get what is
-        // left, and a chain advances at the pace of its most starved strip -- so pairs finish staggered by wave slot and the
-        // tail of the launch runs on a mostly idle chip (PA_STRIP_WAVELOG shows it).  The top strip of every pair therefore
-        // paces itself against the average progress of all pairs (strip_kernel.hpp kJobPace).
-        // Both need every strip resident (at most four wavefronts per SIMD at <= 128 VGPRs); beyond that strips queue in ticket
-        // order and only the priority rotation is kept.
-        static const bool no_pace = getenv("PA_STRIP_NO_PACE") != nullptr;
-        static const bool no_rotate = getenv("PA_STRIP_NO_ROTATE") != nullptr;
-        const size_t simds = (size_t)device_cus() * 4;
-        int tops = 0;
-        for (const StripJob& j : p->jobs) tops += j.hin_gran == nullptr;
-        for (StripJob& j : p->jobs) {
-            if (p->jobs.size() > simds && !no_rotate) j.flags |= kJobRotatePrio;
-            if (!no_pace && p->jobs.size() > simds && p->jobs.size() <= 4 * simds && j.hin_gran == nullptr && tops > 1) {
-                j.flags |= kJobPace;
-                j.ckpt = p->d_misc.as<uint32_t>() + 4;  // the u64 progress counter (zeroed with the ticket before every pass)
-                j.ckpt_stride = tops;
-            }
+    if (cr.astar) return p->astar_full ? astar_full_jobs(p, cr.in.a, cr.in.b, tjobs) : astar_jobs(p, cr.in.a, cr.in.b, tjobs);
+    // (the plain traced batch: chunks of the pairs as they come)
+    p->order_host.resize(pairs);
+    for (size_t i = 0; i < pairs; ++i) p->order_host[i] = (int32_t)i;
+    return p->d_order.alloc(pairs * 4) && hip_ok(hipMemcpy(p->d_order.ptr, p->order_host.data(), pairs * 4, hipMemcpyHostToDevice), "H2D order");
+}
+
+// chunks of pa_batch_align.  ONE by default: measured in round 4 (profiles/README.md), chunks on streams of their own do not
+// shorten the call -- band search and traceback are both bound by instruction issue, so running the traceback of one chunk
+// beside the band search of the next gains nothing (C4: 24.65 against 25.0 ms at the C ABI with four chunks), and chunks too
+// small to fill the chip lose (4096 x 100 kbp in three chunks: 135 against 120 ms).  PA_ALIGN_CHUNKS=n for experiments.
+static bool plan_chunks(CreateRun& cr) {
+    pa_batch* p = cr.p;
+    const size_t *a_len = cr.in.a_len, *b_len = cr.in.b_len, pairs = cr.in.pairs;
+    static const int env_chunks = getenv("PA_ALIGN_CHUNKS") ? atoi(getenv("PA_ALIGN_CHUNKS")) : 0;
+    // (Until the traceback started its expensive pairs first, four chunks paid for many SHORT pairs -- C4: 24.1 against 26.0 ms --
+    //  by cutting the traceback's tail; with the ordering one chunk is ahead there too: 22.3 against 22.9 ms.)
+    int C = 1;
+    if (env_chunks > 0) C = std::min<int>(env_chunks, pa_batch::kMaxChunks);
+    C = (int)std::max<size_t>(1, std::min<size_t>((size_t)C, pairs));
+    p->chunk_lo.assign((size_t)C + 1, 0);
+    p->chunk_base.assign((size_t)C + 1, 0);
+    for (int c = 0; c <= C; ++c) p->chunk_lo[(size_t)c] = pairs * (size_t)c / (size_t)C;
+    uint64_t acc = 0;
+    for (int c = 0; c < C; ++c) {
+        p->chunk_base[(size_t)c] = acc;
+        for (size_t q = p->chunk_lo[(size_t)c]; q < p->chunk_lo[(size_t)c + 1]; ++q) {
+            const size_t i = (size_t)p->order_host[q];
+            acc += a_len[i] + b_len[i] + 2;
         }
     }
-    if (getenv("PA_STRIP_WAVELOG") && !p->trace && !p->jobs.empty()) {
-        // diagnostics: every strip wavefront leaves {HW_ID, XCC_ID, start, end (100 MHz), chunks that had to poll} behind
-        if (!p->d_wavelog.alloc(p->jobs.size() * 32)) return nullptr;
-        for (size_t j = 0; j < p->jobs.size(); ++j) {
-            p->jobs[j].values = p->d_wavelog.as<uint32_t>() + 8 * j;
-            p->jobs[j].flags |= kJobLog;
+    p->chunk_base[(size_t)C] = acc;
+    p->torder_host = p->order_host;
+    for (int c = 0; c < C; ++c) std::sort(p->torder_host.begin() + (long)p->chunk_lo[(size_t)c], p->torder_host.begin() + (long)p->chunk_lo[(size_t)c + 1]);
+    if (!p->d_torder.alloc(std::max<size_t>(pairs, 1) * 4) || !p->d_tlist.alloc(std::max<size_t>(pairs, 1) * 4) ||
+        !hip_ok(hipMemcpy(p->d_torder.ptr, p->torder_host.data(), pairs * 4, hipMemcpyHostToDevice), "H2D trace order"))
+        return false;
+    for (size_t i = 0; i < pairs; ++i) p->max_nm = (uint32_t)std::max<size_t>(p->max_nm, std::min<size_t>(a_len[i] + b_len[i], 0x7FFFFFFFu));
+    p->h_meta = (uint8_t*)pinned_take(64 + pairs * 12 + 64, &p->h_meta_size);
+    if (!p->h_meta) return false;
+    if (!hip_ok(hipEventCreate(&p->ev_pre), "event")) return false;
+    for (int c = 0; c < C; ++c)
+        if (!(p->cstream[c] = stream_take()) || !hip_ok(hipEventCreate(&p->evF0[c]), "event") ||
+            !hip_ok(hipEventCreate(&p->evF1[c]), "event") || !hip_ok(hipEventCreate(&p->evT1[c]), "event"))
+            return false;
+    return true;
+}
+
+static bool upload_trace_jobs(CreateRun& cr, const std::vector<TraceJob>& tjobs, const std::vector<uint64_t>& src_off) {
+    pa_batch* p = cr.p;
+    const size_t pairs = cr.in.pairs;
+    return hip_ok(hipMemsetAsync(p->d_scratch_gran.ptr, 0, pairs * 16 * 8, p->stream), "memset trace granules") &&
+           hip_ok(hipMemcpyAsync(p->d_tjobs.ptr, tjobs.data(), pairs * sizeof(TraceJob), hipMemcpyHostToDevice, p->stream), "H2D trace jobs") &&
+           hip_ok(hipMemcpyAsync(p->d_cig_src_off.ptr, src_off.data(), pairs * 8, hipMemcpyHostToDevice, p->stream), "H2D offsets") &&
+           hip_ok(hipStreamSynchronize(p->stream), "sync");
+}
+
+// Chained batches beyond one wavefront per SIMD: a SIMD serves its OLDEST wavefront first, the younger ones get what is
+// left, and a chain advances at the pace of its most starved strip -- so pairs finish staggered by wave slot and the
+// tail of the launch runs on a mostly idle chip (PA_STRIP_WAVELOG shows it).  The top strip of every pair therefore
+// paces itself against the average progress of all pairs (strip_kernel.hpp kJobPace).
+// Both need every strip resident (at most four wavefronts per SIMD at <= 128 VGPRs); beyond that strips queue in ticket
+// order and only the priority rotation is kept.
+static void apply_pacing(pa_batch* p) {
+    if (p->sequential || p->trace || p->banded || p->jobs.empty()) return;
+    static const bool no_pace = getenv("PA_STRIP_NO_PACE") != nullptr;
+    static const bool no_rotate = getenv("PA_STRIP_NO_ROTATE") != nullptr;
+    const size_t simds = (size_t)device_cus() * 4;
+    int tops = 0;
+    for (const StripJob& j : p->jobs) tops += j.hin_gran == nullptr;
+    for (StripJob& j : p->jobs) {
+        if (p->jobs.size() > simds && !no_rotate) j.flags |= kJobRotatePrio;
+        if (!no_pace && p->jobs.size() > simds && p->jobs.size() <= 4 * simds && j.hin_gran == nullptr && tops > 1) {
+            j.flags |= kJobPace;
+            j.ckpt = p->d_misc.as<uint32_t>() + 4;  // the u64 progress counter (zeroed with the ticket before every pass)
+            j.ckpt_stride = tops;
         }
     }
-    cmark("jobs + descriptors");
-    if (slice_rows) {
+}
+
+// diagnostics (PA_STRIP_WAVELOG): every strip wavefront leaves {HW_ID, XCC_ID, start, end (100 MHz), chunks that had to poll} behind
+static bool attach_wavelog(pa_batch* p) {
+    if (!getenv("PA_STRIP_WAVELOG") || p->trace || p->jobs.empty()) return true;
+    if (!p->d_wavelog.alloc(p->jobs.size() * 32)) return false;
+    for (size_t j = 0; j < p->jobs.size(); ++j) {
+        p->jobs[j].values = p->d_wavelog.as<uint32_t>() + 8 * j;
+        p->jobs[j].flags |= kJobLog;
+    }
+    return true;
+}
+
+static pa_batch* batch_create(const BatchInput& in, bool trace, float band_hint = -1.f, int dt_max_g = 0, int dt_fr_drop = 0,
+                              const pa_astarpa2_params* astar = nullptr, int window_override = -1) {
+    if (!ensure_device()) return nullptr;
+    PhaseClock clock("pa_batch_create");  // diagnostics: where the creation time goes
+    auto p = std::make_unique<pa_batch>();
+    p->pairs = in.pairs;
+    p->trace = trace;
+    p->dt_max_g = dt_max_g;
+    p->dt_fr_drop = dt_fr_drop;
+    CreateRun cr{p.get(), in, astar};
+    choose_shape(cr, band_hint, window_override);
+    if (!layout_pairs(cr) || (trace && !alloc_trace_buffers(cr)) || !alloc_batch_buffers(cr)) return nullptr;
+    clock.mark("host layout + hipMalloc");
+    if (!(p->stream = bstream_take()) || !hip_ok(hipEventCreate(&p->ev0), "event") ||
+        !hip_ok(hipEventCreate(&p->ev1), "event") || !hip_ok(hipEventCreate(&p->ev2), "event"))
+        return nullptr;
+    clock.mark("stream + events");
+    if (!upload_sequences(cr)) return nullptr;
+    clock.mark("upload of the sequences");
+    std::vector<int32_t> first;
+    plan_strip_jobs(cr, first);
+    if (!upload_first_and_desc(cr, first)) return nullptr;
+    if (trace && in.pairs) {
+        std::vector<TraceJob> tjobs(in.pairs);
+        std::vector<uint64_t> src_off(in.pairs);
+        if (!make_trace_jobs(cr, tjobs, src_off) || !plan_chunks(cr) || !upload_trace_jobs(cr, tjobs, src_off)) return nullptr;
+    }
+    apply_pacing(p.get());
+    if (!attach_wavelog(p.get())) return nullptr;
+    clock.mark("jobs + descriptors");
+    if (cr.slice_rows) {
         p->sequential = false;
-        p->sliced = slice::create(p->n.data(), p->m.data(), pairs, p->code_off.data(), p->prof_off.data(), slice_rows);
+        p->sliced = slice::create(p->n.data(), p->m.data(), in.pairs, p->code_off.data(), p->prof_off.data(), cr.slice_rows);
         if (!p->sliced) return nullptr;
-        cmark("bit-sliced plan");
+        clock.mark("bit-sliced plan");
     }
     if (!p->d_jobs.alloc(p->jobs.size() * sizeof(StripJob))) return nullptr;
     if (!p->jobs.empty() &&
@@ -1201,7 +1323,7 @@ static pa_batch* batch_create(const uint8_t* const* a, const size_t* a_len, cons
 
 extern "C" pa_batch* pa_batch_create(const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b,
                                      const size_t* b_len, size_t pairs) {
-    return batch_create(a, a_len, b, b_len, pairs, false);
+    return batch_create({a, a_len, b, b_len, pairs}, false);
 }
 
 extern "C" pa_batch* pa_batch_create_banded(const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b,
@@ -1210,19 +1332,19 @@ extern "C" pa_batch* pa_batch_create_banded(const uint8_t* const* a, const size_
         set_error("pa_batch_create_banded: divergence_hint must be >= 0");
         return nullptr;
     }
-    return batch_create(a, a_len, b, b_len, pairs, false, divergence_hint);
+    return batch_create({a, a_len, b, b_len, pairs}, false, divergence_hint);
 }
 
 extern "C" pa_batch* pa_batch_create_trace(const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b,
                                            const size_t* b_len, size_t pairs) {
-    return batch_create(a, a_len, b, b_len, pairs, true);
+    return batch_create({a, a_len, b, b_len, pairs}, true);
 }
 
 // ... with the traceback options of `trace_params->front` (dt_trace, max_g, fr_drop): DT-trace through every block first, the
 // re-fill only where it gives up (blocks/trace.rs:51-125), e.g. the `simple` preset's { dt_trace: true, max_g: 40, fr_drop: 10 }.
 extern "C" pa_batch* pa_batch_create_trace_params(const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b,
                                                   const size_t* b_len, size_t pairs, const pa_astarpa2_params* trace_params) {
-    if (!trace_params) return batch_create(a, a_len, b, b_len, pairs, true);
+    if (!trace_params) return batch_create({a, a_len, b, b_len, pairs}, true);
     const engine::AstarPa2Params tp = engine::params_from_c(*trace_params);
     if (!tp.front.sparse || tp.block_width != 256) {
         set_error("pa_batch_create_trace_params: the batched traceback walks sparse 256-column blocks");
@@ -1232,7 +1354,7 @@ extern "C" pa_batch* pa_batch_create_trace_params(const uint8_t* const* a, const
         set_error("pa_batch_create_trace_params: max_g must be in 1..%d", kDtMaxG);
         return nullptr;
     }
-    return batch_create(a, a_len, b, b_len, pairs, true, -1.f, tp.front.dt_trace ? (int)tp.front.max_g : 0, tp.front.dt_trace ? (int)tp.front.fr_drop : 0);
+    return batch_create({a, a_len, b, b_len, pairs}, true, -1.f, tp.front.dt_trace ? (int)tp.front.max_g : 0, tp.front.dt_trace ? (int)tp.front.fr_drop : 0);
 }
 
 // 1 if pa_batch_create_params takes these parameters, 0 if they belong to pa_align (or are invalid).
@@ -1255,7 +1377,7 @@ extern "C" pa_batch* pa_batch_create_params(const uint8_t* const* a, const size_
                   "their relatives; use pa_align for other parameters");
         return nullptr;
     }
-    return batch_create(a, a_len, b, b_len, pairs, true, -1.f, ap.front.dt_trace ? (int)ap.front.max_g : 0, ap.front.dt_trace ? (int)ap.front.fr_drop : 0, params);
+    return batch_create({a, a_len, b, b_len, pairs}, true, -1.f, ap.front.dt_trace ? (int)ap.front.max_g : 0, ap.front.dt_trace ? (int)ap.front.fr_drop : 0, params);
 }
 
 // Profiles -> (granule clear) -> DP kernel, all queued on the batch's stream; ev0/ev1 bracket the DP kernel.
@@ -1553,10 +1675,8 @@ static int batch_align_small(pa_batch* p, int32_t* cost_out, char** cigar_out, f
     std::vector<std::string> texts(P);
     // one after another: two sweeps of long pairs at once get in each other's way (measured: 2 pairs 69 ms side by side, 29 ms in a row)
     for (size_t i = 0; i < P; ++i) {
-        std::vector<uint8_t> ba(p->n[i]), bb(p->m[i]);
-        if (!hip_ok(hipMemcpy(ba.data(), p->d_a.as<uint8_t>() + p->a_off[i], p->n[i], hipMemcpyDeviceToHost), "D2H a") ||
-            !hip_ok(hipMemcpy(bb.data(), p->d_b.as<uint8_t>() + p->b_off[i], p->m[i], hipMemcpyDeviceToHost), "D2H b"))
-            return PA_E_HIP;
+        std::vector<uint8_t> ba, bb;
+        if (!fetch_pair(p, i, ba, bb)) return PA_E_HIP;
         int32_t c = 0;
         int rc = align_hip(ba.data(), p->n[i], bb.data(), p->m[i], p->aparams_c, true, false, &c, &texts[i], &p->pair_stats[i]);
         if (rc == PA_E_TIMEOUT) rc = align_hip(ba.data(), p->n[i], bb.data(), p->m[i], p->aparams_c, true, false, &c, &texts[i], &p->pair_stats[i]);
@@ -1566,6 +1686,342 @@ static int batch_align_small(pa_batch* p, int32_t* cost_out, char** cigar_out, f
     if (const int rc = give_cstrings(texts, cigar_out)) return rc;
     if (forward_ms) *forward_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (trace_ms) *trace_ms = 0.f;  // (the engine's traceback is inside the figure above)
+    return 0;
+}
+
+// What the phases of one pa_batch_align call share.
+struct AlignRun {
+    pa_batch* p;
+    int32_t* cost_out;
+    char** cigar_out;
+    const size_t C;              // chunks
+    const bool cost_only_astar;  // batched A*PA2 without CIGARs asked for: no traceback, the costs come from the forward pass
+    unsigned long long* h_total;  // the pinned meta: text total per chunk, text length and offset per position
+    uint32_t* h_tlen;
+    uint64_t* h_dst;
+    std::vector<uint32_t> lens;  // per pair: CIGAR elements, or kTraceFailed
+    std::vector<int32_t> costs;
+    std::vector<apa2::PairResult> results;  // (A*PA2)
+    std::vector<size_t> handed_back;  // pairs the traceback handed back (a state the reference would panic on): the host engine redoes them
+    PhaseClock clock{"pa_batch_align"};
+    CigarGuard guard;
+    AlignRun(pa_batch* p_, int32_t* cost_out_, char** cigar_out_)
+        : p(p_), cost_out(cost_out_), cigar_out(cigar_out_), C(p_->chunk_lo.empty() ? 0 : p_->chunk_lo.size() - 1), cost_only_astar(p_->astar && !cigar_out_),
+          h_total((unsigned long long*)p_->h_meta), h_tlen((uint32_t*)(p_->h_meta + 64)), h_dst((uint64_t*)(p_->h_meta + 64 + ((p_->pairs * 4 + 7) & ~size_t(7)))),
+          guard(p_, cigar_out_) {}
+};
+
+// ---- per chunk, on its own stream: [band search] -> traceback -> CIGAR text into the chunk's packed region -> its lengths to the host ----
+static int launch_chunks(AlignRun& r) {
+    pa_batch* p = r.p;
+    unsigned long long* d_total = p->d_cmeta.as<unsigned long long>();
+    uint32_t* d_ticket = p->d_cmeta.as<uint32_t>() + 2 * pa_batch::kMaxChunks;
+    if (!hip_ok(hipMemsetAsync(p->d_cmeta.ptr, 0, 256, p->stream), "memset chunk meta") || !hip_ok(hipEventRecord(p->ev_pre, p->stream), "event")) return PA_E_HIP;
+    for (size_t c = 0; c < r.C; ++c) {
+        hipStream_t s = p->cstream[c];
+        const size_t lo = p->chunk_lo[c], cnt = p->chunk_lo[c + 1] - lo;
+        if (!hip_ok(hipStreamWaitEvent(s, p->ev_pre, 0), "wait") || !hip_ok(hipEventRecord(p->evF0[c], s), "event")) return PA_E_HIP;
+        if (p->astar)
+            if (const int rc = launch_astar(p, s, lo, cnt, d_ticket + c, nullptr)) return rc;
+        if (!hip_ok(hipEventRecord(p->evF1[c], s), "event")) return PA_E_HIP;
+        if (cnt && !r.cost_only_astar) {
+            static const int tbw = [] { const char* e = getenv("PA_TRACE_BLOCK_WAVES"); const int v = e ? atoi(e) : kStripBlockWaves; return v >= 1 && v <= kStripBlockWaves ? v : kStripBlockWaves; }();
+            const dim3 tg((unsigned)((cnt + tbw - 1) / tbw)), tb(64 * tbw);
+            const TraceJob* tjp = p->d_tjobs.as<TraceJob>();
+            const int32_t* list = p->d_torder.as<int32_t>() + lo;
+            uint32_t* terr = p->d_misc.as<uint32_t>() + 1;
+            // the traceback starts its most expensive pairs first (PA_TRACE_ORDER=0: index order, for comparison)
+            static const bool by_cost = [] { const char* e = getenv("PA_TRACE_ORDER"); return !(e && atoi(e) == 0); }();
+            const int32_t* tlist = list;
+            if (by_cost && cnt > (size_t)tbw) {
+                hipLaunchKernelGGL(trace_order_kernel, dim3(1), dim3(1024), 0, s, tjp, list, (int)cnt, p->d_tlist.as<int32_t>() + lo, p->max_nm);
+                if (!hip_ok(hipGetLastError(), "trace_order_kernel launch")) return PA_E_HIP;
+                tlist = p->d_tlist.as<int32_t>() + lo;
+            }
+            launch_trace(p->dt_max_g > 0, p->astar, tg, tb, s, tjp, tlist, (int)cnt, terr);
+            if (!hip_ok(hipGetLastError(), "trace_kernel launch") || !hip_ok(hipEventRecord(p->evT1[c], s), "event")) return PA_E_HIP;
+            hipLaunchKernelGGL(format_pack_kernel, dim3((unsigned)cnt), dim3(64), 0, s, p->d_cigar.as<uint32_t>(), p->d_cig_src_off.as<uint64_t>(), p->d_cigar_len.as<uint32_t>(),
+                               list, p->d_packed.as<uint8_t>() + p->chunk_base[c], d_total + c, p->d_tlen_pos.as<uint32_t>() + lo, p->d_dst_pos.as<uint64_t>() + lo);
+            if (!hip_ok(hipGetLastError(), "format_pack_kernel") ||
+                !hip_ok(hipMemcpyAsync(r.h_total + c, d_total + c, 8, hipMemcpyDeviceToHost, s), "D2H total") ||
+                !hip_ok(hipMemcpyAsync(r.h_tlen + lo, p->d_tlen_pos.as<uint32_t>() + lo, cnt * 4, hipMemcpyDeviceToHost, s), "D2H text lens") ||
+                !hip_ok(hipMemcpyAsync(r.h_dst + lo, p->d_dst_pos.as<uint64_t>() + lo, cnt * 8, hipMemcpyDeviceToHost, s), "D2H text offsets"))
+                return PA_E_HIP;
+        } else if (!hip_ok(hipEventRecord(p->evT1[c], s), "event")) {
+            return PA_E_HIP;
+        }
+    }
+    return 0;
+}
+
+// ---- per chunk, as it completes: its packed text to the host, strings to the caller (the later chunks are still on the GPU) ----
+static int collect_chunk_text(AlignRun& r) {
+    pa_batch* p = r.p;
+    char** const cigar_out = r.cigar_out;
+    const uint32_t* const h_tlen = r.h_tlen;
+    const uint64_t* const h_dst = r.h_dst;
+    for (size_t c = 0; c < r.C; ++c) {
+        hipStream_t s = p->cstream[c];
+        const size_t lo = p->chunk_lo[c], cnt = p->chunk_lo[c + 1] - lo;
+        if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
+        if (!cnt || r.cost_only_astar || !cigar_out) continue;
+        const uint64_t total = r.h_total[c];
+        if (total > p->h_text_size) {  // pinned, so the copy runs at link speed; from the process-wide pool
+            pinned_give(p->h_text, p->h_text_size);
+            p->h_text = (uint8_t*)pinned_take(total + total / 4 + 4096, &p->h_text_size);
+            if (!p->h_text) {
+                p->h_text_size = 0;
+                return PA_E_HIP;
+            }
+        }
+        if (total && (!hip_ok(hipMemcpyAsync(p->h_text, p->d_packed.as<uint8_t>() + p->chunk_base[c], total, hipMemcpyDeviceToHost, s), "D2H cigars") ||
+                      !hip_ok(hipStreamSynchronize(s), "sync")))
+            return PA_E_HIP;
+        // strings to the caller: one malloc + one copy per pair; for tens of megabytes of text (4096 x 100 kbp: 70 MB) on several threads
+        const bool view = p->view_mode && r.C == 1;  // pa_batch_align_view: the text stays where the copy from the GPU put it
+        std::atomic<bool> oom{false};
+        auto make = [&](size_t q) {
+            const size_t i = (size_t)p->torder_host[q];
+            if (h_tlen[q] == kTextFailed) return;
+            if (view) {
+                cigar_out[i] = (char*)(p->h_text + h_dst[q]);
+                p->view_len[i] = h_tlen[q];
+                return;
+            }
+            char* out = (char*)std::malloc((size_t)h_tlen[q] + 1);
+            if (!out) {
+                oom = true;
+                return;
+            }
+            if (h_tlen[q]) std::memcpy(out, p->h_text + h_dst[q], h_tlen[q]);
+            out[h_tlen[q]] = 0;
+            cigar_out[i] = out;
+        };
+        if (total >= (size_t(8) << 20) && cnt >= 64 && host_threads() > 1 && !view) {  // (a view copies nothing)
+            const unsigned nt = std::min<unsigned>(host_threads(), 8);
+            std::vector<std::thread> th;
+            for (unsigned t = 0; t < nt; ++t)
+                th.emplace_back([&, t] {
+                    for (size_t q = lo + t; q < lo + cnt; q += nt) make(q);
+                });
+            for (auto& t : th) t.join();
+        } else {
+            for (size_t q = lo; q < lo + cnt; ++q) make(q);
+        }
+        if (oom) {
+            set_error("out of memory");
+            return PA_E_NOMEM;
+        }
+        for (size_t q = lo; q < lo + cnt; ++q)
+            if (h_tlen[q] == kTextFailed) r.handed_back.push_back((size_t)p->torder_host[q]);
+    }
+    return 0;
+}
+
+// ---- the small per-pair arrays, once ----
+static int read_pair_arrays(AlignRun& r) {
+    pa_batch* p = r.p;
+    const size_t P = p->pairs;
+    r.lens.assign(P, 0);
+    r.costs.assign(P, 0);
+    uint32_t misc[4] = {0, 0, 0, 0};
+    if (P && !r.cost_only_astar &&
+        (!hip_ok(hipMemcpy(r.lens.data(), p->d_cigar_len.ptr, P * 4, hipMemcpyDeviceToHost), "D2H lens") ||
+         !hip_ok(hipMemcpy(r.costs.data(), p->d_costs.ptr, P * 4, hipMemcpyDeviceToHost), "D2H costs")))
+        return PA_E_HIP;
+    if (!hip_ok(hipMemcpy(misc, p->d_misc.ptr, 16, hipMemcpyDeviceToHost), "D2H")) return PA_E_HIP;
+    if (misc[3]) {
+        set_error("sequence contains a base outside ACGT");
+        return PA_E_INVALID_BASE;
+    }
+    if (misc[1] != PA_ERR_NONE) {
+        set_error("device spin timeout (err=%u)", misc[1]);
+        return PA_E_TIMEOUT;
+    }
+    p->gran_dirty = false;
+    return 0;
+}
+
+// kernel times.  With several chunks the kernels of different chunks run side by side: the figures are the SPANS from the first start to
+// the last end of each phase (equal to the kernel times when there is one chunk), and the two spans overlap.
+static int kernel_spans(AlignRun& r, float* forward_ms, float* trace_ms) {
+    pa_batch* p = r.p;
+    auto span = [&](hipEvent_t* from, hipEvent_t* to, float* out) -> bool {
+        float best = 0.f;
+        for (size_t c0 = 0; c0 < r.C; ++c0)
+            for (size_t c1 = 0; c1 < r.C; ++c1) {
+                float ms = 0.f;
+                if (!hip_ok(hipEventElapsedTime(&ms, from[c0], to[c1]), "elapsed")) return false;
+                if (ms > best) best = ms;
+            }
+        *out = best;
+        return true;
+    };
+    if (forward_ms) {
+        *forward_ms = 0.f;
+        if (p->astar) {
+            if (!span(p->evF0, p->evF1, forward_ms)) return PA_E_HIP;
+        } else if (!p->jobs.empty() && !hip_ok(hipEventElapsedTime(forward_ms, p->ev0, p->ev1), "elapsed")) {
+            return PA_E_HIP;
+        }
+    }
+    if (trace_ms) {
+        *trace_ms = 0.f;
+        if (!span(p->evF1, p->evT1, trace_ms)) return PA_E_HIP;
+    }
+    return 0;
+}
+
+// A*PA2: per-pair statistics (domain.rs:31-43) of the band search and the traceback
+static int astar_pair_stats(AlignRun& r) {
+    pa_batch* p = r.p;
+    const size_t P = p->pairs;
+    r.results.resize(P);
+    std::vector<uint32_t> ts(P * 8, 0);
+    if (P && (!hip_ok(hipMemcpy(r.results.data(), p->d_results.ptr, P * sizeof(apa2::PairResult), hipMemcpyDeviceToHost), "D2H results") ||
+              !hip_ok(hipMemcpy(ts.data(), p->d_tstats.ptr, P * 32, hipMemcpyDeviceToHost), "D2H trace stats")))
+        return PA_E_HIP;
+    if (align_profile() && !p->astar_full && P) {  // diagnostics: the spread of the pairs' band-search times (what ends the launch: the work, or a few chains?)
+        std::vector<double> ms;
+        for (const apa2::PairResult& res : r.results)
+            if (res.pad0) ms.push_back((double)res.pad0 / 1e5);
+        std::sort(ms.begin(), ms.end());
+        auto q = [&](double f) { return ms.empty() ? 0.0 : ms[(size_t)(f * (double)(ms.size() - 1))]; };
+        double sum = 0;
+        for (double x : ms) sum += x;
+        std::fprintf(stderr, "[pa_batch_align] per-pair band search ms: min %.2f  median %.2f  p90 %.2f  p99 %.2f  p99.9 %.2f  max %.2f  sum %.1f  (%zu pairs)\n", q(0), q(0.5), q(0.9),
+                     q(0.99), q(0.999), q(1.0), sum, ms.size());
+    }
+    p->pair_stats.assign(P, pa_astarpa2_stats{});
+    p->apa2_strip_instr = 0;
+    for (size_t i = 0; i < P; ++i) {
+        pa_astarpa2_stats& st = p->pair_stats[i];
+        const apa2::PairResult& res = r.results[i];
+        if (p->sp.doubling == apa2::kDoublingBand) {  // (the reference reports block counters after a band doubling only, lib.rs:158)
+            st.num_blocks = res.num_blocks;
+            st.num_incremental_blocks = res.num_incremental_blocks;
+            st.computed_lanes = res.computed_lanes;
+            st.unique_lanes = res.unique_lanes;
+        }
+        st.f_max_tries = res.f_max_tries;
+        st.sanity_violations = res.sanity_violations;
+        p->apa2_strip_instr += (double)res.strip_instr;
+        if (r.cost_only_astar) {  // no traceback ran: the cost is the forward pass's, a pair it handed back goes to the host engine
+            r.costs[i] = res.cost;
+            r.lens[i] = res.status != apa2::kOk ? kTraceFailed : 0u;
+            if (res.status != apa2::kOk) r.handed_back.push_back(i);
+            continue;
+        }
+        st.dt_trace_tries = ts[8 * i + 0];
+        st.dt_trace_success = ts[8 * i + 1];
+        st.dt_trace_fallback = ts[8 * i + 2];
+        st.fill_tries = ts[8 * i + 3];
+        st.fill_success = ts[8 * i + 4];
+        st.fill_fallback = ts[8 * i + 5];
+    }
+    return 0;
+}
+
+// ---- second round (A*PA2): pairs whose band left their window of the column store, again with full-height slots ----
+static int window_second_round(AlignRun& r) {
+    pa_batch* p = r.p;
+    std::vector<size_t> redo;
+    for (size_t i = 0; i < p->pairs; ++i)
+        if (r.results[i].status == apa2::kErrWindow) redo.push_back(i);
+    // The second round's memory is bounded: the pairs go in sub-batches whose full-height stores stay below ~24 GB each (one pair
+    // alone may exceed it: 9.8 MB per 100 kbp pair, 1 GB per 1 Mbp pair), one sub-batch at a time; pa_batch_window_retry_bytes reports
+    // the largest.  PA_WINDOW_RETRY_BYTES overrides the bound (tests).
+    double retry_cap = 24e9;
+    if (const char* e = getenv("PA_WINDOW_RETRY_BYTES")) retry_cap = std::max(1.0, atof(e));
+    for (size_t r0 = 0; r0 < redo.size();) {
+        size_t r1 = r0;
+        double bytes = 0;
+        while (r1 < redo.size()) {
+            const size_t i = redo[r1];
+            const double need = ((double)p->n[i] / 256.0 + 2.0) * (double)((p->m[i] + 63) / 64) * 16.0;
+            if (r1 > r0 && bytes + need > retry_cap) break;
+            bytes += need;
+            r1 += 1;
+        }
+        p->window_retry_peak_bytes = std::max(p->window_retry_peak_bytes, bytes);
+        const size_t R = r1 - r0;
+        std::vector<std::vector<uint8_t>> ra(R), rb(R);
+        std::vector<const uint8_t*> ap(R), bp(R);
+        std::vector<size_t> al(R), bl(R);
+        for (size_t q = 0; q < R; ++q) {
+            const size_t i = redo[r0 + q];
+            if (!fetch_pair(p, i, ra[q], rb[q])) return PA_E_HIP;
+            ap[q] = ra[q].data();
+            bp[q] = rb[q].data();
+            al[q] = p->n[i];
+            bl[q] = p->m[i];
+        }
+        std::unique_ptr<pa_batch> sub(batch_create({ap.data(), al.data(), bp.data(), bl.data(), R}, true, -1.f, p->dt_max_g, p->dt_fr_drop, &p->aparams_c, 0));
+        if (!sub) return PA_E_HIP;
+        std::vector<int32_t> c2(R, 0);
+        std::vector<char*> g2(R, nullptr);
+        const int rc2 = pa_batch_align(sub.get(), c2.data(), r.cigar_out ? g2.data() : nullptr, nullptr, nullptr);
+        if (rc2 != 0) return rc2;  // (pa_batch_align hands out no strings when it fails)
+        for (size_t q = 0; q < R; ++q) {
+            const size_t i = redo[r0 + q];
+            r.costs[i] = c2[q];
+            r.lens[i] = 0;
+            r.results[i].status = apa2::kOk;
+            if (q < sub->pair_stats.size()) p->pair_stats[i] = sub->pair_stats[q];
+            if (r.cigar_out) {
+                r.guard.release(i);
+                r.cigar_out[i] = g2[q];
+            }
+        }
+        p->trace_fallbacks += sub->trace_fallbacks;
+        p->window_retries += R;
+        r0 = r1;
+    }
+    if (!redo.empty()) {  // (they are not the host engine's)
+        std::vector<size_t> keep;
+        for (const size_t i : r.handed_back)
+            if (r.results[i].status != apa2::kOk || r.lens[i] == kTraceFailed) keep.push_back(i);
+        r.handed_back.swap(keep);
+    }
+    return 0;
+}
+
+// a state the reference would panic on (or one the kernels leave alone): the host engine redoes the pairs that were handed back
+static int redo_handed_back(AlignRun& r) {
+    pa_batch* p = r.p;
+    pa_astarpa2_params fallback = p->astar ? p->aparams_c : traced_batch_params();
+    if (!p->astar && p->dt_max_g > 0) {
+        fallback.front.dt_trace = 1;
+        fallback.front.max_g = p->dt_max_g;
+        fallback.front.fr_drop = p->dt_fr_drop;
+    }
+    for (const size_t i : r.handed_back) {
+        std::string text;
+        p->trace_fallbacks += 1;
+        std::vector<uint8_t> ba, bb;
+        if (!fetch_pair(p, i, ba, bb)) return PA_E_HIP;
+        int32_t c = 0;
+        pa_astarpa2_stats fst{};
+        const int rc = align_hip(ba.data(), p->n[i], bb.data(), p->m[i], fallback, !r.cost_only_astar, false, &c, &text, &fst);
+        if (rc != 0) return rc;
+        if (p->astar) {
+            p->pair_stats[i] = fst;
+            if (r.results[i].status != apa2::kOk) r.costs[i] = c;  // the forward pass itself handed the pair back
+            r.cost_out[i] = c;
+        }
+        if (c != r.costs[i]) {
+            set_error("traceback fallback disagrees with the batched cost (pair %zu: %d vs %d)", i, c, r.costs[i]);
+            return PA_E_INTERNAL;
+        }
+        if (!r.cigar_out) continue;
+        r.guard.release(i);
+        r.cigar_out[i] = (char*)std::malloc(text.size() + 1);
+        if (!r.cigar_out[i]) {
+            set_error("out of memory");
+            return PA_E_NOMEM;
+        }
+        std::memcpy(r.cigar_out[i], text.c_str(), text.size() + 1);
+    }
     return 0;
 }
 
@@ -1581,334 +2037,32 @@ extern "C" int pa_batch_align(pa_batch* p, int32_t* cost_out, char** cigar_out, 
         if (trace_ms) *trace_ms = 0.f;
         return 0;
     }
-    static const bool prof = getenv("PA_ALIGN_PROFILE") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-    double t_mark = t_begin;
-    auto mark = [&](const char* what) {
-        if (!prof) return;
-        const double t = now();
-        std::fprintf(stderr, "[pa_batch_align] %-28s %8.3f ms\n", what, t - t_mark);
-        t_mark = t;
-    };
-    if (cigar_out)
-        for (size_t i = 0; i < P; ++i) cigar_out[i] = nullptr;
-    // a failure after the first string has been handed out: free them all again, the caller owns outputs only on success
-    auto fail_all = [&](int code) {
-        if (cigar_out)
-            for (size_t k = 0; k < P; ++k) {
-                if (!(p->view_mode && p->in_text(cigar_out[k]))) std::free(cigar_out[k]);
-                cigar_out[k] = nullptr;
-            }
-        return code;
-    };
+    AlignRun r(p, cost_out, cigar_out);  // (nulls cigar_out; a failing return below frees what has been handed out by then)
     // ---- everything before the chunks, on the batch's stream: profiles, clears, (full DP) the checkpointing forward pass ----
-    const bool cost_only_astar = p->astar && !cigar_out;  // batched A*PA2 without CIGARs asked for: no traceback, the costs come from the forward pass
     if (const int rc = batch_forward(p, !p->astar)) return rc;
-    const size_t C = p->chunk_lo.empty() ? 0 : p->chunk_lo.size() - 1;
-    unsigned long long* d_total = p->d_cmeta.as<unsigned long long>();
-    uint32_t* d_ticket = p->d_cmeta.as<uint32_t>() + 2 * pa_batch::kMaxChunks;
-    unsigned long long* h_total = (unsigned long long*)p->h_meta;
-    uint32_t* h_tlen = (uint32_t*)(p->h_meta + 64);
-    uint64_t* h_dst = (uint64_t*)(p->h_meta + 64 + ((P * 4 + 7) & ~size_t(7)));
-    if (!hip_ok(hipMemsetAsync(p->d_cmeta.ptr, 0, 256, p->stream), "memset chunk meta") || !hip_ok(hipEventRecord(p->ev_pre, p->stream), "event")) return PA_E_HIP;
-    // ---- per chunk, on its own stream: [band search] -> traceback -> CIGAR text into the chunk's packed region -> its lengths to the host ----
-    for (size_t c = 0; c < C; ++c) {
-        hipStream_t s = p->cstream[c];
-        const size_t lo = p->chunk_lo[c], cnt = p->chunk_lo[c + 1] - lo;
-        if (!hip_ok(hipStreamWaitEvent(s, p->ev_pre, 0), "wait") || !hip_ok(hipEventRecord(p->evF0[c], s), "event")) return PA_E_HIP;
-        if (p->astar)
-            if (const int rc = launch_astar(p, s, lo, cnt, d_ticket + c, nullptr)) return rc;
-        if (!hip_ok(hipEventRecord(p->evF1[c], s), "event")) return PA_E_HIP;
-        if (cnt && !cost_only_astar) {
-            static const int tbw = [] { const char* e = getenv("PA_TRACE_BLOCK_WAVES"); const int v = e ? atoi(e) : kStripBlockWaves; return v >= 1 && v <= kStripBlockWaves ? v : kStripBlockWaves; }();
-            const dim3 tg((unsigned)((cnt + tbw - 1) / tbw)), tb(64 * tbw);
-            const TraceJob* tjp = p->d_tjobs.as<TraceJob>();
-            const int32_t* list = p->d_torder.as<int32_t>() + lo;
-            uint32_t* terr = p->d_misc.as<uint32_t>() + 1;
-            // the traceback starts its most expensive pairs first (PA_TRACE_ORDER=0: index order, for comparison)
-            static const bool by_cost = [] { const char* e = getenv("PA_TRACE_ORDER"); return !(e && atoi(e) == 0); }();
-            const int32_t* tlist = list;
-            if (by_cost && cnt > (size_t)tbw) {
-                hipLaunchKernelGGL(trace_order_kernel, dim3(1), dim3(1024), 0, s, tjp, list, (int)cnt, p->d_tlist.as<int32_t>() + lo, p->max_nm);
-                if (!hip_ok(hipGetLastError(), "trace_order_kernel launch")) return PA_E_HIP;
-                tlist = p->d_tlist.as<int32_t>() + lo;
-            }
-            if (p->dt_max_g > 0 && p->astar) hipLaunchKernelGGL((trace_kernel<true, true>), tg, tb, tbw * sizeof(DtLds), s, tjp, tlist, (int)cnt, terr);
-            else if (p->dt_max_g > 0) hipLaunchKernelGGL((trace_kernel<true, false>), tg, tb, tbw * sizeof(DtLds), s, tjp, tlist, (int)cnt, terr);
-            else if (p->astar) hipLaunchKernelGGL((trace_kernel<false, true>), tg, tb, 0, s, tjp, tlist, (int)cnt, terr);
-            else hipLaunchKernelGGL((trace_kernel<false, false>), tg, tb, 0, s, tjp, tlist, (int)cnt, terr);
-            if (!hip_ok(hipGetLastError(), "trace_kernel launch") || !hip_ok(hipEventRecord(p->evT1[c], s), "event")) return PA_E_HIP;
-            hipLaunchKernelGGL(format_pack_kernel, dim3((unsigned)cnt), dim3(64), 0, s, p->d_cigar.as<uint32_t>(), p->d_cig_src_off.as<uint64_t>(), p->d_cigar_len.as<uint32_t>(),
-                               list, p->d_packed.as<uint8_t>() + p->chunk_base[c], d_total + c, p->d_tlen_pos.as<uint32_t>() + lo, p->d_dst_pos.as<uint64_t>() + lo);
-            if (!hip_ok(hipGetLastError(), "format_pack_kernel") ||
-                !hip_ok(hipMemcpyAsync(h_total + c, d_total + c, 8, hipMemcpyDeviceToHost, s), "D2H total") ||
-                !hip_ok(hipMemcpyAsync(h_tlen + lo, p->d_tlen_pos.as<uint32_t>() + lo, cnt * 4, hipMemcpyDeviceToHost, s), "D2H text lens") ||
-                !hip_ok(hipMemcpyAsync(h_dst + lo, p->d_dst_pos.as<uint64_t>() + lo, cnt * 8, hipMemcpyDeviceToHost, s), "D2H text offsets"))
-                return PA_E_HIP;
-        } else if (!hip_ok(hipEventRecord(p->evT1[c], s), "event")) {
-            return PA_E_HIP;
-        }
-    }
-    mark("launches");
-    // ---- per chunk, as it completes: its packed text to the host, strings to the caller (the later chunks are still on the GPU) ----
-    std::vector<size_t> handed_back;  // pairs the traceback handed back (a state the reference would panic on): the host engine redoes them
-    for (size_t c = 0; c < C; ++c) {
-        hipStream_t s = p->cstream[c];
-        const size_t lo = p->chunk_lo[c], cnt = p->chunk_lo[c + 1] - lo;
-        if (!hip_ok(hipStreamSynchronize(s), "sync")) return fail_all(PA_E_HIP);
-        if (!cnt || cost_only_astar || !cigar_out) continue;
-        const uint64_t total = h_total[c];
-        if (total > p->h_text_size) {  // pinned, so the copy runs at link speed; from the process-wide pool
-            pinned_give(p->h_text, p->h_text_size);
-            p->h_text = (uint8_t*)pinned_take(total + total / 4 + 4096, &p->h_text_size);
-            if (!p->h_text) {
-                p->h_text_size = 0;
-                return fail_all(PA_E_HIP);
-            }
-        }
-        if (total && (!hip_ok(hipMemcpyAsync(p->h_text, p->d_packed.as<uint8_t>() + p->chunk_base[c], total, hipMemcpyDeviceToHost, s), "D2H cigars") ||
-                      !hip_ok(hipStreamSynchronize(s), "sync")))
-            return fail_all(PA_E_HIP);
-        // strings to the caller: one malloc + one copy per pair; for tens of megabytes of text (4096 x 100 kbp: 70 MB) on several threads
-        std::atomic<bool> oom{false};
-        auto make = [&](size_t q) {
-            const size_t i = (size_t)p->torder_host[q];
-            if (h_tlen[q] == kTextFailed) return;
-            if (p->view_mode && C == 1) {  // pa_batch_align_view: the text stays where the copy from the GPU put it
-                cigar_out[i] = (char*)(p->h_text + h_dst[q]);
-                p->view_len[i] = h_tlen[q];
-                return;
-            }
-            char* out = (char*)std::malloc((size_t)h_tlen[q] + 1);
-            if (!out) {
-                oom = true;
-                return;
-            }
-            if (h_tlen[q]) std::memcpy(out, p->h_text + h_dst[q], h_tlen[q]);
-            out[h_tlen[q]] = 0;
-            cigar_out[i] = out;
-        };
-        if (total >= (size_t(8) << 20) && cnt >= 64 && host_threads() > 1 && !(p->view_mode && C == 1)) {  // (a view copies nothing)
-            const unsigned nt = std::min<unsigned>(host_threads(), 8);
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < nt; ++t)
-                th.emplace_back([&, t] {
-                    for (size_t q = lo + t; q < lo + cnt; q += nt) make(q);
-                });
-            for (auto& t : th) t.join();
-        } else {
-            for (size_t q = lo; q < lo + cnt; ++q) make(q);
-        }
-        if (oom) {
-            set_error("out of memory");
-            return fail_all(PA_E_NOMEM);
-        }
-        for (size_t q = lo; q < lo + cnt; ++q)
-            if (h_tlen[q] == kTextFailed) handed_back.push_back((size_t)p->torder_host[q]);
-    }
-    mark("chunks: text D2H + strings");
-    // ---- the small per-pair arrays, once ----
-    std::vector<uint32_t> lens(P, 0);
-    std::vector<int32_t> costs(P, 0);
-    uint32_t misc[4] = {0, 0, 0, 0};
-    if (P && !cost_only_astar &&
-        (!hip_ok(hipMemcpy(lens.data(), p->d_cigar_len.ptr, P * 4, hipMemcpyDeviceToHost), "D2H lens") ||
-         !hip_ok(hipMemcpy(costs.data(), p->d_costs.ptr, P * 4, hipMemcpyDeviceToHost), "D2H costs")))
-        return fail_all(PA_E_HIP);
-    if (!hip_ok(hipMemcpy(misc, p->d_misc.ptr, 16, hipMemcpyDeviceToHost), "D2H")) return fail_all(PA_E_HIP);
-    if (misc[3]) {
-        set_error("sequence contains a base outside ACGT");
-        return fail_all(PA_E_INVALID_BASE);
-    }
-    if (misc[1] != PA_ERR_NONE) {
-        set_error("device spin timeout (err=%u)", misc[1]);
-        return fail_all(PA_E_TIMEOUT);
-    }
-    p->gran_dirty = false;
-    // kernel times.  With several chunks the kernels of different chunks run side by side: the figures are the SPANS from the first start to
-    // the last end of each phase (equal to the kernel times when there is one chunk), and the two spans overlap.
-    auto span = [&](hipEvent_t* from, hipEvent_t* to, float* out) -> bool {
-        float best = 0.f;
-        for (size_t c0 = 0; c0 < C; ++c0)
-            for (size_t c1 = 0; c1 < C; ++c1) {
-                float ms = 0.f;
-                if (!hip_ok(hipEventElapsedTime(&ms, from[c0], to[c1]), "elapsed")) return false;
-                if (ms > best) best = ms;
-            }
-        *out = best;
-        return true;
-    };
-    if (forward_ms) {
-        *forward_ms = 0.f;
-        if (p->astar) {
-            if (!span(p->evF0, p->evF1, forward_ms)) return fail_all(PA_E_HIP);
-        } else if (!p->jobs.empty() && !hip_ok(hipEventElapsedTime(forward_ms, p->ev0, p->ev1), "elapsed")) {
-            return fail_all(PA_E_HIP);
-        }
-    }
-    if (trace_ms) {
-        *trace_ms = 0.f;
-        if (!span(p->evF1, p->evT1, trace_ms)) return fail_all(PA_E_HIP);
-    }
-    std::vector<apa2::PairResult> results;
-    if (p->astar) {  // per-pair statistics (domain.rs:31-43) of the band search and the traceback
-        results.resize(P);
-        std::vector<uint32_t> ts(P * 8, 0);
-        if (P && (!hip_ok(hipMemcpy(results.data(), p->d_results.ptr, P * sizeof(apa2::PairResult), hipMemcpyDeviceToHost), "D2H results") ||
-                  !hip_ok(hipMemcpy(ts.data(), p->d_tstats.ptr, P * 32, hipMemcpyDeviceToHost), "D2H trace stats")))
-            return fail_all(PA_E_HIP);
-        if (prof && !p->astar_full && P) {  // diagnostics: the spread of the pairs' band-search times (what ends the launch: the work, or a few chains?)
-            std::vector<double> ms;
-            for (const apa2::PairResult& r : results)
-                if (r.pad0) ms.push_back((double)r.pad0 / 1e5);
-            std::sort(ms.begin(), ms.end());
-            auto q = [&](double f) { return ms.empty() ? 0.0 : ms[(size_t)(f * (double)(ms.size() - 1))]; };
-            double sum = 0;
-            for (double x : ms) sum += x;
-            std::fprintf(stderr, "[pa_batch_align] per-pair band search ms: min %.2f  median %.2f  p90 %.2f  p99 %.2f  p99.9 %.2f  max %.2f  sum %.1f  (%zu pairs)\n", q(0), q(0.5), q(0.9),
-                         q(0.99), q(0.999), q(1.0), sum, ms.size());
-        }
-        p->pair_stats.assign(P, pa_astarpa2_stats{});
-        p->apa2_strip_instr = 0;
-        for (size_t i = 0; i < P; ++i) {
-            pa_astarpa2_stats& st = p->pair_stats[i];
-            const apa2::PairResult& r = results[i];
-            if (p->sp.doubling == apa2::kDoublingBand) {  // (the reference reports block counters after a band doubling only, lib.rs:158)
-                st.num_blocks = r.num_blocks;
-                st.num_incremental_blocks = r.num_incremental_blocks;
-                st.computed_lanes = r.computed_lanes;
-                st.unique_lanes = r.unique_lanes;
-            }
-            st.f_max_tries = r.f_max_tries;
-            st.sanity_violations = r.sanity_violations;
-            p->apa2_strip_instr += (double)r.strip_instr;
-            if (cost_only_astar) {  // no traceback ran: the cost is the forward pass's, a pair it handed back goes to the host engine
-                costs[i] = r.cost;
-                lens[i] = r.status != apa2::kOk ? kTraceFailed : 0u;
-                if (r.status != apa2::kOk) handed_back.push_back(i);
-                continue;
-            }
-            st.dt_trace_tries = ts[8 * i + 0];
-            st.dt_trace_success = ts[8 * i + 1];
-            st.dt_trace_fallback = ts[8 * i + 2];
-            st.fill_tries = ts[8 * i + 3];
-            st.fill_success = ts[8 * i + 4];
-            st.fill_fallback = ts[8 * i + 5];
-        }
-    }
-    // ---- second round: pairs whose band left their window of the column store, again with full-height slots ----
+    if (const int rc = launch_chunks(r)) return rc;
+    r.clock.mark("launches");
+    if (const int rc = collect_chunk_text(r)) return rc;
+    r.clock.mark("chunks: text D2H + strings");
+    if (const int rc = read_pair_arrays(r)) return rc;
+    if (const int rc = kernel_spans(r, forward_ms, trace_ms)) return rc;
     if (p->astar) {
-        std::vector<size_t> redo;
+        if (const int rc = astar_pair_stats(r)) return rc;
+        if (const int rc = window_second_round(r)) return rc;
+    }
+    r.clock.mark("second round (windows)");
+    if (!cigar_out && !r.cost_only_astar)  // (costs alone of a traced full-DP batch: the pairs the traceback handed back are not redone)
+        r.handed_back.clear();
+    if (cigar_out && !r.cost_only_astar) {  // (without cigar_out the loop over the chunks above did not look at the lengths)
+        r.handed_back.clear();
         for (size_t i = 0; i < P; ++i)
-            if (results[i].status == apa2::kErrWindow) redo.push_back(i);
-        // The second round's memory is bounded: the pairs go in sub-batches whose full-height stores stay below ~24 GB each (one pair
-        // alone may exceed it: 9.8 MB per 100 kbp pair, 1 GB per 1 Mbp pair), one sub-batch at a time; pa_batch_window_retry_bytes reports
-        // the largest.  PA_WINDOW_RETRY_BYTES overrides the bound (tests).
-        double retry_cap = 24e9;
-        if (const char* e = getenv("PA_WINDOW_RETRY_BYTES")) retry_cap = std::max(1.0, atof(e));
-        for (size_t r0 = 0; r0 < redo.size();) {
-            size_t r1 = r0;
-            double bytes = 0;
-            while (r1 < redo.size()) {
-                const size_t i = redo[r1];
-                const double need = ((double)p->n[i] / 256.0 + 2.0) * (double)((p->m[i] + 63) / 64) * 16.0;
-                if (r1 > r0 && bytes + need > retry_cap) break;
-                bytes += need;
-                r1 += 1;
-            }
-            p->window_retry_peak_bytes = std::max(p->window_retry_peak_bytes, bytes);
-            const size_t R = r1 - r0;
-            std::vector<std::vector<uint8_t>> ra(R), rb(R);
-            std::vector<const uint8_t*> ap(R), bp(R);
-            std::vector<size_t> al(R), bl(R);
-            for (size_t q = 0; q < R; ++q) {
-                const size_t i = redo[r0 + q];
-                ra[q].resize(p->n[i]);
-                rb[q].resize(p->m[i]);
-                if ((p->n[i] && !hip_ok(hipMemcpy(ra[q].data(), p->d_a.as<uint8_t>() + p->a_off[i], p->n[i], hipMemcpyDeviceToHost), "D2H a")) ||
-                    (p->m[i] && !hip_ok(hipMemcpy(rb[q].data(), p->d_b.as<uint8_t>() + p->b_off[i], p->m[i], hipMemcpyDeviceToHost), "D2H b")))
-                    return fail_all(PA_E_HIP);
-                ap[q] = ra[q].data();
-                bp[q] = rb[q].data();
-                al[q] = p->n[i];
-                bl[q] = p->m[i];
-            }
-            std::unique_ptr<pa_batch> sub(batch_create(ap.data(), al.data(), bp.data(), bl.data(), R, true, -1.f, p->dt_max_g, p->dt_fr_drop, &p->aparams_c, 0));
-            if (!sub) return fail_all(PA_E_HIP);
-            std::vector<int32_t> c2(R, 0);
-            std::vector<char*> g2(R, nullptr);
-            const int rc2 = pa_batch_align(sub.get(), c2.data(), cigar_out ? g2.data() : nullptr, nullptr, nullptr);
-            if (rc2 != 0) return fail_all(rc2);  // (pa_batch_align hands out no strings when it fails)
-            for (size_t q = 0; q < R; ++q) {
-                const size_t i = redo[r0 + q];
-                costs[i] = c2[q];
-                lens[i] = 0;
-                results[i].status = apa2::kOk;
-                if (q < sub->pair_stats.size()) p->pair_stats[i] = sub->pair_stats[q];
-                if (cigar_out) {
-                    if (!(p->view_mode && p->in_text(cigar_out[i]))) std::free(cigar_out[i]);
-                    cigar_out[i] = g2[q];
-                }
-            }
-            p->trace_fallbacks += sub->trace_fallbacks;
-            p->window_retries += R;
-            r0 = r1;
-        }
-        if (!redo.empty()) {  // (they are not the host engine's)
-            std::vector<size_t> keep;
-            for (const size_t i : handed_back)
-                if (results[i].status != apa2::kOk || lens[i] == kTraceFailed) keep.push_back(i);
-            handed_back.swap(keep);
-        }
+            if (r.lens[i] == kTraceFailed) r.handed_back.push_back(i);
     }
-    mark("second round (windows)");
-    if (!cigar_out && !cost_only_astar)  // (costs alone of a traced full-DP batch: the pairs the traceback handed back are not redone)
-        handed_back.clear();
-    if (cigar_out && !cost_only_astar) {  // (without cigar_out the loop over the chunks above did not look at the lengths)
-        handed_back.clear();
-        for (size_t i = 0; i < P; ++i)
-            if (lens[i] == kTraceFailed) handed_back.push_back(i);
-    }
-    for (size_t i = 0; i < P; ++i) cost_out[i] = costs[i];
-    mark("small arrays + statistics");
-    pa_astarpa2_params fallback = p->astar ? p->aparams_c : traced_batch_params();
-    if (!p->astar && p->dt_max_g > 0) {
-        fallback.front.dt_trace = 1;
-        fallback.front.max_g = p->dt_max_g;
-        fallback.front.fr_drop = p->dt_fr_drop;
-    }
-    for (const size_t i : handed_back) {
-        // a state the reference would panic on (or one the kernels leave alone): the host engine redoes this pair
-        std::string text;
-        p->trace_fallbacks += 1;
-        std::vector<uint8_t> ba(p->n[i]), bb(p->m[i]);
-        if ((p->n[i] && !hip_ok(hipMemcpy(ba.data(), p->d_a.as<uint8_t>() + p->a_off[i], p->n[i], hipMemcpyDeviceToHost), "D2H a")) ||
-            (p->m[i] && !hip_ok(hipMemcpy(bb.data(), p->d_b.as<uint8_t>() + p->b_off[i], p->m[i], hipMemcpyDeviceToHost), "D2H b")))
-            return fail_all(PA_E_HIP);
-        int32_t c = 0;
-        pa_astarpa2_stats fst{};
-        const int rc = align_hip(ba.data(), p->n[i], bb.data(), p->m[i], fallback, !cost_only_astar, false, &c, &text, &fst);
-        if (rc != 0) return fail_all(rc);
-        if (p->astar) {
-            p->pair_stats[i] = fst;
-            if (results[i].status != apa2::kOk) costs[i] = c;  // the forward pass itself handed the pair back
-            cost_out[i] = c;
-        }
-        if (c != costs[i]) {
-            set_error("traceback fallback disagrees with the batched cost (pair %zu: %d vs %d)", i, c, costs[i]);
-            return fail_all(PA_E_INTERNAL);
-        }
-        if (!cigar_out) continue;
-        if (!(p->view_mode && p->in_text(cigar_out[i]))) std::free(cigar_out[i]);
-        cigar_out[i] = (char*)std::malloc(text.size() + 1);
-        if (!cigar_out[i]) {
-            set_error("out of memory");
-            return fail_all(PA_E_NOMEM);
-        }
-        std::memcpy(cigar_out[i], text.c_str(), text.size() + 1);
-    }
-    mark("pairs handed back");
+    for (size_t i = 0; i < P; ++i) cost_out[i] = r.costs[i];
+    r.clock.mark("small arrays + statistics");
+    if (const int rc = redo_handed_back(r)) return rc;
+    r.clock.mark("pairs handed back");
+    r.guard.commit();
     return 0;
 }
 

@@ -248,6 +248,42 @@ def test_chunks_and_trace_order_do_not_change_results(env):
     assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-500:], r.stderr[-1500:])
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("chunks,count", [(3, 7), (8, 3)])
+def test_more_chunks_than_pairs_can_fill_evenly(chunks, count):
+    """The chunk plan at its edges: 7 pairs in 3 chunks (2 + 2 + 3) and 8 chunks asked for 3 pairs (one pair each).  Both families and the
+    full-DP traced batch, each plan aligned twice: cost, CIGAR string and statistics against the CPU-kernel engine."""
+    import os
+    import subprocess
+    import sys
+    import textwrap
+
+    code = textwrap.dedent("""
+        import sys
+        sys.path.insert(0, %r)
+        import oracle
+        import astar_pairwise_aligner_amd as pa
+        from tests.test_gpu_engine import gpu_params
+        from tests.test_sweep_emu import KEYS
+        from tests.util_seq import gen_pair
+        pairs = [gen_pair((100, 700, 1500, 2300, 3000, 450, 1900)[i], (0.01, 0.05, 0.1, 0.15, 0.08, 0.03, 0.12)[i], 300 + i) for i in range(%d)]
+        nw = oracle.make_params(domain="full", heuristic="none", doubling="none", block_width=256, sparse=True, incremental_doubling=False, dt_trace=False)
+        for oc in (oracle.params_simple(), oracle.params_full(), nw):
+            want = [oracle.cpu_align(x, y, oc) for x, y in pairs]
+            b = pa.Batch(pairs, trace=True) if oc is nw else pa.Batch(pairs, params=gpu_params(pa, oc))
+            for rep in range(2):
+                costs, cigars, _, _ = b.align_c_strings() if rep else b.align()
+                assert [(int(c), g) for c, g in zip(costs, cigars)] == [w[:2] for w in want], rep
+                if oc is not nw:
+                    assert all(s[k] == w[2][k] for s, w in zip(b.pair_stats(), want) for k in KEYS), rep
+            assert b.trace_fallbacks() == 0
+            b.close()
+        print("ok")
+    """) % (str(__import__("pathlib").Path(__file__).resolve().parent.parent), count)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=dict(os.environ, PA_ALIGN_CHUNKS=str(chunks)))
+    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-300:], r.stderr[-1500:])
+
+
 @pytest.mark.parametrize("preset", ["simple", "full"])
 def test_two_pairs_per_strip_changes_nothing(pa, oracle, monkeypatch, preset):
     """Round 5: two blocks of at most 16 words from two pairs of one workgroup run as ONE strip (pair A in lanes 0..31, pair B in lanes

@@ -405,3 +405,63 @@ def test_the_second_round_is_bounded_in_memory(pa, oracle, monkeypatch):
         assert per_pair <= peak <= 2.5 * per_pair, (peak, per_pair)  # two pairs at a time: five sub-batches
         for (x, y), c, g in list(zip(pairs, costs, cigars))[::3]:
             assert (int(c), g) == oracle.cpu_align(x, y, oc)[:2]
+
+
+@pytest.mark.parametrize("preset", ["simple", "full"])
+def test_view_pointers_after_a_forced_second_round(preset):
+    """pa_batch_align_view on a plan whose windows are far too small (PA_APA2_WINDOW=4 words, read once per process: a child), every pair
+    of the second round a sub-batch of its own (PA_WINDOW_RETRY_BYTES=1).  Who owns each returned pointer: the texts of the first round
+    lie packed, one after another, in the plan's text buffer; a pair of the second round has a NUL-terminated string of its own outside
+    it, as many of them as pa_batch_window_retries counts.  A second call (it releases the plan-owned strings of the first) returns the
+    same; cost, text and statistics of every pair equal the engine over the CPU kernels."""
+    import os
+    import subprocess
+    import sys
+    import textwrap
+
+    code = textwrap.dedent("""
+        import ctypes as C
+        import sys
+        sys.path.insert(0, %r)
+        import numpy as np
+        import oracle
+        import astar_pairwise_aligner_amd as pa
+        from astar_pairwise_aligner_amd import capi
+        from tests.test_gpu_engine import gpu_params
+        from tests.test_sweep_emu import KEYS
+        from tests.util_seq import gen_pair
+        oc = oracle.params_full() if %r == "full" else oracle.params_simple()
+        pairs = [gen_pair(n, e, seed) for n, e, seed in [(60, 0.05, 1), (100, 0.01, 2), (3000, 0.15, 3), (2500, 0.1, 4), (1500, 0.15, 5), (3000, 0.3, 6)]]
+        n = len(pairs)
+        want = [oracle.cpu_align(x, y, oc) for x, y in pairs]
+        b = pa.Batch(pairs, params=gpu_params(pa, oc))
+        L = capi.load()
+        for rep in range(2):
+            out, lens, txt = np.zeros(n, np.int32), np.zeros(n, np.uint32), (C.c_void_p * n)()
+            assert L.pa_batch_align_view(b._h, capi._p(out), txt, capi._p(lens), None, None) == 0, capi.last_error()
+            retries = b.window_retries() // (rep + 1)  # (the counter sums over the calls)
+            assert 1 <= retries < n and b.trace_fallbacks() == 0, (retries, b.trace_fallbacks())
+            st = b.pair_stats()
+            for i in range(n):
+                assert (int(out[i]), C.string_at(txt[i], int(lens[i])).decode()) == want[i][:2], i
+                assert {k: st[i][k] for k in KEYS} == {k: want[i][2][k] for k in KEYS}, i
+            # the smallest pair (one word of rows: its window is its whole column) is in the text buffer; what is packed behind it is too
+            spans = sorted((txt[i], int(lens[i]), i) for i in range(n))
+            k = [s[2] for s in spans].index(0)
+            while k > 0 and spans[k - 1][0] + spans[k - 1][1] == spans[k][0]:
+                k -= 1
+            packed = [spans[k][2]]
+            while k + 1 < n and spans[k][0] + spans[k][1] == spans[k + 1][0]:
+                k += 1
+                packed.append(spans[k][2])
+            own = [i for i in range(n) if i not in packed]
+            assert len(own) == retries, (own, retries)
+            assert all(C.string_at(txt[i], int(lens[i]) + 1)[-1] == 0 for i in own)
+        c2, g2, _, _ = b.align_c_strings()  # pa_batch_align on the same plan: every string the caller's own
+        assert [(int(c), g) for c, g in zip(c2, g2)] == [w[:2] for w in want] and b.window_retries() == 3 * retries
+        b.close()
+        print("ok", retries)
+    """) % (str(__import__("pathlib").Path(__file__).resolve().parent.parent), preset)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, PA_APA2_WINDOW="4", PA_WINDOW_RETRY_BYTES="1"))
+    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-300:], r.stderr[-1500:])

@@ -321,6 +321,34 @@ def test_view_and_c_string_entry_points_agree(pa, oracle):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dt", [False, True])
+def test_costs_alone_then_cigars_on_the_same_traced_plan(pa, oracle, dt):
+    """pa_batch_align with cigar_out = NULL on a traced full-DP plan (re-fill only, and with the DT-trace options) returns the costs and hands
+    out no string; the same plan aligned again WITH CIGARs gives the engine's strings, and costs alone once more the same costs.  Costs
+    against the plain DP, strings against the engine over the CPU kernels, nothing goes to the host engine."""
+    from astar_pairwise_aligner_amd import capi
+    from tests.test_gpu_engine import gpu_params
+
+    pairs = [gen_pair(n, e, seed=40 + n) for n, e in ((100, 0.01), (257, 0.15), (700, 0.05), (1500, 0.1), (3000, 0.15))] + [(b"", b"ACGTAC"), (b"ACGT", b"")]
+    prm = dt_params(oracle) if dt else traced_params(oracle)
+    bt = pa.Batch(pairs, trace=True, trace_params=gpu_params(pa, prm) if dt else None)
+    want = [oracle.levenshtein(a, b) for a, b in pairs]
+
+    def costs_alone():
+        out = np.full(len(pairs), -1, np.int32)
+        assert capi.load().pa_batch_align(bt._h, capi._p(out), None, None, None) == 0, capi.last_error()
+        return out.tolist()
+
+    assert costs_alone() == want
+    costs, cigars, _, _ = bt.align_c_strings()
+    assert costs.tolist() == want
+    for (a, b), g in zip(pairs, cigars):
+        assert g == oracle.cpu_align(a, b, prm)[1] and oracle.cigar_verify(g, a, b) == oracle.levenshtein(a, b)
+    assert costs_alone() == want and bt.trace_fallbacks() == 0
+    bt.close()
+
+
+@pytest.mark.gpu
 def test_c_batch_view_program(tmp_path):
     """tests/c_abi/batch_view_check.c: pa_batch_align_view from plain C beside pa_batch_align and pa_align, both presets."""
     import os
