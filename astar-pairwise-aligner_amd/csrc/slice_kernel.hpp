@@ -28,6 +28,11 @@
 // MI355X_MICROARCH.md R2: a boundary row is preset to hp = hm = ~0, which no real delta pair can be).  Jobs (group, strip) are claimed by an
 // atomic ticket in producer-before-consumer order, so a consumer's producer has always started; every poll is bounded.
 //
+// The step: 7 R + 11 VALU instructions in ONE basic block that every lane runs in every step -- eight DPP instructions (PA_SLICE_FEED), the
+// rows, one store, two running counters and the capture test.  No lane is predicated: a lane in front of column 0 is kept in the left
+// column's state by the NEUTRAL border (hp, hm) = (0, ~0) that the pipeline registers start with, a lane behind the last column computes
+// what nothing reads; the store's offset and the capture's column are per-lane counters, the step counter is scalar (see the kernel).
+//
 // Ragged pairs: rows beyond |b| of a pair are padding that nothing reads (rows only depend on rows above them).  Pairs of a group whose
 // |a| differ are CAPTURED: when a lane has finished column |a_p| of pair p it stores bit p of its rows' (vp, vm) -- events sorted by
 // column, one per distinct |a| of the group; the last event is the group's last column.  slice_score_kernel then sums, per pair, the
@@ -127,6 +132,29 @@ __device__ __forceinline__ void st_boundary(uint2* p, uint32_t hp, uint32_t hm) 
               [hmp_] "v"(hmp));                                                                                                         \
     } while (0)
 
+// The top of a step: every lane takes what the lane above it had a step ago -- the column's two code planes (a0, a1, in place) and the
+// bottom row's (hp, hm) of the column (from ohp / ohm into hpp / hmp) --, lane 0 the chunk registers' value of its own lane, and the four
+// chunk registers rotate one lane.  v_cndmask_b32_dpp does the first in ONE instruction a register: vcc = 1 selects the second source in
+// lane 0 and the DPP source (wave_shr:1; bound_ctrl, so lane 0 -- which has no source lane -- is written all the same) in every other lane;
+// v_mov_b32_dpp keeps `old` in lane 0 instead, which costs a copy of the chunk register in front and, for a0 / a1, one behind.  The
+// registers a DPP operand reads must not have been written by the two instructions before (the assembler adds no s_nop inside asm): the
+// rotations come first and read only what the step before rotated, ohp / ohm -- written by the last rows of the step before -- come last.
+#define PA_SLICE_FEED(a0, a1, hpp, hmp, ohp, ohm, cAx, cAy, cHx, cHy)                                                                    \
+    asm volatile(                                                                                                                       \
+        "s_mov_b64 vcc, 1\n\t"                                                                                                          \
+        "v_cndmask_b32_dpp %[a0_], %[a0_], %[cAx_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                         \
+        "v_cndmask_b32_dpp %[a1_], %[a1_], %[cAy_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                         \
+        "v_cndmask_b32_dpp %[hpp_], %[ohp_], %[cHx_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                       \
+        "v_cndmask_b32_dpp %[hmp_], %[ohm_], %[cHy_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                       \
+        "v_mov_b32_dpp %[cAx_], %[cAx_] wave_rol:1 row_mask:0xf bank_mask:0xf\n\t"                                                      \
+        "v_mov_b32_dpp %[cAy_], %[cAy_] wave_rol:1 row_mask:0xf bank_mask:0xf\n\t"                                                      \
+        "v_mov_b32_dpp %[cHx_], %[cHx_] wave_rol:1 row_mask:0xf bank_mask:0xf\n\t"                                                      \
+        "v_mov_b32_dpp %[cHy_], %[cHy_] wave_rol:1 row_mask:0xf bank_mask:0xf"                                                          \
+        : [a0_] "+v"(a0), [a1_] "+v"(a1), [hpp_] "=&v"(hpp), [hmp_] "=&v"(hmp), [cAx_] "+v"(cAx), [cAy_] "+v"(cAy), [cHx_] "+v"(cHx),   \
+          [cHy_] "+v"(cHy)                                                                                                              \
+        : [ohp_] "v"(ohp), [ohm_] "v"(ohm)                                                                                              \
+        : "vcc")
+
 // ticket_err[0] = ticket, [1] = error code (first one wins)
 template <int R>
 __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict__ jobs, int njobs, const SliceGroup* __restrict__ groups,
@@ -173,9 +201,9 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
         // write-through boundary store of the step just before, i.e. one round trip to memory per chunk with the wavefront parked
         // (tools/slice_wait_probe.py).  So the prefetch loads are issued from inline asm (the compiler keeps no score for them) and waited
         // for by hand kWaitStep steps later with vmcnt(kWaitStep): by then exactly kWaitStep younger stores have been issued -- ONE PER STEP,
-        // by EVERY strip, by ALL lanes: a raw buffer store whose offset is out of range except in lane 63 of a strip that has a strip below
-        // (an out-of-range store is dropped by the memory pipeline but issued and counted like any other), so the instruction is issued
-        // whenever any lane is at a column, which is every step of the loop -- and "at most kWaitStep operations outstanding" then means
+        // by EVERY strip, by ALL lanes, unconditionally: a raw buffer store whose offset is out of range except in lane 63 of a strip that
+        // has a strip below, and there only while the lane is at a column (an out-of-range store is dropped by the memory pipeline but
+        // issued and counted like any other) -- and "at most kWaitStep operations outstanding" then means
         // "everything older than those stores has retired": the loads, and the stores of the chunk before, issued microseconds ago.
         // Rules that keep this sound (tests/test_slice_isa.py checks the first two in the compiled code of every instantiation):
         //  * between the load and the wait nothing may READ the loads' destination registers -- the compiler believes they are valid from
@@ -184,7 +212,20 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
         //  * no compiler-visible wait may sit in the step loop (the row loads of the job are waited for before the loops);
         //  * more operations in between (the capture's atomics) only make the wait stronger.
         constexpr int kWaitStep = 8;
-        uint32_t o_hp = 0, o_hm = 0, o_a0 = 0, o_a1 = 0;
+        // The pipeline registers: what this lane worked on in the step before and the lane below takes in this one.  (hp, hm) starts as
+        // (0, ~0), the NEUTRAL border: a row with vp = ~0, vm = 0 that takes it in has z = ~0 whatever its eq, so hm = vp = ~0, hp = 0,
+        // vp' = ~0, vm' = 0 -- it keeps the left column's state and hands (0, ~0) on.  A lane in front of column 0 therefore needs no
+        // predicate: it runs the rows like every other lane and changes nothing (tests/test_slice_neutral_border.py).  A lane behind the last
+        // column computes garbage that nothing reads: its columns were captured at c + 1 == ev_col <= n, its bottom row only goes to lanes
+        // that are behind the end too, and its boundary store is out of the descriptor's range.
+        uint32_t a0 = 0, a1 = 0, o_hp = 0, o_hm = ~0u;
+        // Per-lane running counters instead of index arithmetic in the step: `off`, the boundary store's byte offset (+ 8 a step), is
+        // 8 c in lane 63 of a strip that has a strip below -- out of the descriptor's n * 8 bytes while c < 0 ((uint32)c * 8 >= 2^32 - 8 * 63)
+        // and from c = n on -- and in every other lane starts at 0x7FFFFFF0 and stays out of range for the whole job (n + 63 steps, n < 2^27:
+        // no wrap); `cnt` = c + 1, the columns this lane has finished after the step, is real in every lane (every lane captures).
+        uint32_t off = (lane == 63 && has_out) ? (uint32_t)(-lane) * 8u : 0x7FFFFFF0u;
+        int cnt = 1 - lane;
+        constexpr int kNoEvent = INT32_MIN;  // no lane's cnt (1 - 63 .. n + 63) is ever this
         uint32_t ev_i = 0;
         int ev_col = ev[0].col;
         const int nchunks = (n + 63 + 63) / 64;  // steps 0 .. n + 62
@@ -252,51 +293,45 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
             const int jend = min(64, n + 63 - q * 64);
             const int wait_at = more ? kWaitStep : -1;  // (one scalar compare per step)
             for (int j = 0; j < jend; ++j) {
+                asm volatile("" : "+s"(j));  // (the step counter stays scalar: as a phi of the loop it went to a VGPR, three VALU instructions a step)
                 if (j == wait_at) {  // (uniform)
                     asm volatile("s_waitcnt vmcnt(8) ; pa_prefetch_wait" : "+v"(nA), "+v"(nH)::"memory");
                     kA = make_uint2((uint32_t)nA, (uint32_t)(nA >> 32));
                     if (has_in) kH = make_uint2((uint32_t)nH, (uint32_t)(nH >> 32));
                 }
-                const int c = q * 64 + j - lane;
                 // lane 0 takes the chunk registers' value of ITS lane -- they rotate one lane per step, so that is column 64 q + j --, every other
                 // lane the value the lane above it had a step ago
-                const uint32_t a0 = dpp_wave_shr1(cA.x, o_a0), a1 = dpp_wave_shr1(cA.y, o_a1);
-                uint32_t hpp = dpp_wave_shr1(cH.x, o_hp), hmp = dpp_wave_shr1(cH.y, o_hm);
-                cA.x = dpp_wave_rol1(cA.x);
-                cA.y = dpp_wave_rol1(cA.y);
-                cH.x = dpp_wave_rol1(cH.x);
-                cH.y = dpp_wave_rol1(cH.y);
-                o_a0 = a0;
-                o_a1 = a1;
-                if ((unsigned)c < (unsigned)n) {
+                uint32_t hpp, hmp;
+                PA_SLICE_FEED(a0, a1, hpp, hmp, o_hp, o_hm, cA.x, cA.y, cH.x, cH.y);
 #pragma unroll
-                    for (int i = 0; i < R; i += 2) {
-                        uint32_t hpo, hmo;
-                        PA_SLICE_ROW_PAIR(vp[i], vm[i], vp[i + 1], vm[i + 1], nb0[i], nb1[i], nb0[i + 1], nb1[i + 1], a0, a1, hpp, hmp, hpo, hmo);
-                        hpp = hpo;
-                        hmp = hmo;
-                    }
-                    o_hp = hpp;
-                    o_hm = hmp;
-                    {  // lane 63's (hp, hm) of column c: 8 bytes, write-through; every other offset is out of range (see the rules above)
-                        const pa_slice_u32x2 d = {hpp, hmp};
-                        __builtin_amdgcn_raw_buffer_store_b64(d, hrs, (lane == 63 && has_out) ? (uint32_t)c * 8u : 0x7FFFFFF0u, 0, 16);  // aux 16 = sc1
-                    }
-                    if (c + 1 == ev_col) {  // some pairs' a ends here: keep their bits of this lane's rows (the last event is the last column)
-                        const uint32_t mask = ev[ev_i].mask;
-                        // V is zeroed before every pass; a pair is captured once, so OR-ing its bit in is exact.  One row at a time (the
-                        // compiler would otherwise hold 2 R masked values at once: this path is rare, registers are not)
-#pragma unroll
-                        for (int i = 0; i < R; ++i) {
-                            atomicOr(&V[row0 + i].x, vp[i] & mask);
-                            atomicOr(&V[row0 + i].y, vm[i] & mask);
-                            asm volatile("" ::: "memory");
-                        }
-                        ++ev_i;
-                        ev_col = ev_i < grp.ev_count ? ev[ev_i].col : -1;
-                        __builtin_amdgcn_s_waitcnt(0);  // (otherwise the compiler waits for this load at the test above, in EVERY step -- behind the store)
-                    }
+                for (int i = 0; i < R; i += 2) {
+                    uint32_t hpo, hmo;
+                    PA_SLICE_ROW_PAIR(vp[i], vm[i], vp[i + 1], vm[i + 1], nb0[i], nb1[i], nb0[i + 1], nb1[i + 1], a0, a1, hpp, hmp, hpo, hmo);
+                    hpp = hpo;
+                    hmp = hmo;
                 }
+                o_hp = hpp;
+                o_hm = hmp;
+                {  // lane 63's (hp, hm) of column c: 8 bytes, write-through; every other offset is out of range (see the rules above)
+                    const pa_slice_u32x2 d = {hpp, hmp};
+                    __builtin_amdgcn_raw_buffer_store_b64(d, hrs, off, 0, 16);  // aux 16 = sc1
+                }
+                off += 8u;
+                if (cnt == ev_col) {  // some pairs' a ends here: keep their bits of this lane's rows (the last event is the last column)
+                    const uint32_t mask = ev[ev_i].mask;
+                    // V is zeroed before every pass; a pair is captured once, so OR-ing its bit in is exact.  One row at a time (the
+                    // compiler would otherwise hold 2 R masked values at once: this path is rare, registers are not)
+#pragma unroll
+                    for (int i = 0; i < R; ++i) {
+                        atomicOr(&V[row0 + i].x, vp[i] & mask);
+                        atomicOr(&V[row0 + i].y, vm[i] & mask);
+                        asm volatile("" ::: "memory");
+                    }
+                    ++ev_i;
+                    ev_col = ev_i < grp.ev_count ? ev[ev_i].col : kNoEvent;
+                    __builtin_amdgcn_s_waitcnt(0);  // (otherwise the compiler waits for this load at the test above, in EVERY step -- behind the store)
+                }
+                ++cnt;
             }
         }
         if (dbg && lane == 0) {

@@ -38,7 +38,7 @@ struct Info {
     double boundary_bytes;        // of those, the boundary rows that are reset before every pass
 };
 Info info(const Plan* p);
-constexpr int kStepOverheadInstr = 24;  // VALU instructions of a strip step outside the rows (ISA count: DPP, predicates, addresses, the poll test)
+constexpr int kStepOverheadInstr = 11;  // VALU instructions of a strip step outside the rows (ISA count, tests/test_slice_step_isa.py: 8 DPP, the store offset, the column counter and its compare)
 
 }  // namespace slice
 }  // namespace pa

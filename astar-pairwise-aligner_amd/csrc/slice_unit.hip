@@ -28,12 +28,15 @@ struct Plan {
 
 static int strips_for(size_t m, int R) { return (int)((m + (size_t)64 * R - 1) / ((size_t)64 * R)); }
 
-// ns per row step (7 instructions) per wavefront at two wavefronts per SIMD, and per step outside the rows (24 instructions, the same as with
-// the 8-instruction row of round 6, which priced them at three of its row steps: 3 x 17.9 ns): the bench batch's 8192 jobs of 100 063 steps
-// take their wave slots 4 x 86.5 ms (346 ms a launch: profiles/r07_runs/row_ab.log), 864 ns a step = 50 x 16.2 + 53.7;
+// ns per row step (7 instructions) per wavefront at two wavefronts per SIMD, and per step outside the rows (11 instructions).  The row step:
+// the bench batch's 8192 jobs of 100 063 steps took their wave slots 4 x 86.5 ms with the predicated step of round 7 (346 ms a launch:
+// profiles/r07_runs/row_ab.log), 864 ns a step = 50 x 16.2 + 53.7 (24 instructions outside the rows, priced at 3.31 row steps).  The step
+// outside the rows now: the same batch, alternated three times with that build on one box (profiles/r08_runs/step_ab.log), 353.8-354.2
+// against 342.2-342.6 ms a launch = 884.3 against 855.5 ns a step; on that box a row step is 884.3 / 53.31 = 16.59 ns, so the 28.8 ns
+// that went leave 55.0 - 28.8 = 26.2 ns = 1.58 row steps = 25.6 ns at 16.2 ns a row step.
 // kChainPenalty: what a strip loses per strip of its group's chain (asleep behind the strip above, filling and draining the chain) -- 36 strips
 // of 44 rows against 32 of 50 for 16 384 x 100 kbp: 789 against 760 ms where the plain count of instructions calls it a tie.
-static constexpr double kNsPerRowStep = 16.2, kNsStepOverhead = 53.7, kChainPenalty = 0.0015;
+static constexpr double kNsPerRowStep = 16.2, kNsStepOverhead = 25.6, kChainPenalty = 0.0015;
 
 int choose_rows_per_lane(const size_t* a_len, const size_t* b_len, size_t pairs, double simds, double* est_ns) {
     if (const char* e = getenv("PA_SLICE")) {

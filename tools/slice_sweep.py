@@ -1,5 +1,7 @@
 """Round 6: the bit-sliced kernel (PA_SLICE=1, the library's rows per lane) against the strip kernels (PA_SLICE=0) and the default choice,
-per batch shape: kernel ms of the best of three passes.  python tools/slice_sweep.py 100000x64 10000x4096 ..."""
+per batch shape: kernel ms of the best of three passes.  python tools/slice_sweep.py 100000x64 10000x4096 ...
+--modes 52,50,48,default runs these PA_SLICE settings instead (a number above 1 forces that many rows per lane): is the library's own
+choice of rows per lane the fastest one?"""
 import os
 import sys
 
@@ -8,13 +10,19 @@ import astar_pairwise_aligner_amd as pa
 from astar_pairwise_aligner_amd.generate import generate_pair
 
 pa.require_gpu()
-cases = [tuple(int(x) for x in a.split("x")) for a in sys.argv[1:]]
+argv = sys.argv[1:]
+modes = ("0", "1", None)
+if "--modes" in argv:
+    at = argv.index("--modes")
+    modes = tuple(None if m == "default" else m for m in argv[at + 1].split(","))
+    del argv[at : at + 2]
+cases = [tuple(int(x) for x in a.split("x")) for a in argv]
 for n, pairs in cases:
     base = [generate_pair(n, 0.05, seed=s + 1) for s in range(min(pairs, 64))]
     ps = [base[i % len(base)] for i in range(pairs)]
     row = []
     ref = None
-    for mode in ("0", "1", None):
+    for mode in modes:
         if mode is None:
             os.environ.pop("PA_SLICE", None)
         else:
