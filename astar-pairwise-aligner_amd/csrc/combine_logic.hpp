@@ -1,4 +1,4 @@
-// combine_logic.hpp -- the gathering protocol of the call combiner behind pa_align and the astarpa-c symbols (engine_hip.hip), host
+// combine_logic.hpp -- the gathering protocol of the call combiner behind pa_align and the astarpa-c symbols (combine_unit.hip), host
 // code only, written once so that it can run without a GPU: oracle/combine_emu.cpp drives it from many host threads with a stand-in for
 // the batch, under ThreadSanitizer (tests/test_combine_emu.py).
 //

@@ -11,7 +11,7 @@
 //   lib.rs:122-175        cost_or_align;   params.rs:46-128 presets nw / simple / full
 //
 // The DP rectangles themselves are NOT computed here: every `compute` / `fill` goes to the Backend
-// (the HIP strip kernels in the shipped library; see engine_hip.hip).  The backend owns the sequence
+// (the HIP strip kernels in the shipped library; see hip_backend.hpp).  The backend owns the sequence
 // profiles and the persistent horizontal-delta row `h` used by incremental doubling (blocks.rs:103-105).
 #pragma once
 #include <algorithm>
@@ -400,7 +400,7 @@ struct has_compute_chain : std::false_type {};
 template <class B>
 struct has_compute_chain<B, std::void_t<typename B::ChainSeg>> : std::true_type {};
 
-// Backend concept (implemented by HipBackend in engine_hip.hip and by the test-only CpuBackend):
+// Backend concept (implemented by HipBackend in hip_backend.hpp and by the test-only CpuBackend):
 //   I n() const; I m() const;                       sequence lengths
 //   const uint8_t* a() const; const uint8_t* b() const;   raw ASCII (trace uses them, trace.rs:443-500)
 //   void enable_h_row();                            allocate the persistent h row (blocks.rs:119-123)

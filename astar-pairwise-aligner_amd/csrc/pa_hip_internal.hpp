@@ -51,6 +51,30 @@ struct DeviceBuf {
     template <class T>
     T* as() const { return reinterpret_cast<T*>(ptr); }
 };
+// A pinned host block that only grows (hipHostMallocDefault): a request beyond its size frees it and allocates max(2 * bytes, 64 KiB).
+// Its owner keeps it for its own life; it is not one of pinned_take's pooled blocks.
+struct PinnedBuf {
+    void* ptr = nullptr;
+    size_t size = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { release(); }
+    void* reserve(size_t bytes) {  // nullptr (and the error set) when the allocation fails
+        if (bytes > size) {
+            release();
+            const size_t want = bytes * 2 > (size_t(1) << 16) ? bytes * 2 : size_t(1) << 16;
+            if (!hip_ok(hipHostMalloc(&ptr, want, hipHostMallocDefault), "hipHostMalloc")) return nullptr;
+            size = want;
+        }
+        return ptr;
+    }
+    void release() {
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr;
+        size = 0;
+    }
+};
 // d.alloc(max(bytes, 16)), then the copy queued on s
 bool upload(DeviceBuf& d, const void* src, size_t bytes, hipStream_t s);
 // Device-memory budget of one traced chunk: the megabytes in the environment variable `env_mb`, else a quarter of the free memory.
@@ -96,6 +120,19 @@ bool launch_strips(const StripJob* d_jobs, int njobs, bool fill, uint32_t* d_tic
 bool launch_pairs(const StripJob* d_jobs, const int32_t* d_first, int npairs, uint32_t* d_ticket_err, hipStream_t s, int k, bool ckpt = false);
 int align_hip(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, const pa_astarpa2_params& params, bool trace, bool self_check,
               int32_t* cost_out, std::string* cigar_out, pa_astarpa2_stats* stats_out);
+// combine_unit.hip -- callers inside align_hip at the same time become one batch.  A caller that combine_eligible() accepts (lengths, a
+// parameter set the batch kernels take, not the combiner's own batch handing a pair back) holds a CombineInside while it is inside:
+// these are the crowd that combine_align() looks at when it decides whether to combine now.  combine_align: 0 = done, results handed
+// out; nonzero = not combined, the caller takes the single-pair path.
+bool combine_eligible(size_t a_len, size_t b_len, const pa_astarpa2_params& params);
+struct CombineInside {
+    CombineInside();
+    ~CombineInside();
+    CombineInside(const CombineInside&) = delete;
+    CombineInside& operator=(const CombineInside&) = delete;
+};
+int combine_align(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, const pa_astarpa2_params& params, int32_t* cost_out,
+                  std::string* cigar_out, pa_astarpa2_stats* stats_out);
 // The semi-global search's ScatterProfile of a pattern (four u64 match masks per 64-row word, padding rows match everything) and its
 // left column v0 (V words), max(ceil(plen / 64), 1) words each.  PA_E_INVALID_BASE on a character outside ACGTNYR* (either case).
 int search_profile(const uint8_t* pattern, size_t plen, float unmatched_cost, std::vector<uint64_t>& prof, std::vector<uint64_t>& v0);

@@ -404,7 +404,7 @@ void DeviceBuf::release() {
         }
         if (size >= kCacheMin && cache_on()) {
             // hipFree waits for the device before it lets a buffer go; a cached block may be handed to another thread at once, so
-            // this waits too (whoever must not wait -- the sweep's pool while passes are in flight -- never frees, engine_hip.hip)
+            // this waits too (whoever must not wait -- the sweep's pool while passes are in flight -- never frees, sweep_hip.hpp)
             int cur = device;
             (void)hipGetDevice(&cur);
             if (cur != device) (void)hipSetDevice(device);  // (a batch destroyed from a thread bound to another GPU)

@@ -6,7 +6,7 @@
 // (band.rs:100-182).  With traceback on, the blocks of the successful pass are read back and handed to the engine's own
 // Blocks::trace (engine.hpp), so DT-trace / re-fill / parent are the same code as on the host-driven path.
 //
-// Templated over a Launcher (device memory + one pass): the HIP launcher lives in engine_hip.hip, tests/tools/sweep_emu has
+// Templated over a Launcher (device memory + one pass): the HIP launcher lives in sweep_hip.hpp, tests/tools/sweep_emu has
 // one that runs the same wave program on host threads.
 #pragma once
 #include <cstring>

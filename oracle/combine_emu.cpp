@@ -2,7 +2,7 @@
  * oracle/combine_emu.cpp -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
  *
  * The gathering protocol of the call combiner (astar-pairwise-aligner_amd/csrc/combine_logic.hpp: concurrent callers of pa_align become
- * one batch) WITHOUT a GPU: T host threads submit requests through the very template engine_hip.hip instantiates; the "batch" is a
+ * one batch) WITHOUT a GPU: T host threads submit requests through the very template combine_unit.hip instantiates; the "batch" is a
  * stand-in that takes a while and computes a function of every request's input.  What it checks: every caller gets ITS result, nobody is
  * left waiting (lost wake-ups, a batch that throws), requests really travel in groups, several batches run side by side -- and, built
  * with -fsanitize=thread (`make -C oracle tsan_combine`), that the requests (stack objects of their owners, filled in by another thread)

@@ -1,4 +1,4 @@
-"""The call combiner's gathering protocol (csrc/combine_logic.hpp, what engine_hip.hip runs behind pa_align and the astarpa-c symbols)
+"""The call combiner's gathering protocol (csrc/combine_logic.hpp, what combine_unit.hip runs behind pa_align and the astarpa-c symbols)
 on host threads with a stand-in batch (oracle/combine_emu.cpp): every caller gets its own result, nobody is left waiting -- also when
 batches throw --, requests travel in groups and several batches run side by side; `make -C oracle tsan_combine`: the same under
 ThreadSanitizer.  The GPU side: tests/test_gpu_engine.py::test_concurrent_callers_are_combined_and_get_the_single_call_results."""

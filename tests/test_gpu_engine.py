@@ -259,7 +259,7 @@ def test_c_abi_is_reentrant_across_threads(pa, oracle):
 
 def test_concurrent_callers_are_combined_and_get_the_single_call_results(pa, oracle, monkeypatch):
     """Round 5: callers that are inside pa_align / an astarpa-c symbol at the same time are combined into one batch on the GPU
-    (csrc/engine_hip.hip combine_align).  Sixteen threads, both presets through the drop-in symbols and through pa_align with statistics:
+    (csrc/combine_unit.hip combine_align).  Sixteen threads, both presets through the drop-in symbols and through pa_align with statistics:
     EVERY result equals what the same call returns when it is made alone (the single-pair route), and the counters say calls were combined."""
     import ctypes as C
     import threading

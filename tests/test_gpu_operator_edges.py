@@ -3,8 +3,10 @@ plain DP of tests/rect_plain.py, bit for bit, at the shapes where the routes of 
 threshold (16 words), one strip (32 words), the mailbox fill's limits (1 MiB of `values`, 64 strips), the staged route (more than
 1024 strips, or PA_ENGINE_NO_FAST_PATH), unaligned column and word offsets, empty ranges, and the stored h row under every mode.
 
-Nothing here is compared with oracle/: tests/test_rect_plain.py pins the plain model to it on the CPU."""
+The operator calls are not compared with oracle/: tests/test_rect_plain.py pins the plain model to it on the CPU.  Only the engine
+calls of the staged route (ENGINE_PAIRS) are, as everywhere else, checked against the engine over the CPU oracle kernels."""
 import ctypes as C
+import json
 import os
 import subprocess
 import sys
@@ -16,7 +18,7 @@ import pytest
 
 from tests import rect_plain as rp
 from tests import strip_plain as sp
-from tests.util_seq import mutate, rand_seq
+from tests.util_seq import gen_pair, mutate, rand_seq
 
 pytestmark = pytest.mark.gpu
 
@@ -292,9 +294,29 @@ def test_handle_staged_by_size(tall):
 # ---- (h) the staged route at small shapes ------------------------------------------------------------------------------------
 
 
+ENGINE_PAIRS = [(300, 0.1), (3000, 0.1), (12000, 0.1)]
+
+
+def engine_over_operators(pa):
+    """[cost, CIGAR, statistics] of pa_align, traced, with the `incremental_doubling` configuration of tests/test_gpu_engine.py: the
+    host-driven engine, whose blocks go through HipBackend::compute_chain -- one fused launch through the mailbox, or, when there is
+    no mailbox route, one compute() per segment."""
+    import oracle
+    from tests.test_engine_cpu import configs
+    from tests.test_gpu_engine import STAT_KEYS, gpu_params
+
+    al = gpu_params(pa, configs(oracle)["incremental_doubling"]).make_aligner(True)
+    out = []
+    for n, e in ENGINE_PAIRS:
+        a, b = gen_pair(n, e, seed=n)
+        cost, cigar, stats = al.align_with_stats(a, b)
+        out.append([int(cost), cigar, {k: int(stats[k]) for k in STAT_KEYS}])
+    return out
+
+
 def staged_child():
     """Runs in a process of its own with PA_ENGINE_NO_FAST_PATH set (the library reads it once per process): reduced forms of the
-    grid, the random scripts and the fills, all through plan_rect + strip_kernel."""
+    grid, the random scripts and the fills, all through plan_rect + strip_kernel; then the engine over the same route."""
     import astar_pairwise_aligner_amd as pa
 
     assert os.environ.get("PA_ENGINE_NO_FAST_PATH") == "1"
@@ -306,10 +328,11 @@ def staged_child():
     script_check(pa, 50, 150)
     a, b = _similar_pair(*FILL_PAIR, seed=5)
     fill_check(pa, a, b, [(17, 17 + 70, 3, 3 + w) for w in (1, 16, 17, 33, 65)] + [(255, 255 + 33, 31, 31 + 40), (1, 2, 7, 8)], seed=60)
+    print("staged engine " + json.dumps(engine_over_operators(pa)))
     print("staged ok")
 
 
-def test_staged_route_at_small_shapes():
+def test_staged_route_at_small_shapes(pa, oracle):
     code = textwrap.dedent("""
         import sys
         sys.path.insert(0, %r)
@@ -318,6 +341,22 @@ def test_staged_route_at_small_shapes():
     """) % str(ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, PA_ENGINE_NO_FAST_PATH="1"))
     assert r.returncode == 0 and "staged ok" in r.stdout, f"child exited with {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    # the engine's chained blocks: one compute() per segment in the child, the fused chain in this process, the CPU-kernel engine
+    from tests.test_engine_cpu import configs
+    from tests.test_gpu_engine import STAT_KEYS
+
+    assert "PA_ENGINE_NO_FAST_PATH" not in os.environ
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("staged engine ")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    staged = json.loads(lines[0][len("staged engine "):])
+    fused = engine_over_operators(pa)
+    assert len(staged) == len(fused) == len(ENGINE_PAIRS)
+    for (n, e), got_staged, got_fused in zip(ENGINE_PAIRS, staged, fused):
+        a, b = gen_pair(n, e, seed=n)
+        wc, wg, ws = oracle.cpu_align(a, b, configs(oracle)["incremental_doubling"])
+        want = [wc, wg, {k: int(ws[k]) for k in STAT_KEYS}]
+        assert got_staged == want, ("staged", n)
+        assert got_fused == want, ("fused", n)
 
 
 # ---- (i) argument errors -----------------------------------------------------------------------------------------------------

@@ -2,9 +2,14 @@
 NoCost / GapCost / SH and the sparse, non-incremental block engine runs every align_for_bounded_dist pass as ONE persistent
 launch with the band logic (domain.rs:117-350) in the kernel.  Cost, CIGAR string and every band statistic must equal the
 host-driven engine over the CPU oracle kernels, and the host-driven engine over the HIP kernels (PA_ENGINE_NO_SWEEP)."""
+import json
 import os
 import random
+import subprocess
+import sys
+import textwrap
 import time
+from pathlib import Path
 
 import pytest
 
@@ -12,6 +17,8 @@ from tests.test_sweep_emu import KEYS, variants
 from tests.util_seq import gen_pair, rand_seq
 
 pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.fixture(scope="module")
@@ -77,6 +84,55 @@ def test_random_pairs_all_variants(pa, oracle):
         elif mode < 0.3:
             b = rand_seq(rng.randint(1, n + 50), s + 2)  # unrelated
         both(pa, oracle, a, b, vs[name], trace=rng.random() < 0.8)
+
+
+def small_traced_pairs():
+    return [gen_pair(n, e, seed=n * 7 + int(e * 100)) for n in (1, 255, 256, 257, 3000, 8191) for e in (0.05, 0.15)]
+
+
+def align_small_traced_pairs(pa):
+    """[cost, CIGAR, KEYS statistics] of every small pair, traced, `simple` preset."""
+    al = pa.AstarPa2Params.simple().make_aligner(True)
+    out = []
+    for a, b in small_traced_pairs():
+        cost, cigar, stats = al.align_with_stats(a, b)
+        out.append([int(cost), cigar, {k: int(stats[k]) for k in KEYS}])
+    return out
+
+
+def two_step_child():
+    """Runs in a process of its own with PA_SWEEP_READ_TWO_STEP set (the library reads it once per process): the blocks of every
+    successful pass come back by the two-step route of HipSweepLauncher::read_blocks, which otherwise only Mbp pairs take."""
+    import astar_pairwise_aligner_amd as pa
+
+    assert os.environ.get("PA_SWEEP_READ_TWO_STEP") == "1"
+    pa.require_gpu()
+    print("two-step " + json.dumps(align_small_traced_pairs(pa)))
+
+
+def test_two_step_read_back_at_small_shapes(pa, oracle):
+    """Both read-back routes build their engine blocks with one helper: at one block, around a block edge and at a dozen to 32 blocks
+    the two-step route (child process), the pinned one-synchronisation route (this process) and the CPU-kernel engine agree on
+    cost, CIGAR and statistics."""
+    assert "PA_SWEEP_READ_TWO_STEP" not in os.environ  # (this process takes the pinned route)
+    code = textwrap.dedent("""
+        import sys
+        sys.path.insert(0, %r)
+        from tests.test_gpu_sweep import two_step_child
+        two_step_child()
+    """) % str(ROOT)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, PA_SWEEP_READ_TWO_STEP="1"))
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("two-step ")]
+    assert r.returncode == 0 and len(lines) == 1, f"child exited with {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    two_step = json.loads(lines[0][len("two-step "):])
+    pinned = align_small_traced_pairs(pa)
+    pairs = small_traced_pairs()
+    assert len(two_step) == len(pinned) == len(pairs) == 12
+    for (a, b), got2, got1 in zip(pairs, two_step, pinned):
+        wc, wg, ws = oracle.cpu_align(a, b, oracle.params_simple())
+        want = [wc, wg, {k: int(ws[k]) for k in KEYS}]
+        assert got2 == want, ("two-step", len(a), len(b))
+        assert got1 == want, ("pinned", len(a), len(b))
 
 
 def test_sweep_equals_host_driven_engine(pa, oracle):
