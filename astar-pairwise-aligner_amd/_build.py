@@ -10,7 +10,7 @@ PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libastarpa_c_hip.so"
 
-HIP_SOURCES = ["pa_hip.hip", "runtime_unit.hip", "rect_unit.hip", "search_unit.hip", "debug_unit.hip", "engine_hip.hip", "combine_unit.hip", "astarpa_c.hip", "pairs_io.hip", "apa2_simple_unit.hip", "apa2_full_unit.hip", "gcsh_build_unit.hip", "sketch_unit.hip", "slice_unit.hip", "search_batch_unit.hip", "affine_unit.hip"]
+HIP_SOURCES = ["pa_hip.hip", "apa2_jobs_unit.hip", "runtime_unit.hip", "rect_unit.hip", "search_unit.hip", "debug_unit.hip", "engine_hip.hip", "combine_unit.hip", "astarpa_c.hip", "pairs_io.hip", "apa2_simple_unit.hip", "apa2_full_unit.hip", "gcsh_build_unit.hip", "sketch_unit.hip", "slice_unit.hip", "search_batch_unit.hip", "affine_unit.hip"]
 
 
 def _hipcc() -> str:
@@ -61,7 +61,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         return LIB_PATH
     # One hipcc per translation unit, side by side (they share no device symbols: no -fgpu-rdc), then one link: the build takes as
     # long as the slowest unit, rect_unit.hip with the strip and pair kernels' instances (about 190 s; apa2_full_unit.hip 35 s,
-    # pa_hip.hip and engine_hip.hip 20 s each, every other unit under 15 s; combine_unit.hip has no kernels).
+    # pa_hip.hip and engine_hip.hip 20 s each, every other unit under 15 s; combine_unit.hip and apa2_jobs_unit.hip have no kernels).
     from concurrent.futures import ThreadPoolExecutor
 
     extra = os.environ.get("PA_HIPCC_EXTRA", "").split()  # experiments only (e.g. -DPA_PHASE_BARRIERS)

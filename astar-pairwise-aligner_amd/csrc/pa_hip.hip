@@ -1,13 +1,9 @@
 // pa_hip.hip -- the batched plans of libastarpa_c_hip.so: struct pa_batch (full DP, banded, traced, A*PA2), how it is planned, launched
 // and reported (pa_batch_*), and the traceback and CIGAR-text kernels it launches.  The runtime layer is runtime_unit.hip, the strips
 // rect_unit.hip.  gfx950 only.
-#include "pa_hip_internal.hpp"
-#include "slice_plan.hpp"
+#include "pa_batch.hpp"
 #include "engine_capi.hpp"
 #include "trace_kernel.hpp"
-#include "apa2_units.hpp"
-
-#include <sched.h>
 
 #include <algorithm>
 #include <chrono>
@@ -99,170 +95,49 @@ __global__ __launch_bounds__(64) void format_pack_kernel(const uint32_t* __restr
 
 using namespace pa;
 
-// PA_ALIGN_PROFILE (diagnostics: where the time of a creation, an alignment call and a destruction goes), read once per process.
-static bool align_profile() {
-    static const bool on = getenv("PA_ALIGN_PROFILE") != nullptr;
-    return on;
+pa_batch::~pa_batch() {
+    const bool prof = align_profile();
+    const auto t0 = std::chrono::steady_clock::now();
+    if (prof) {  // (diagnostics: which of the batch's streams is still busy)
+        std::fprintf(stderr, "[pa_batch_destroy] busy: batch stream %d", stream && hipStreamQuery(stream) == hipErrorNotReady);
+        for (int c = 0; c < kMaxChunks; ++c)
+            if (cstream[c]) std::fprintf(stderr, " chunk%d %d", c, hipStreamQuery(cstream[c]) == hipErrorNotReady);
+        std::fprintf(stderr, "\n");
+        if (stream) (void)hipStreamSynchronize(stream);
+        std::fprintf(stderr, "[pa_batch_destroy] batch stream wait %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    // everything that reads or writes this batch's buffers was queued on its own streams: wait for those, not for the device
+    bool waited = true;
+    if (stream) waited = hipStreamSynchronize(stream) == hipSuccess && waited;
+    for (int c = 0; c < kMaxChunks; ++c)
+        if (cstream[c]) waited = hipStreamSynchronize(cstream[c]) == hipSuccess && waited;
+    if (waited) release_scope_begin_waited();
+    else release_scope_begin();  // (a stream whose wait failed: wait for the whole device before the buffers go anywhere)
+    if (prof) std::fprintf(stderr, "[pa_batch_destroy] device wait %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (ev2) (void)hipEventDestroy(ev2);
+    free_view_owned();
+    pinned_give(h_text, h_text_size);
+    pinned_give(h_meta, h_meta_size);
+    if (ev_pre) (void)hipEventDestroy(ev_pre);
+    if (evB0) (void)hipEventDestroy(evB0);
+    if (evB1) (void)hipEventDestroy(evB1);
+    for (int c = 0; c < kMaxChunks; ++c) {
+        if (evF0[c]) (void)hipEventDestroy(evF0[c]);
+        if (evF1[c]) (void)hipEventDestroy(evF1[c]);
+        if (evT1[c]) (void)hipEventDestroy(evT1[c]);
+        if (waited) stream_give(cstream[c], d_a.device);
+        else if (cstream[c]) (void)hipStreamDestroy(cstream[c]);  // a stream whose synchronize failed is not pooled
+    }
+    if (prof) std::fprintf(stderr, "[pa_batch_destroy] events, streams, pinned %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (waited) bstream_give(stream, d_a.device);  // (the batch waited for its streams above: nothing of it is queued on the stream any more)
+    else if (stream) (void)hipStreamDestroy(stream);
+    slice::destroy(sliced);
 }
 
-// The marks of PA_ALIGN_PROFILE on stderr: "[tag] what  ms since the mark before".  lap() is the figure alone.
-struct PhaseClock {
-    const char* tag;
-    double t_mark = now();
-    explicit PhaseClock(const char* tag_) : tag(tag_) {}
-    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-    double lap() {
-        const double t = now(), ms = t - t_mark;
-        t_mark = t;
-        return ms;
-    }
-    void mark(const char* what) {
-        if (align_profile()) std::fprintf(stderr, "[%s] %-28s %8.3f ms\n", tag, what, lap());
-    }
-};
-
-// ---- batched full DP ----------------------------------------------------------------------------
-
-struct pa_batch {
-    struct ReleaseScope {  // FIRST member = destroyed last: ends the scope the destructor's body opens (one device wait for all the buffers)
-        std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-        ~ReleaseScope() {
-            release_scope_end();
-            if (align_profile())
-                std::fprintf(stderr, "[pa_batch_destroy] buffers released %.3f ms after the batch was created\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        }
-    } release_scope_;
-    size_t pairs = 0;
-    std::vector<size_t> n, m, a_off, b_off, code_off, prof_off, gran_off;
-    DeviceBuf d_a, d_b, d_codes, d_prof, d_v, d_gran, d_jobs, d_sums, d_misc, d_desc, d_wavelog;
-    size_t max_n = 0, max_m = 0;
-    std::vector<StripJob> jobs;
-    std::vector<int> last_job;  // per pair (or -1 when w == 0)
-    size_t total_gran = 0;
-    bool gran_dirty = true;  // the hand-off granules must be cleared before the next pass
-    int k = 1;  // 32-row subwords per lane of this batch's strips
-    bool sequential = false;  // one wavefront per pair (pair_kernel) instead of chained strips
-    int block_waves = 1;
-    DeviceBuf d_first;  // sequential: first job of every pair (+ end)
-    // big cost-only batches: groups of 32 pairs, bit-sliced (slice_kernel.hpp); the strips of `jobs` are not planned then
-    slice::Plan* sliced = nullptr;
-    // banded mode (pa_batch_create_banded): per-pair cost threshold of the diagonal band that was planned
-    bool banded = false;
-    std::vector<int32_t> band_t;
-    size_t band_retries = 0;  // pairs re-run with a wider band (summed over passes)
-    DeviceBuf d_rjobs, d_rfirst;  // retry sub-batches
-    // traceback mode (pa_batch_create_trace / pa_batch_align)
-    bool trace = false;
-    int dt_max_g = 0, dt_fr_drop = 0;  // DT-trace options of the batched traceback (0: re-fill only)
-    size_t trace_fallbacks = 0;  // pairs whose traceback was redone by the host engine
-    std::vector<size_t> ckpt_off, cigar_off, word_off;  // per pair, in u32 (ckpt) / elements (cigar) / words of b before this pair
-    DeviceBuf d_scratch_gran;
-    DeviceBuf d_ckpt, d_cigar, d_cigar_len, d_costs, d_scratch_v, d_scratch_vals, d_tjobs, d_cig_src_off, d_packed;
-    hipEvent_t ev2 = nullptr;
-    uint8_t* h_text = nullptr;  // pinned host buffer for the packed CIGAR text of one chunk
-    size_t h_text_size = 0;
-    // pa_batch_align_view: the texts stay in h_text (one chunk) and the caller gets pointers + lengths; strings that come from elsewhere
-    // (the host engine, the second round, the small-batch route, several chunks) are malloc'ed as usual and owned by the plan
-    bool view_mode = false;
-    std::vector<uint32_t> view_len;
-    std::vector<char*> view_owned;
-    bool in_text(const char* q) const { return h_text && (const uint8_t*)q >= h_text && (const uint8_t*)q < h_text + h_text_size; }
-    void free_view_owned() {
-        for (char* q : view_owned) std::free(q);
-        view_owned.clear();
-    }
-    // pa_batch_align can work in CHUNKS of the (heaviest-first) order, each on a stream of its own: forward pass (batched A*PA2),
-    // traceback, CIGAR text and its copy-out of different chunks overlap (one chunk by default: see the chunk plan in batch_create)
-    static constexpr int kMaxChunks = 8;
-    std::vector<int32_t> order_host;   // position -> pair (A*PA2: heaviest first; else the identity)
-    std::vector<int32_t> torder_host;  // the same chunks with the pairs of a chunk in index order: what the traceback and the text kernels walk
-                                       // (neighbouring pairs of the input in one workgroup: C4 traceback 10.0 against 10.9 ms in the forward order)
-    DeviceBuf d_torder;
-    DeviceBuf d_tlist;     // the traceback's own order: each chunk's pairs by descending cost (trace_order_kernel)
-    uint32_t max_nm = 1;   // the longest |a| + |b| of the batch: no cost is larger
-    std::vector<size_t> chunk_lo;      // chunk c = positions [chunk_lo[c], chunk_lo[c + 1])
-    std::vector<uint64_t> chunk_base;  // byte offset of chunk c's region of d_packed
-    hipStream_t cstream[kMaxChunks] = {};
-    hipEvent_t ev_pre = nullptr, evF0[kMaxChunks] = {}, evF1[kMaxChunks] = {}, evT1[kMaxChunks] = {};
-    DeviceBuf d_cmeta, d_tlen_pos, d_dst_pos;  // d_cmeta: u64 text totals [kMaxChunks], then u32 tickets [kMaxChunks]
-    uint8_t* h_meta = nullptr;                  // pinned: u64 totals [kMaxChunks], u32 tlen [pairs], u64 dst [pairs]
-    size_t h_meta_size = 0;
-    // A*PA2 mode (pa_batch_create_params): one wavefront runs the whole band search of a pair (apa2_kernel.hpp); d_ckpt is the
-    // pairs' column store, the traceback reads the blocks of the successful pass from it
-    bool astar = false;
-    // the block-column store is band-proportional: slot width per pair in words (sweep_logic.hpp SlotGeom); a pair whose band leaves its
-    // window is aligned again with full-height slots (second round of pa_batch_align)
-    std::vector<uint32_t> win_words, slot_ratio;
-    int window_override = -1;  // -1: the policy below; 0: full columns; > 0: that many words
-    size_t window_retries = 0;
-    double window_retry_peak_bytes = 0;  // the largest full-height block-column store a second round of this plan held at a time
-    pa_astarpa2_params aparams_c{};
-    apa2::SearchParams sp{};
-    DeviceBuf d_rec, d_results, d_pjobs, d_order, d_tstats, d_sh;
-    DeviceBuf d_sketch;  // [pairs] the divergence sketch (sketch_unit.hip), kept so that it is released with the batch's other buffers
-    DeviceBuf d_rdv;  // 8 x u64: the rendezvous of half-wave blocks in the last forward pass (strips run fused, served by a partner, alone, withdrawn)
-    // ... the whole family (pa_batch_create_params with GCSH / pruning / incremental doubling: apa2_full_kernel.hpp)
-    bool astar_full = false;
-    apa2::FullParams fsp{};
-    DeviceBuf d_fjobs, d_jh, d_hrow, d_mi, d_mj, d_active, d_win, d_win0, d_lrec, d_cell, d_probe;
-    size_t full_matches = 0, full_seeds = 0;
-    double full_build_ms = 0;  // host time spent on the matches of the heuristic (reporting; 0 when the GPU finds them)
-    // the matches found on the GPU (gcsh_build_kernel.hpp), inside every pa_batch_align / pa_batch_run
-    bool device_build = false;
-    DeviceBuf d_bjobs, d_bscratch, d_bstatus, d_bticket;
-    hipEvent_t evB0 = nullptr, evB1 = nullptr;
-    std::vector<pa_astarpa2_stats> pair_stats;  // of the last pa_batch_align
-    double apa2_strip_instr = 0;  // modelled VALU instructions of the DP strips of the last pa_batch_align (reporting)
-    double cells = 0, word_updates = 0, algo_bytes = 0;
-    hipStream_t stream = nullptr;
-    // INVARIANT (round 6, replaces a flag nothing ever set): everything that reads or writes this batch's buffers is queued on `stream` or on
-    // one of cstream[] -- never on the null stream or a stream of another object.  The destructor relies on it: it waits for these streams
-    // only and hands the buffers to the cache, where another thread may take them at once.  PA_POISON_ALLOC runs keep it honest.
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~pa_batch() {
-        const bool prof = align_profile();
-        const auto t0 = std::chrono::steady_clock::now();
-        if (prof) {  // (diagnostics: which of the batch's streams is still busy)
-            std::fprintf(stderr, "[pa_batch_destroy] busy: batch stream %d", stream && hipStreamQuery(stream) == hipErrorNotReady);
-            for (int c = 0; c < kMaxChunks; ++c)
-                if (cstream[c]) std::fprintf(stderr, " chunk%d %d", c, hipStreamQuery(cstream[c]) == hipErrorNotReady);
-            std::fprintf(stderr, "\n");
-            if (stream) (void)hipStreamSynchronize(stream);
-            std::fprintf(stderr, "[pa_batch_destroy] batch stream wait %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        }
-        // everything that reads or writes this batch's buffers was queued on its own streams: wait for those, not for the device
-        bool waited = true;
-        if (stream) waited = hipStreamSynchronize(stream) == hipSuccess && waited;
-        for (int c = 0; c < kMaxChunks; ++c)
-            if (cstream[c]) waited = hipStreamSynchronize(cstream[c]) == hipSuccess && waited;
-        if (waited) release_scope_begin_waited();
-        else release_scope_begin();  // (a stream whose wait failed: wait for the whole device before the buffers go anywhere)
-        if (prof) std::fprintf(stderr, "[pa_batch_destroy] device wait %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (ev2) (void)hipEventDestroy(ev2);
-        free_view_owned();
-        pinned_give(h_text, h_text_size);
-        pinned_give(h_meta, h_meta_size);
-        if (ev_pre) (void)hipEventDestroy(ev_pre);
-        if (evB0) (void)hipEventDestroy(evB0);
-        if (evB1) (void)hipEventDestroy(evB1);
-        for (int c = 0; c < kMaxChunks; ++c) {
-            if (evF0[c]) (void)hipEventDestroy(evF0[c]);
-            if (evF1[c]) (void)hipEventDestroy(evF1[c]);
-            if (evT1[c]) (void)hipEventDestroy(evT1[c]);
-            if (waited) stream_give(cstream[c], d_a.device);
-            else if (cstream[c]) (void)hipStreamDestroy(cstream[c]);  // a stream whose synchronize failed is not pooled
-        }
-        if (prof) std::fprintf(stderr, "[pa_batch_destroy] events, streams, pinned %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        if (waited) bstream_give(stream, d_a.device);  // (the batch waited for its streams above: nothing of it is queued on the stream any more)
-        else if (stream) (void)hipStreamDestroy(stream);
-        slice::destroy(sliced);
-    }
-};
-
 // Pair i's two sequences, back from the device (an empty one is not copied).
-static bool fetch_pair(const pa_batch* p, size_t i, std::vector<uint8_t>& a, std::vector<uint8_t>& b) {
+bool fetch_pair(const pa_batch* p, size_t i, std::vector<uint8_t>& a, std::vector<uint8_t>& b) {
     a.resize(p->n[i]);
     b.resize(p->m[i]);
     return (!p->n[i] || hip_ok(hipMemcpy(a.data(), p->d_a.as<uint8_t>() + p->a_off[i], p->n[i], hipMemcpyDeviceToHost), "D2H a")) &&
@@ -504,393 +379,6 @@ static bool apa2_full_supported(const engine::AstarPa2Params& p) {
     return p.domain == DomainKind::Astar && p.block_width == sweep::kBlockW && p.front.sparse &&
            (p.doubling == DoublingKind::BandDoubling || p.doubling == DoublingKind::LinearSearch) &&
            (!p.front.dt_trace || (p.front.max_g >= 1 && p.front.max_g <= kDtMaxG));
-}
-
-// The start order of the batched band search: the most expensive pairs first (sketch_unit.hip has the why).  Expected work of a pair:
-// its length times the band its final pass needs, band ~ estimated cost = e (n + m) / 2 with e from the sketch ((1 - e)^16 = found / 64).
-// PA_APA2_ORDER_INPUT keeps the caller's order, PA_APA2_ORDER_LENGTH the order of the lengths (round 4) -- experiments and tests.
-static bool astar_start_order(pa_batch* p, std::vector<int32_t>& order) {
-    const size_t P = p->pairs;
-    order.resize(P);
-    for (size_t i = 0; i < P; ++i) order[i] = (int32_t)i;
-    if (getenv("PA_APA2_ORDER_INPUT") || P < 2) return true;
-    PhaseClock clock("pa_batch_create");
-    static_assert(sizeof(apa2::SketchDesc) == sizeof(PairDesc), "the sketch reads the batch's pair descriptors");
-    std::vector<uint8_t> found(P, 64);
-    const bool sketch = !getenv("PA_APA2_ORDER_LENGTH");
-    if (sketch) {
-        if (!p->d_sketch.alloc(P) ||
-            !hip_ok(apa2::launch_sketch_kernel(p->stream, p->d_a.as<uint8_t>(), p->d_b.as<uint8_t>(), (const apa2::SketchDesc*)p->d_desc.ptr, (int)P, p->d_sketch.as<uint8_t>()),
-                    "sketch_kernel launch") ||
-            !hip_ok(hipMemcpyAsync(found.data(), p->d_sketch.ptr, P, hipMemcpyDeviceToHost, p->stream), "D2H sketch") || !hip_ok(hipStreamSynchronize(p->stream), "sync"))
-            return false;
-    }
-    const double sketch_ms = clock.lap();
-    // e from found / 64 = (1 - e)^16, by table (nothing found: as if half a sample had been)
-    double e_of[65];
-    for (int f = 0; f <= 64; ++f) e_of[f] = 1.0 - std::pow(std::max(0.5, (double)f) / 64.0, 1.0 / 16.0);
-    // descending by the expected work, ties in the caller's order: one sort of 64-bit words (float bits of a positive key order like integers)
-    std::vector<uint64_t> keyed(P);
-    for (size_t i = 0; i < P; ++i) {
-        const float len = (float)(p->n[i] + p->m[i]);
-        const float key = sketch ? len * ((float)e_of[std::min<int>(found[i], 64)] * len * 0.5f + 128.0f) : len;
-        uint32_t bits;
-        std::memcpy(&bits, &key, 4);
-        keyed[i] = ((uint64_t)bits << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)i);
-    }
-    std::sort(keyed.begin(), keyed.end(), std::greater<uint64_t>());
-    for (size_t i = 0; i < P; ++i) order[i] = (int32_t)(0xFFFFFFFFu - (uint32_t)(keyed[i] & 0xFFFFFFFFu));
-    if (align_profile()) std::fprintf(stderr, "[%s]   start order: sketch %.3f ms, sort %.3f ms\n", clock.tag, sketch_ms, clock.lap());
-    return true;
-}
-
-// The per-pair descriptors of the A*PA2 mode; completes the trace jobs (banded blocks, statistics).
-static bool astar_jobs(pa_batch* p, const uint8_t* const* a, const uint8_t* const* b, std::vector<TraceJob>& tjobs) {
-    const engine::AstarPa2Params ap = engine::params_from_c(p->aparams_c);
-    const size_t P = p->pairs;
-    p->sp.heur = ap.heuristic == engine::HeuristicKind::Gap ? sweep::kHeurGap : (ap.heuristic == engine::HeuristicKind::SH ? sweep::kHeurSH : sweep::kHeurNone);
-    p->sp.sparse_h = ap.sparse_h ? 1 : 0;
-    p->sp.doubling = ap.doubling == engine::DoublingKind::LinearSearch ? apa2::kDoublingLinear : apa2::kDoublingBand;
-    p->sp.start = (int32_t)ap.start;
-    p->sp.factor = ap.factor;
-    p->sp.delta = (int32_t)ap.delta;
-    std::vector<size_t> rec_off(P), sh_off(P);
-    size_t tr = 0, tsh = 0;
-    for (size_t i = 0; i < P; ++i) {
-        rec_off[i] = tr;
-        tr += (p->n[i] + 255) / 256 + 2;
-        sh_off[i] = tsh;
-        if (p->sp.heur == sweep::kHeurSH) tsh += p->n[i] + 1;
-    }
-    if (!p->d_rec.alloc(std::max<size_t>(tr, 1) * sizeof(sweep::BlockRec)) || !p->d_results.alloc(std::max<size_t>(P, 1) * sizeof(apa2::PairResult)) ||
-        !p->d_pjobs.alloc(std::max<size_t>(P, 1) * sizeof(apa2::PairJob)) || !p->d_order.alloc(std::max<size_t>(P, 1) * 4) ||
-        !p->d_tstats.alloc(std::max<size_t>(P, 1) * 32) || !p->d_sh.alloc(std::max<size_t>(tsh, 1) * 4))
-        return false;
-    if (p->sp.heur == sweep::kHeurSH && tsh) {  // SeedHeuristicH (pa-heuristic sh.rs:47-106): host-built per-column table
-        std::vector<int32_t> sh(tsh);
-        for (size_t i = 0; i < P; ++i) {
-            engine::SeedHeuristicH h(a[i], (engine::I)p->n[i], b[i], (engine::I)p->m[i], ap.heuristic_k, (int)ap.heuristic_p);
-            std::copy(h.h_by_i.begin(), h.h_by_i.end(), sh.begin() + sh_off[i]);
-        }
-        if (!hip_ok(hipMemcpy(p->d_sh.ptr, sh.data(), tsh * 4, hipMemcpyHostToDevice), "H2D sh")) return false;
-    }
-    std::vector<apa2::PairJob> pj(P);
-    std::vector<int32_t> order(P);
-    for (size_t i = 0; i < P; ++i) {
-        const size_t w = (p->m[i] + 63) / 64, nblk = (p->n[i] + 255) / 256;
-        apa2::PairJob& j = pj[i];
-        j.a_codes = p->d_codes.as<uint32_t>() + p->code_off[i];
-        j.b_prof = p->d_prof.as<uint32_t>() + p->prof_off[i] * 4;
-        j.rec = p->d_rec.as<sweep::BlockRec>() + rec_off[i];
-        j.col = p->d_ckpt.as<uint32_t>() + p->ckpt_off[i];
-        j.col_stride = (int64_t)p->win_words[i];
-        j.slot_ratio = p->slot_ratio[i];
-        j.pad0 = 0;
-        j.sh_h = p->sp.heur == sweep::kHeurSH ? p->d_sh.as<int32_t>() + sh_off[i] : nullptr;
-        j.gran = p->d_scratch_gran.as<uint64_t>() + i * 16;
-        j.sum = p->d_sums.as<int32_t>() + i;
-        j.result = p->d_results.as<apa2::PairResult>() + i;
-        j.n = (int32_t)p->n[i];
-        j.m = (int32_t)p->m[i];
-        TraceJob& t = tjobs[i];
-        t.rec = j.rec;
-        t.res = j.result;
-        t.tstats = p->d_tstats.as<uint32_t>() + 8 * i;
-        t.final_v = p->d_ckpt.as<uint32_t>() + p->ckpt_off[i] + nblk * (size_t)p->win_words[i] * 4;  // (unused: banded blocks go through the slots)
-        t.win = (int32_t)p->win_words[i];
-        t.slot_ratio = p->slot_ratio[i];
-        (void)w;
-        order[i] = (int32_t)i;
-    }
-    if (!astar_start_order(p, order)) return false;  // the most expensive pairs first
-    p->order_host = order;
-    if (P && (!hip_ok(hipMemcpy(p->d_pjobs.ptr, pj.data(), P * sizeof(apa2::PairJob), hipMemcpyHostToDevice), "H2D pair jobs") ||
-              !hip_ok(hipMemcpy(p->d_order.ptr, order.data(), P * 4, hipMemcpyHostToDevice), "H2D order")))
-        return false;
-    return true;
-}
-
-// Words per slot of a pair's block-column store.  Measured on the CPU-kernel engine (round 4): `simple` on 100 kbp at 5 % ends with bands of
-// 133 words within 69 words of the main diagonal, 10 kbp at 15 % with 37 within 20; `full` (GCSH) on 100 kbp at 5 % with 12 within 7.
-// The windows below hold those with room to spare; what does not fit (15 % on 100 kbp: 260 words) is aligned again with full columns.
-static size_t window_words(size_t n, size_t m, bool gcsh, int override_) {
-    const size_t wtot = std::max<size_t>((m + 63) / 64, 1);
-    static const int env = getenv("PA_APA2_WINDOW") ? atoi(getenv("PA_APA2_WINDOW")) : -1;
-    const int o = override_ >= 0 ? override_ : env;
-    if (o == 0) return wtot;
-    size_t W = o > 0 ? (size_t)o : (gcsh ? 64 : ((2 * ((std::max(n, m) + 1249) / 1250) + 32 + 7) & ~size_t(7)));
-    return std::min(W, wtot);
-}
-
-// Host threads for per-pair host work of a batch (the matches of GCSH, the SH tables): as many as the process may run on.
-static unsigned host_threads() {
-    static const unsigned n = [] {
-        if (const char* e = getenv("PA_HOST_THREADS")) return (unsigned)std::max(1, atoi(e));
-        unsigned c = 0;
-#if defined(__linux__)
-        cpu_set_t set;
-        CPU_ZERO(&set);
-        if (sched_getaffinity(0, sizeof set, &set) == 0) c = (unsigned)CPU_COUNT(&set);
-#endif
-        if (c == 0) c = std::thread::hardware_concurrency();
-        return std::max(1u, std::min(c, 64u));
-    }();
-    return n;
-}
-template <class F>
-static void parallel_pairs(size_t P, F&& f) {
-    const unsigned nt = (unsigned)std::min<size_t>(host_threads(), std::max<size_t>(P, 1));
-    if (nt <= 1) {
-        for (size_t i = 0; i < P; ++i) f(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; ++t)
-        th.emplace_back([&] {
-            for (size_t i = next.fetch_add(1); i < P; i = next.fetch_add(1)) f(i);
-        });
-    for (auto& t : th) t.join();
-}
-
-// The per-pair descriptors of the whole-family mode (apa2_full_kernel.hpp); completes the trace jobs like astar_jobs.
-// The matches of GCSH (seeds, exact k-mer matches in the reference's push order, the transform filter, local pruning p:
-// csrc/gcsh.hpp) are found on host threads; the contours are derived on the device.
-static bool astar_full_jobs(pa_batch* p, const uint8_t* const* a, const uint8_t* const* b, std::vector<TraceJob>& tjobs) {
-    const engine::AstarPa2Params ap = engine::params_from_c(p->aparams_c);
-    const size_t P = p->pairs;
-    const bool cprof = align_profile();  // diagnostics: where the creation time goes
-    auto cnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double c_mark = cnow();
-    auto cmark = [&](const char* what) {
-        if (!cprof) return;
-        const double t = cnow();
-        std::fprintf(stderr, "[pa_batch_create]   full: %-22s %8.3f ms\n", what, t - c_mark);
-        c_mark = t;
-    };
-    p->sp.heur = ap.heuristic == engine::HeuristicKind::Gap ? sweep::kHeurGap : (ap.heuristic == engine::HeuristicKind::SH ? sweep::kHeurSH : sweep::kHeurNone);
-    p->sp.sparse_h = ap.sparse_h ? 1 : 0;
-    p->sp.doubling = ap.doubling == engine::DoublingKind::LinearSearch ? apa2::kDoublingLinear : apa2::kDoublingBand;
-    p->sp.start = (int32_t)ap.start;
-    p->sp.factor = ap.factor;
-    p->sp.delta = (int32_t)ap.delta;
-    p->fsp.sparse_h = ap.sparse_h ? 1 : 0;
-    p->fsp.prune = ap.prune ? 1 : 0;
-    p->fsp.incremental = ap.front.incremental_doubling ? 1 : 0;
-    p->fsp.doubling = ap.doubling == engine::DoublingKind::LinearSearch ? 2 : 1;
-    p->fsp.start = (int32_t)ap.start;
-    p->fsp.factor = ap.factor;
-    p->fsp.delta = (int32_t)ap.delta;
-    const bool gcsh = ap.heuristic == engine::HeuristicKind::GCSH, sh = ap.heuristic == engine::HeuristicKind::SH;
-    const int32_t hk = ap.heuristic_k < 1 ? 1 : ap.heuristic_k;
-    std::vector<size_t> rec_off(P), sh_off(P), col_off(P), seed_off(P), match_off(P + 1, 0);
-    size_t tr = 0, tsh = 0, tn = 0, tseeds = 0;
-    for (size_t i = 0; i < P; ++i) {
-        rec_off[i] = tr;
-        tr += (p->n[i] + 255) / 256 + 2;
-        sh_off[i] = tsh;
-        if (sh) tsh += p->n[i] + 1;
-        col_off[i] = tn;
-        tn += (p->n[i] + 63) & ~size_t(63);
-        seed_off[i] = tseeds;
-        if (gcsh) tseeds += p->n[i] >= (size_t)hk ? (p->n[i] - hk) / hk + 1 : 0;
-    }
-    // The matches of GCSH are found on the GPU, once, at the end of this function (gcsh_build_kernel.hpp), when the look-ahead of local
-    // pruning fits its LDS arrays; PA_GCSH_HOST_BUILD=1 finds them on host threads at creation instead (tests compare the two).
-    static const bool host_build_env = getenv("PA_GCSH_HOST_BUILD") != nullptr && getenv("PA_GCSH_HOST_BUILD")[0] != '0';
-    p->device_build = gcsh && !host_build_env && ap.heuristic_p >= 0 && ap.heuristic_p <= apa2::kBuildMaxP && hk <= 31;
-    // ---- host threads: the matches (GCSH, unless the GPU finds them) / the per-column table (SH) of every pair ----
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<std::vector<int32_t>> pmi(gcsh ? P : 0), pmj(gcsh ? P : 0);
-    std::vector<apa2::GcshSeedWindow> win(p->device_build ? 0 : tseeds);
-    std::vector<int32_t> shv(tsh);
-    std::atomic<bool> bad_base{false};
-    if ((gcsh && !p->device_build) || sh)
-        parallel_pairs(P, [&](size_t i) {
-            const engine::I n = (engine::I)p->n[i], m = (engine::I)p->m[i];
-            if (n == 0 || m == 0) return;
-            if (sh) {
-                engine::SeedHeuristicH h(a[i], n, b[i], m, ap.heuristic_k, (int)ap.heuristic_p);
-                std::copy(h.h_by_i.begin(), h.h_by_i.end(), shv.begin() + (long)sh_off[i]);
-                return;
-            }
-            engine::GcshHeuristic gh(a[i], n, b[i], m, ap.heuristic_k, (int)ap.heuristic_p, ap.prune, false);
-            pmi[i].reserve(gh.by_start.size());
-            pmj[i].reserve(gh.by_start.size());
-            for (const auto& mt : gh.by_start) {
-                pmi[i].push_back(mt.i);
-                pmj[i].push_back(mt.j);
-            }
-            for (size_t s = 0; s < gh.active_range.size(); ++s)
-                win[seed_off[i] + s] = apa2::GcshSeedWindow{(int32_t)gh.active_range[s].b0, (int32_t)gh.active_range[s].b1, -1, 0};
-        });
-    size_t tm = 0;
-    std::vector<size_t> cap(P, 0), tsz(P, 0);
-    size_t ttab = 0;
-    for (size_t i = 0; i < P; ++i) {
-        match_off[i] = tm;
-        if (gcsh && !p->device_build) tm += pmi[i].size();
-        if (p->device_build) {
-            // room for the candidates of a pair: every seed once and half of them again, plus 2048 (a pair that needs more -- a
-            // repeat-rich sequence -- is flagged by the kernel and goes to the host engine)
-            const size_t ns = p->n[i] >= (size_t)hk ? (p->n[i] - hk) / hk + 1 : 0;
-            cap[i] = ns + ns / 2 + 2048;
-            size_t t2 = 64;
-            while (t2 < 2 * ns + 1) t2 *= 2;
-            tsz[i] = t2;
-            ttab += t2;
-            tm += cap[i];
-        }
-    }
-    match_off[P] = tm;
-    p->full_matches = tm;
-    p->full_seeds = tseeds;
-    p->full_build_ms = p->device_build ? 0.0 : std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    cmark("host tables / sizes");
-    if (!p->d_rec.alloc(std::max<size_t>(tr, 1) * sizeof(sweep::BlockRec)) || !p->d_jh.alloc(std::max<size_t>(tr, 1) * 4) ||
-        !p->d_results.alloc(std::max<size_t>(P, 1) * sizeof(apa2::PairResult)) || !p->d_fjobs.alloc(std::max<size_t>(P, 1) * sizeof(apa2::FullJob)) ||
-        !p->d_order.alloc(std::max<size_t>(P, 1) * 4) || !p->d_tstats.alloc(std::max<size_t>(P, 1) * 32) || !p->d_sh.alloc(std::max<size_t>(tsh, 1) * 4) ||
-        !p->d_hrow.alloc(std::max<size_t>(tn, 64)) || !p->d_mi.alloc(std::max<size_t>(tm, 1) * 4) || !p->d_mj.alloc(std::max<size_t>(tm, 1) * 4) ||
-        !p->d_active.alloc(std::max<size_t>(tm, 64)) || !p->d_win.alloc(std::max<size_t>(tseeds, 1) * sizeof(apa2::GcshSeedWindow)) ||
-        !p->d_win0.alloc(std::max<size_t>(tseeds, 1) * sizeof(apa2::GcshSeedWindow)) ||
-        !p->d_lrec.alloc((tm + 2 * std::max<size_t>(P, 1)) * sizeof(apa2::GcshCell)) || !p->d_cell.alloc(std::max<size_t>(tm, 1) * sizeof(apa2::GcshCell)) ||
-        !p->d_probe.alloc(128 + 8 * std::max<size_t>(P, 1)))  // (16 counters, then per pair: HW_ID / XCC_ID and the ticks of its band search; PA_APA2_PROBE_STATS)
-        return false;
-    cmark("device buffers");
-    if (tsh && !hip_ok(hipMemcpy(p->d_sh.ptr, shv.data(), tsh * 4, hipMemcpyHostToDevice), "H2D sh")) return false;
-    if (tm && !p->device_build) {  // (the GPU's builder writes d_mi / d_mj itself: nothing to upload -- until round 4 this sent 2 x 4 tm bytes of zeros)
-        std::vector<int32_t> mi(tm), mj(tm);
-        for (size_t i = 0; i < P; ++i) {
-            std::copy(pmi[i].begin(), pmi[i].end(), mi.begin() + (long)match_off[i]);
-            std::copy(pmj[i].begin(), pmj[i].end(), mj.begin() + (long)match_off[i]);
-        }
-        if (!hip_ok(hipMemcpy(p->d_mi.ptr, mi.data(), tm * 4, hipMemcpyHostToDevice), "H2D matches") ||
-            !hip_ok(hipMemcpy(p->d_mj.ptr, mj.data(), tm * 4, hipMemcpyHostToDevice), "H2D matches"))
-            return false;
-    }
-    if (tseeds && !p->device_build && !hip_ok(hipMemcpy(p->d_win0.ptr, win.data(), tseeds * sizeof(apa2::GcshSeedWindow), hipMemcpyHostToDevice), "H2D seed windows")) return false;
-    std::vector<apa2::GcshBuildJob> bj(p->device_build ? P : 0);
-    if (p->device_build) {
-        // scratch of the build kernel, one slice per pair: u32 keys / next_same / cnt / fill per seed, the table, five ints and two bytes
-        // per candidate slot
-        const size_t words = 4 * tseeds + P + ttab + 4 * tm, bytes = words * 4 + 2 * tm + 64;
-        if (!p->d_bscratch.alloc(bytes) || !p->d_bjobs.alloc(std::max<size_t>(P, 1) * sizeof(apa2::GcshBuildJob)) || !p->d_bstatus.alloc(std::max<size_t>(P, 1) * 4) ||
-            !p->d_bticket.alloc(64) || !hip_ok(hipEventCreate(&p->evB0), "event") || !hip_ok(hipEventCreate(&p->evB1), "event"))
-            return false;
-        cmark("  build: buffers");
-        int32_t* w32 = p->d_bscratch.as<int32_t>();
-        uint8_t* w8 = (uint8_t*)(w32 + words);
-        size_t o32 = 0, o8 = 0;
-        for (size_t i = 0; i < P; ++i) {
-            const size_t ns = p->n[i] >= (size_t)hk ? (p->n[i] - hk) / hk + 1 : 0;
-            apa2::GcshBuildJob& x = bj[i];
-            std::memset(&x, 0, sizeof x);
-            x.a = p->d_a.as<uint8_t>() + p->a_off[i];
-            x.b = p->d_b.as<uint8_t>() + p->b_off[i];
-            x.keys = (uint32_t*)(w32 + o32);
-            o32 += ns;
-            x.next_same = w32 + o32;
-            o32 += ns;
-            x.cnt = w32 + o32;
-            o32 += ns + 1;
-            x.fill = w32 + o32;
-            o32 += ns;
-            x.slot = w32 + o32;
-            o32 += tsz[i];
-            x.tmp_s = w32 + o32;
-            o32 += cap[i];
-            x.tmp_j = w32 + o32;
-            o32 += cap[i];
-            x.gpos = w32 + o32;
-            o32 += cap[i];
-            x.cj = w32 + o32;
-            o32 += cap[i];
-            x.flag = w8 + o8;
-            o8 += cap[i];
-            x.keptg = w8 + o8;
-            o8 += cap[i];
-            x.mi = p->d_mi.as<int32_t>() + match_off[i];
-            x.mj = p->d_mj.as<int32_t>() + match_off[i];
-            x.win0 = p->d_win0.as<apa2::GcshSeedWindow>() + seed_off[i];
-            x.nmatch_out = &p->d_fjobs.as<apa2::FullJob>()[i].g.nmatch;
-            x.status = p->d_bstatus.as<uint32_t>() + i;
-            x.n = (int32_t)p->n[i];
-            x.m = (int32_t)p->m[i];
-            x.k = hk;
-            x.p = (int32_t)ap.heuristic_p;
-            x.nseeds = (int32_t)ns;
-            x.tsize = (int32_t)tsz[i];
-            x.cap = (int32_t)cap[i];
-        }
-        cmark("  build: descriptors");
-        if (P && !hip_ok(hipMemcpy(p->d_bjobs.ptr, bj.data(), P * sizeof(apa2::GcshBuildJob), hipMemcpyHostToDevice), "H2D build jobs")) return false;
-        cmark("  build: H2D");
-    }
-    cmark("build scratch + jobs");
-    const bool launch_build = p->device_build && P;
-    std::vector<apa2::FullJob> fj(P);
-    std::vector<int32_t> order(P);
-    for (size_t i = 0; i < P; ++i) {
-        const size_t w = (p->m[i] + 63) / 64, nblk = (p->n[i] + 255) / 256;
-        apa2::FullJob& j = fj[i];
-        std::memset(&j, 0, sizeof j);
-        j.a_codes = p->d_codes.as<uint32_t>() + p->code_off[i];
-        j.b_prof = p->d_prof.as<uint32_t>() + p->prof_off[i] * 4;
-        j.rec = p->d_rec.as<sweep::BlockRec>() + rec_off[i];
-        j.jh = p->d_jh.as<int32_t>() + rec_off[i];
-        j.col = p->d_ckpt.as<uint32_t>() + p->ckpt_off[i];
-        j.col_stride = (int64_t)p->win_words[i];
-        j.slot_ratio = p->slot_ratio[i];
-        j.hrow = p->d_hrow.as<uint8_t>() + col_off[i];
-        j.sh_h = sh ? p->d_sh.as<int32_t>() + sh_off[i] : nullptr;
-        j.gran = p->d_scratch_gran.as<uint64_t>() + i * 16;
-        j.sum = p->d_sums.as<int32_t>() + i;
-        j.result = p->d_results.as<apa2::PairResult>() + i;
-        j.n = (int32_t)p->n[i];
-        j.m = (int32_t)p->m[i];
-        j.heur = (int32_t)ap.heuristic;
-        if (gcsh) {
-            apa2::GcshDev& g = j.g;
-            g.mi = p->d_mi.as<int32_t>() + match_off[i];
-            g.mj = p->d_mj.as<int32_t>() + match_off[i];
-            g.active = p->d_active.as<uint8_t>() + match_off[i];
-            g.win = p->d_win.as<apa2::GcshSeedWindow>() + seed_off[i];
-            g.lrec = p->d_lrec.as<apa2::GcshCell>() + match_off[i] + 2 * i;
-            g.cell = p->d_cell.as<apa2::GcshCell>() + match_off[i];
-            g.nmatch = (int32_t)(match_off[i + 1] - match_off[i]);
-            g.nlayers = 1;
-            g.n = j.n;
-            g.m = j.m;
-            g.k = hk;
-            g.nseeds = j.n >= hk ? (j.n - hk) / hk + 1 : 0;
-            g.prune = ap.prune ? 1 : 0;
-        }
-        TraceJob& t = tjobs[i];
-        t.rec = j.rec;
-        t.res = j.result;
-        t.tstats = p->d_tstats.as<uint32_t>() + 8 * i;
-        t.final_v = p->d_ckpt.as<uint32_t>() + p->ckpt_off[i] + nblk * (size_t)p->win_words[i] * 4;  // (unused: banded blocks go through the slots)
-        t.win = (int32_t)p->win_words[i];
-        t.slot_ratio = p->slot_ratio[i];
-        (void)w;
-        order[i] = (int32_t)i;
-    }
-    if (!astar_start_order(p, order)) return false;  // the most expensive pairs first
-    p->order_host = order;
-    if (P && (!hip_ok(hipMemcpy(p->d_fjobs.ptr, fj.data(), P * sizeof(apa2::FullJob), hipMemcpyHostToDevice), "H2D pair jobs") ||
-              !hip_ok(hipMemcpy(p->d_order.ptr, order.data(), P * 4, hipMemcpyHostToDevice), "H2D order")))
-        return false;
-    cmark("pair jobs + order");
-    if (launch_build) {
-        // The matches of GCSH are part of the batch like the sequences they are derived from: found here, once, by the GPU (one wavefront
-        // per pair, 12.8 KB of LDS each: twelve to a CU), on the batch's stream -- the first alignment call queues behind it.
-        const int cus = device_cus();
-        static const int per_cu = getenv("PA_BUILD_WAVES_PER_CU") ? std::max(1, atoi(getenv("PA_BUILD_WAVES_PER_CU"))) : 12;
-        const int grid = (int)std::min<size_t>(P, (size_t)cus * (size_t)per_cu);
-        if (!hip_ok(hipMemsetAsync(p->d_bticket.ptr, 0, 64, p->stream), "memset") || !hip_ok(hipEventRecord(p->evB0, p->stream), "event")) return false;
-        if (!hip_ok(apa2::launch_gcsh_build_kernel(grid, p->stream, p->d_bjobs.as<apa2::GcshBuildJob>(), (int)P, p->d_bticket.as<uint32_t>()), "gcsh_build_kernel launch") || !hip_ok(hipEventRecord(p->evB1, p->stream), "event")) return false;
-    }
-    return true;
 }
 
 // The caller's pairs, as every pa_batch_create* entry point receives them.
@@ -1156,6 +644,17 @@ static bool upload_first_and_desc(CreateRun& cr, const std::vector<int32_t>& fir
     return hip_ok(hipStreamSynchronize(p->stream), "sync");  // desc is a local
 }
 
+void fill_trace_job(std::vector<TraceJob>& tjobs, const pa_batch* p, size_t i, const sweep::BlockRec* rec, const apa2::PairResult* result) {
+    TraceJob& t = tjobs[i];
+    const size_t nblk = (p->n[i] + 255) / 256;
+    t.rec = rec;
+    t.res = result;
+    t.tstats = p->d_tstats.as<uint32_t>() + 8 * i;
+    t.final_v = p->d_ckpt.as<uint32_t>() + p->ckpt_off[i] + nblk * (size_t)p->win_words[i] * 4;  // (unused: banded blocks go through the slots)
+    t.win = (int32_t)p->win_words[i];
+    t.slot_ratio = p->slot_ratio[i];
+}
+
 // The traceback's per-pair jobs; A*PA2 completes them (and decides the start order), a plain traced batch takes the pairs as they come.
 static bool make_trace_jobs(CreateRun& cr, std::vector<TraceJob>& tjobs, std::vector<uint64_t>& src_off) {
     pa_batch* p = cr.p;
@@ -1186,7 +685,7 @@ static bool make_trace_jobs(CreateRun& cr, std::vector<TraceJob>& tjobs, std::ve
         t.slot_ratio = 0;
         src_off[i] = p->cigar_off[i];
     }
-    if (cr.astar) return p->astar_full ? astar_full_jobs(p, cr.in.a, cr.in.b, tjobs) : astar_jobs(p, cr.in.a, cr.in.b, tjobs);
+    if (cr.astar) return apa2_make_jobs(p, cr.in.a, cr.in.b, tjobs);  // apa2_jobs_unit.hip
     // (the plain traced batch: chunks of the pairs as they come)
     p->order_host.resize(pairs);
     for (size_t i = 0; i < pairs; ++i) p->order_host[i] = (int32_t)i;
@@ -1416,6 +915,33 @@ static int launch_astar(pa_batch* p, hipStream_t s, size_t lo, size_t cnt, uint3
     return hip_ok(e, "apa2_kernel launch") ? 0 : PA_E_HIP;
 }
 
+// PA_APA2_DEBUG (diagnostics): the forward pass alone with a host-mapped debug block, its progress markers once a second and the first
+// results on stderr; a kernel that has not finished after eight seconds ends the process.
+static int launch_astar_watched(pa_batch* p, hipStream_t s) {
+    void* hp = nullptr;
+    if (!hip_ok(hipHostMalloc(&hp, 256, hipHostMallocMapped), "hipHostMalloc(debug)")) return PA_E_HIP;
+    std::memset(hp, 0, 256);
+    uint32_t* dbg = (uint32_t*)hp;
+    if (const int rc = launch_astar(p, s, 0, p->pairs, p->d_misc.as<uint32_t>(), dbg)) return rc;
+    std::fprintf(stderr, "[apa2] forward launched: pairs %zu\n", p->pairs);
+    for (int sec = 0; sec < 8 && hipStreamQuery(s) == hipErrorNotReady; ++sec) {
+        const volatile uint32_t* d = dbg;
+        std::fprintf(stderr, "[apa2] t=%ds stage %u f_max %d tries %u block %u js %d je %d strip %u pair %u\n", sec, d[0], (int)d[1], d[2], d[3], (int)d[4], (int)d[5], d[6], d[7]);
+        std::this_thread::sleep_for(std::chrono::milliseconds(1000));
+    }
+    if (hipStreamQuery(s) == hipErrorNotReady) {
+        std::fprintf(stderr, "[apa2] the forward kernel does not finish: giving up\n");
+        std::_Exit(3);
+    }
+    if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
+    std::vector<apa2::PairResult> r(std::min<size_t>(p->pairs, 8));
+    if (!hip_ok(hipMemcpy(r.data(), p->d_results.ptr, r.size() * sizeof(apa2::PairResult), hipMemcpyDeviceToHost), "D2H")) return PA_E_HIP;
+    for (size_t i = 0; i < r.size(); ++i)
+        std::fprintf(stderr, "[apa2] pair %zu: status %d cost %d f_max %d tries %u blocks %u lanes %llu last %d len %d\n", i, r[i].status, r[i].cost, r[i].f_max,
+                     r[i].f_max_tries, r[i].num_blocks, (unsigned long long)r[i].computed_lanes, r[i].last_block_idx, r[i].blocks_len);
+    return 0;
+}
+
 // Profiles -> (granule clear) -> DP kernel, all queued on the batch's stream; ev0/ev1 bracket the DP kernel.
 // launch = false (batched A*PA2 through pa_batch_align): everything BEFORE the band-search kernel only; the caller launches it chunk by
 // chunk on streams of their own.
@@ -1446,31 +972,10 @@ static int batch_forward(pa_batch* p, bool launch = true) {
     if (!hip_ok(hipEventRecord(p->ev0, s), "event")) return PA_E_HIP;
     if (p->astar) {
         if (p->pairs) {
-            uint32_t* dbg = nullptr;
             if (getenv("PA_APA2_DEBUG")) {
-                void* hp = nullptr;
-                if (!hip_ok(hipHostMalloc(&hp, 256, hipHostMallocMapped), "hipHostMalloc(debug)")) return PA_E_HIP;
-                std::memset(hp, 0, 256);
-                dbg = (uint32_t*)hp;
-            }
-            if (const int rc = launch_astar(p, s, 0, p->pairs, p->d_misc.as<uint32_t>(), dbg)) return rc;
-            if (dbg) {  // diagnostics: the forward pass alone, progress markers and first results on stderr
-                std::fprintf(stderr, "[apa2] forward launched: pairs %zu\n", p->pairs);
-                for (int sec = 0; sec < 8 && hipStreamQuery(s) == hipErrorNotReady; ++sec) {
-                    const volatile uint32_t* d = dbg;
-                    std::fprintf(stderr, "[apa2] t=%ds stage %u f_max %d tries %u block %u js %d je %d strip %u pair %u\n", sec, d[0], (int)d[1], d[2], d[3], (int)d[4], (int)d[5], d[6], d[7]);
-                    std::this_thread::sleep_for(std::chrono::milliseconds(1000));
-                }
-                if (hipStreamQuery(s) == hipErrorNotReady) {
-                    std::fprintf(stderr, "[apa2] the forward kernel does not finish: giving up\n");
-                    std::_Exit(3);
-                }
-                if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
-                std::vector<apa2::PairResult> r(std::min<size_t>(p->pairs, 8));
-                if (!hip_ok(hipMemcpy(r.data(), p->d_results.ptr, r.size() * sizeof(apa2::PairResult), hipMemcpyDeviceToHost), "D2H")) return PA_E_HIP;
-                for (size_t i = 0; i < r.size(); ++i)
-                    std::fprintf(stderr, "[apa2] pair %zu: status %d cost %d f_max %d tries %u blocks %u lanes %llu last %d len %d\n", i, r[i].status, r[i].cost, r[i].f_max,
-                                 r[i].f_max_tries, r[i].num_blocks, (unsigned long long)r[i].computed_lanes, r[i].last_block_idx, r[i].blocks_len);
+                if (const int rc = launch_astar_watched(p, s)) return rc;
+            } else if (const int rc = launch_astar(p, s, 0, p->pairs, p->d_misc.as<uint32_t>(), nullptr)) {
+                return rc;
             }
         }
     } else if (p->sequential) {
@@ -1556,6 +1061,43 @@ static int banded_finish(pa_batch* p, std::vector<int32_t>& sums, int32_t* cost_
     return 0;
 }
 
+// The end of a cost-only pass: d_sums into `sums` and the error words of d_misc -- an invalid base (word 3), a spin timeout (word
+// `err_word`: 5 for the bit-sliced kernel, 1 for the strips; `timeout_msg` takes its value).
+static int read_sums_and_errors(pa_batch* p, int32_t* sums, int err_word, const char* timeout_msg) {
+    hipStream_t s = p->stream;
+    uint32_t misc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (p->pairs && !hip_ok(hipMemcpyAsync(sums, p->d_sums.ptr, p->pairs * 4, hipMemcpyDeviceToHost, s), "D2H")) return PA_E_HIP;
+    if (!hip_ok(hipMemcpyAsync(misc, p->d_misc.ptr, err_word < 4 ? 16 : 32, hipMemcpyDeviceToHost, s), "D2H")) return PA_E_HIP;
+    if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
+    if (misc[3]) {
+        set_error("sequence contains a base outside ACGT");
+        return PA_E_INVALID_BASE;
+    }
+    if (misc[err_word] != PA_ERR_NONE) {
+        set_error(timeout_msg, misc[err_word]);
+        return PA_E_TIMEOUT;
+    }
+    return 0;
+}
+
+// PA_STRIP_WAVELOG (diagnostics, attach_wavelog): what every strip wavefront left behind, as a table in the file the variable names.
+static void dump_wavelog(const pa_batch* p) {
+    std::vector<uint32_t> log(p->jobs.size() * 8);
+    if (hip_ok(hipMemcpy(log.data(), p->d_wavelog.ptr, log.size() * 4, hipMemcpyDeviceToHost), "D2H wavelog")) {
+        if (FILE* f = std::fopen(getenv("PA_STRIP_WAVELOG"), "w")) {
+            std::fprintf(f, "job k word0 xcc se cu simd wave t0 t1 polled\n");
+            for (size_t j = 0; j < p->jobs.size(); ++j) {
+                const uint32_t* r = &log[8 * j];
+                const uint32_t hw = r[0];
+                std::fprintf(f, "%zu %d %d %u %u %u %u %u %llu %llu %u\n", j, p->sequential ? p->jobs[j].k : p->k, p->jobs[j].word0, r[1] & 15u,
+                             (hw >> 13) & 7u, (hw >> 8) & 15u, (hw >> 4) & 3u, hw & 15u, (unsigned long long)(r[2] | ((uint64_t)r[3] << 32)),
+                             (unsigned long long)(r[4] | ((uint64_t)r[5] << 32)), r[6]);
+            }
+            std::fclose(f);
+        }
+    }
+}
+
 extern "C" int pa_batch_run(pa_batch* p, int32_t* cost_out, float* kernel_ms) {
     if (!p) return PA_E_ARG;
     if (p->astar) {  // batched A*PA2, costs only: the band search without the traceback kernels (the distance over the traced band)
@@ -1570,18 +1112,7 @@ extern "C" int pa_batch_run(pa_batch* p, int32_t* cost_out, float* kernel_ms) {
         if (const int rc = slice::run(p->sliced, s, p->d_codes.as<uint32_t>(), p->d_prof.as<uint64_t>(), p->d_sums.as<int32_t>(), p->d_misc.as<uint32_t>() + 4,
                                       p->ev0, p->ev1))
             return rc;
-        uint32_t misc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (p->pairs && !hip_ok(hipMemcpyAsync(cost_out, p->d_sums.ptr, p->pairs * 4, hipMemcpyDeviceToHost, s), "D2H")) return PA_E_HIP;
-        if (!hip_ok(hipMemcpyAsync(misc, p->d_misc.ptr, 32, hipMemcpyDeviceToHost, s), "D2H")) return PA_E_HIP;
-        if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
-        if (misc[3]) {
-            set_error("sequence contains a base outside ACGT");
-            return PA_E_INVALID_BASE;
-        }
-        if (misc[5] != 0) {
-            set_error("device spin timeout in the bit-sliced kernel (err=%u)", misc[5]);
-            return PA_E_TIMEOUT;
-        }
+        if (const int rc = read_sums_and_errors(p, cost_out, 5, "device spin timeout in the bit-sliced kernel (err=%u)")) return rc;
         if (kernel_ms && !hip_ok(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1), "elapsed")) return PA_E_HIP;
         for (size_t i = 0; i < p->pairs; ++i)  // (a pair with an empty sequence is in no group)
             if (p->n[i] == 0 || p->m[i] == 0) cost_out[i] = (int32_t)(p->n[i] + p->m[i]);
@@ -1590,35 +1121,9 @@ extern "C" int pa_batch_run(pa_batch* p, int32_t* cost_out, float* kernel_ms) {
     if (const int rc = batch_forward(p)) return rc;
     // (4) read back: bottom sums and each pair's last v word (for the rows beyond |b| in the last word)
     std::vector<int32_t> sums(p->pairs, 0);
-    uint32_t misc[4] = {0, 0, 0, 0};
-    if (p->pairs && !hip_ok(hipMemcpyAsync(sums.data(), p->d_sums.ptr, p->pairs * 4, hipMemcpyDeviceToHost, s), "D2H")) return PA_E_HIP;
-    if (!hip_ok(hipMemcpyAsync(misc, p->d_misc.ptr, 16, hipMemcpyDeviceToHost, s), "D2H")) return PA_E_HIP;
-    if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
-    if (misc[3]) {
-        set_error("sequence contains a base outside ACGT");
-        return PA_E_INVALID_BASE;
-    }
-    if (misc[1] != PA_ERR_NONE) {
-        set_error("device spin timeout (err=%u)", misc[1]);
-        return PA_E_TIMEOUT;
-    }
+    if (const int rc = read_sums_and_errors(p, sums.data(), 1, "device spin timeout (err=%u)")) return rc;
     p->gran_dirty = p->banded && !p->sequential;  // clean finish (banded chained strips leave unconsumed granules behind)
-    if (p->d_wavelog.ptr) {
-        std::vector<uint32_t> log(p->jobs.size() * 8);
-        if (hip_ok(hipMemcpy(log.data(), p->d_wavelog.ptr, log.size() * 4, hipMemcpyDeviceToHost), "D2H wavelog")) {
-            if (FILE* f = std::fopen(getenv("PA_STRIP_WAVELOG"), "w")) {
-                std::fprintf(f, "job k word0 xcc se cu simd wave t0 t1 polled\n");
-                for (size_t j = 0; j < p->jobs.size(); ++j) {
-                    const uint32_t* r = &log[8 * j];
-                    const uint32_t hw = r[0];
-                    std::fprintf(f, "%zu %d %d %u %u %u %u %u %llu %llu %u\n", j, p->sequential ? p->jobs[j].k : p->k, p->jobs[j].word0, r[1] & 15u,
-                                 (hw >> 13) & 7u, (hw >> 8) & 15u, (hw >> 4) & 3u, hw & 15u, (unsigned long long)(r[2] | ((uint64_t)r[3] << 32)),
-                                 (unsigned long long)(r[4] | ((uint64_t)r[5] << 32)), r[6]);
-                }
-                std::fclose(f);
-            }
-        }
-    }
+    if (p->d_wavelog.ptr) dump_wavelog(p);
     if (kernel_ms) {
         *kernel_ms = 0.f;
         if (!p->jobs.empty() && !hip_ok(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1), "elapsed")) return PA_E_HIP;

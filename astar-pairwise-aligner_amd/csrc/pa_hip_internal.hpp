@@ -149,5 +149,9 @@ struct PairDesc {
 // codes of every a (skipped when max_n == 0) and profile of every b (skipped when max_m == 0) of `pairs` descriptors
 bool encode_batch_device(const uint8_t* d_a_cat, size_t max_n, uint32_t* d_codes_cat, const uint8_t* d_b_cat, size_t max_m, uint64_t* d_prof_cat,
                          const PairDesc* d_desc, size_t pairs, uint32_t* d_bad, hipStream_t s);
+// apa2_jobs_unit.hip -- host threads for per-pair host work of a batch (PA_HOST_THREADS, else as many as the process may run on), and
+// the words per slot of a pair's block-column store in the batched A*PA2 modes (PA_APA2_WINDOW; override_ < 0: the policy)
+unsigned host_threads();
+size_t window_words(size_t n, size_t m, bool gcsh, int override_);
 
 }  // namespace pa

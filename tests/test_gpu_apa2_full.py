@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 
 FULL_FAMILY = ["full", "gcsh_noprune", "gcsh_k8_p0_prune", "gcsh_k6_p3_prune_incr", "gcsh_k10_p5_nosparseh", "gap_incr", "sh12_incr", "dijkstra_incr_nodt",
                "gap_incr_f15"]
+UNEVEN_REPEAT_UNIT = 50  # bases of the unit of the tandem repeat in uneven_slices_pairs
 
 
 @pytest.fixture(scope="module")
@@ -266,6 +267,41 @@ def test_band_proportional_columns_and_the_second_round(pa, oracle, name, monkey
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-1500:]
 
 
+def uneven_slices_pairs(repeat_unit=UNEVEN_REPEAT_UNIT):
+    """One batch whose per-pair slices of the job builders' buffers (csrc/apa2_jobs_unit.hip: block records, SH table, h row, seeds,
+    matches, the match builder's scratch) are as uneven as they can be, neighbours of very different size interleaved: empty sequences,
+    |a| = k - 1, k, k + 1 for the presets' k = 12 (no seed, one seed, one seed and a rest), |a| = 255, 256, 257 (one block, one block, two), a
+    tandem repeat of 600 bp (many candidate matches per seed) and 3000 bp at 5 %."""
+    def sized(n, e, seed):
+        a, b = gen_pair(n, e, seed)
+        assert len(a) == n
+        return a, b
+
+    unit = rand_seq(repeat_unit, seed=9)
+    ra = (unit * (600 // repeat_unit + 1))[:600]
+    rb = bytearray(ra)
+    for q in (70, 230, 410, 555):
+        rb[q] = ord("A") if rb[q] != ord("A") else ord("C")
+    repeat = (ra, bytes(rb[:300] + rb[317:]))
+    return [(b"", b""), sized(11, 0.1, 1), (b"ACGT", b""), sized(12, 0.1, 2), (b"", b"ACGTA"), sized(13, 0.1, 3), sized(255, 0.05, 4), repeat,
+            sized(256, 0.05, 5), sized(3000, 0.05, 6), sized(257, 0.05, 7)]
+
+
+@pytest.mark.parametrize("name", ["full", "sh12_incr", "simple", "sh12"])
+def test_uneven_neighbouring_slices(pa, oracle, name):
+    """The batch of uneven_slices_pairs, forwards and reversed: a slice that overlapped its neighbour's would change a result.  Every pair's
+    cost, CIGAR string and twelve statistics equal the CPU-kernel engine's, and the reversed batch returns the same per pair.
+    Pairs the GPU does not serve: 3 for every parameter set -- the three pairs with an empty sequence, which both band-search kernels
+    leave to the host engine (kErrDegenerate).  The tandem repeat is served, so the match builder's scratch slice is exercised, not
+    bypassed: by csrc/gcsh.hpp on the host it has 514 candidate matches for 50 seeds (the builder refuses beyond its 2123 slots,
+    rc -101) and keeps 44 of them (rc -102 needs more than the 64 kept matches its ring holds)."""
+    oc = variants(oracle)[name][0]
+    pairs = uneven_slices_pairs()
+    costs, cigars, _, _ = check(pa, oracle, pairs, oc, max_fallbacks=3)
+    rcosts, rcigars, _, _ = check(pa, oracle, pairs[::-1], oc, max_fallbacks=3)
+    assert list(rcosts[::-1]) == list(costs) and rcigars[::-1] == cigars
+
+
 def test_matches_from_host_threads_give_the_same(pa, oracle):
     """PA_GCSH_HOST_BUILD=1: the matches of GCSH come from host threads at creation (csrc/gcsh.hpp) instead of the GPU's build kernel -- also
     what a parameter set with a look-ahead beyond the kernel's LDS arrays (p > 14) gets.  Same cost, CIGAR string and statistics."""
@@ -281,18 +317,21 @@ def test_matches_from_host_threads_give_the_same(pa, oracle):
         from tests.test_gpu_engine import gpu_params
         from tests.test_sweep_emu import KEYS
         from tests.util_seq import gen_pair
-        pairs = [gen_pair(n, e, seed) for n, e, seed in [(300, 0.05, 1), (3000, 0.1, 3), (10000, 0.15, 4), (30000, 0.08, 6), (9000, 0.3, 8)]]
-        for oc in (oracle.params_full(), oracle.make_params(domain="astar", heuristic="gcsh", k=10, p=20, doubling="band", start="h0", factor=2.0,
-                                                             block_width=256, sparse=True, incremental_doubling=True, dt_trace=True, max_g=40,
-                                                             fr_drop=10, sparse_h=True, prune=True)):
-            b = pa.Batch(pairs, params=gpu_params(pa, oc))
-            costs, cigars, _, _ = b.align()
-            st = b.pair_stats()
-            assert b.full_info()["build_ms"] > 0  # (positive: host threads)
-            for i, (x, y) in enumerate(pairs):
-                w = oracle.cpu_align(x, y, oc)
-                assert (int(costs[i]), cigars[i]) == w[:2] and all(st[i][k] == w[2][k] for k in KEYS), i
-            assert b.trace_fallbacks() == 0
+        from tests.test_gpu_apa2_full import uneven_slices_pairs
+        several = [gen_pair(n, e, seed) for n, e, seed in [(300, 0.05, 1), (3000, 0.1, 3), (10000, 0.15, 4), (30000, 0.08, 6), (9000, 0.3, 8)]]
+        # (... and the batch of uneven neighbouring slices: its three pairs with an empty sequence go to the host engine)
+        for pairs, handed_back in ((several, 0), (uneven_slices_pairs(), 3)):
+            for oc in (oracle.params_full(), oracle.make_params(domain="astar", heuristic="gcsh", k=10, p=20, doubling="band", start="h0", factor=2.0,
+                                                                 block_width=256, sparse=True, incremental_doubling=True, dt_trace=True, max_g=40,
+                                                                 fr_drop=10, sparse_h=True, prune=True)):
+                b = pa.Batch(pairs, params=gpu_params(pa, oc))
+                costs, cigars, _, _ = b.align()
+                st = b.pair_stats()
+                assert b.full_info()["build_ms"] > 0  # (positive: host threads)
+                for i, (x, y) in enumerate(pairs):
+                    w = oracle.cpu_align(x, y, oc)
+                    assert (int(costs[i]), cigars[i]) == w[:2] and all(st[i][k] == w[2][k] for k in KEYS), i
+                assert b.trace_fallbacks() == handed_back, b.trace_fallbacks()
         print("ok")
     """) % str(__import__("pathlib").Path(__file__).resolve().parent.parent)
     import os
