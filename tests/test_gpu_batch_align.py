@@ -251,7 +251,8 @@ def check_dt(pa, oracle, pairs):
 def test_dt_trace_small_and_boundaries(pa, oracle):
     """Device-side DT-trace (blocks/trace.rs:231-416) in the batched traceback: cost and CIGAR string equal the engine over the
     CPU oracle kernels with the same `front` -- which takes the diagonal-transition path wherever it succeeds and re-fills the
-    block where it gives up (max_g, the midpoint early-out, fr_drop)."""
+    block where it gives up (max_g, the midpoint early-out, fr_drop).  (One `front` here: max_g = 40, fr_drop = 10.  The grid of
+    options and the kernel's own edges, against the second restatement, live in tests/test_gpu_trace_edges.py.)"""
     pairs = list(PA_TEST_PAIRS)
     for n in (1, 2, 63, 64, 65, 255, 256, 257, 258, 511, 512, 513, 769, 1000, 1025, 2049):
         for e in (0.0, 0.05, 0.2):
