@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "pa_search_batch_create", "pa_search_batch_run", "pa_search_batch_rows", "pa_search_batch_trace", "pa_search_batch_info",
     "pa_search_batch_destroy",
     "pa_affine_batch_create", "pa_affine_batch_run", "pa_affine_batch_align", "pa_affine_batch_info", "pa_affine_batch_destroy",
+    "pa_affine_batch_align_tiled", "pa_affine_batch_tiled_info",
 ]
 
 _lib = None
@@ -98,6 +99,10 @@ def load(build_if_stale: bool = True) -> C.CDLL:
     L.pa_affine_batch_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
     L.pa_affine_batch_info.restype = None
     L.pa_affine_batch_destroy.argtypes = [vp]
+    if hasattr(L, "pa_affine_batch_align_tiled"):  # (PA_LIB_PATH may point at an older build of the library: diagnostics)
+        L.pa_affine_batch_align_tiled.argtypes = [vp, C.c_uint32, vp, vp] + [C.POINTER(C.c_float)] * 3
+        L.pa_affine_batch_tiled_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
+        L.pa_affine_batch_tiled_info.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -559,6 +564,7 @@ class AffineBatch:
             raise PaError(msg)
         self.last_kernel_ms = 0.0
         self.last_forward_ms = 0.0
+        self.last_refill_ms = 0.0
         self.last_trace_ms = 0.0
 
     def _check(self, rc: int, what: str) -> None:
@@ -591,6 +597,32 @@ class AffineBatch:
         self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
         return [(int(costs[p]), cigars[p]) for p in range(n)]
 
+    def align_tiled(self, tile_cols: int = 0) -> list[tuple[int, str]]:
+        """align() in bounded device memory: checkpoints from a cost-only pass, then only the tiles the path crosses are filled with
+        codes.  tile_cols: columns of a tile, 0 for the default, else in [64, 2^20].  The times are kept in `last_forward_ms`
+        (checkpoint pass), `last_refill_ms` (tile fills) and `last_trace_ms` (walks)."""
+        if not isinstance(tile_cols, (int, np.integer)) or isinstance(tile_cols, bool) or not 0 <= tile_cols < 1 << 32:
+            raise ValueError(f"tile_cols must be 0 or in [64, 2^20], got {tile_cols!r}")
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        cig = (C.c_void_p * max(n, 1))()
+        f, r, t = C.c_float(0), C.c_float(0), C.c_float(0)
+        rc = L.pa_affine_batch_align_tiled(self._h, int(tile_cols), _p(costs), cig, C.byref(f), C.byref(r), C.byref(t))
+        try:
+            self._check(rc, "pa_affine_batch_align_tiled")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_refill_ms, self.last_trace_ms = float(f.value), float(r.value), float(t.value)
+        return [(int(costs[p]), cigars[p]) for p in range(n)]
+
+    def tiled_info(self) -> dict:
+        """Shape of the last align_tiled(): chunks, rounds, tile jobs, cells the fills computed, bytes of the largest chunk."""
+        vals = [C.c_double(0) for _ in range(5)]
+        load().pa_affine_batch_tiled_info(self._h, *[C.byref(v) for v in vals])
+        return {k: int(v.value) for k, v in zip(("chunks", "rounds", "tile_jobs", "refill_cells", "chunk_bytes_max"), vals)}
+
     def info(self) -> dict:
         vals = [C.c_double(0) for _ in range(5)]
         load().pa_affine_batch_info(self._h, *[C.byref(v) for v in vals])
@@ -609,11 +641,12 @@ class AffineBatch:
             pass
 
 
-def align_affine(pairs, cm: AffineCost) -> list[tuple[int, str]]:
-    """[(cost, CIGAR)] of every pair under the gap-affine cost model `cm` (one traced AffineBatch)."""
+def align_affine(pairs, cm: AffineCost, tiled: bool = False) -> list[tuple[int, str]]:
+    """[(cost, CIGAR)] of every pair under the gap-affine cost model `cm` (one traced AffineBatch); tiled=True takes the
+    bounded-memory route (AffineBatch.align_tiled), for pairs whose whole code matrix would not fit."""
     b = AffineBatch(pairs, cm, trace=True)
     try:
-        return b.align()
+        return b.align_tiled() if tiled else b.align()
     finally:
         b.close()
 

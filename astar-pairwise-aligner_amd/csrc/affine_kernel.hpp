@@ -56,7 +56,7 @@ struct Costs {
 struct Pair {
     const uint8_t* a;
     const uint8_t* b;
-    uint8_t* codes;  // FILL only: (n + 1) H + n + 1 bytes
+    uint8_t* codes;  // FILL: (n + 1) H + n + 1 bytes; CKPT: the pair's column checkpoints (below)
     uint32_t n, m;   // |a|, |b|
     uint32_t H;      // rows of a code column: g kRows (segments) or strips 64 kRows
     uint32_t out;    // index into the cost output
@@ -68,15 +68,19 @@ static_assert(sizeof(Pair) == 40, "Pair layout");
 struct Wave {
     uint32_t first, np, lg, strips;
     uint32_t nmax;  // longest a of the wave
-    uint32_t pad_;
-    uint64_t* bnd;  // strips > 1: nmax + 1 boundary values (M | I << 32) of the strip above
+    uint32_t tile_cols;  // CKPT: columns between two column checkpoints
+    uint64_t* bnd;       // strips > 1: nmax + 1 boundary values (M | I << 32) of the strip above; CKPT: of every strip but the last
 };
 static_assert(sizeof(Wave) == 32, "Wave layout");
 
 __device__ __forceinline__ uint32_t umin(uint32_t x, uint32_t y) { return x < y ? x : y; }
 __device__ __forceinline__ uint32_t umin3(uint32_t x, uint32_t y, uint32_t z) { return umin(umin(x, y), z); }
 
-template <bool FILL>
+// CKPT, the checkpoint pass of the tiled traceback: the cost-only recurrence, which also keeps
+//   * the row checkpoints: the boundary row of every strip but the last, strip s at bnd + s (nmax + 1);
+//   * the column checkpoints, in Pair::codes as 8-byte values: (M | D << 32) of rows 1 .. H after columns C, 2C, .. < n (C = tile_cols),
+//     checkpoint k = 0 .. K - 1 (column (k + 1) C, K = (n - 1) / C) at [k H + j - 1], then (M | D << 32) of row 0 at [K H + k].
+template <bool FILL, bool CKPT = false>
 __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __restrict__ waves, int nwaves, const Pair* __restrict__ pairs,
                                                                   Costs C, int32_t* __restrict__ cost_out) {
     const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
@@ -96,6 +100,9 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
     P.H = 0;
     P.out = 0;
     if (present) P = pairs[W.first + seg];
+    const size_t bnd_stride = CKPT ? (size_t)W.nmax + 1 : 0;  // CKPT keeps every strip's boundary row
+    const gu64 ck_col = (gu64)P.codes;
+    const gu64 ck_row0 = CKPT && P.n ? ck_col + (size_t)((P.n - 1) / W.tile_cols) * P.H : ck_col;
     const int n = (int)P.n;
     const uint32_t m = P.m;
     const gcu8 ga = (gcu8)P.a;
@@ -114,7 +121,9 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
         }
         const bool top = first && s == 0;  // row 0 is this lane's
         const bool from_bnd = first && s > 0;
-        const gcu64 bnd = (gcu64)W.bnd;
+        const gcu64 bnd = CKPT && s > 0 ? (gcu64)(W.bnd + (size_t)(s - 1) * bnd_stride) : (gcu64)W.bnd;
+        int next_ck = (int)W.tile_cols;  // CKPT: the next checkpoint column and its index
+        uint32_t kck = 0;
         uint32_t r0M = kInf, r0D = kInf;  // row 0 of the previous column
         uint32_t topPrev = kInf;          // M of the row above this lane's first row, previous column
         uint32_t outM = kInf, outI = kInf, outC = 0x100u;
@@ -182,7 +191,17 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
                     const u32x4 w = {code[0], code[1], code[2], code[3]};
                     *reinterpret_cast<PA_GLOBAL u32x4*>(codes + (size_t)i * P.H + j0) = w;  // one 16-byte store
                 }
-                if (last && s + 1 < (int)W.strips) ((gu64)W.bnd)[i] = (uint64_t)Iup << 32 | Mup;
+                if (last && s + 1 < (int)W.strips) ((gu64)(CKPT ? W.bnd + (size_t)s * bnd_stride : W.bnd))[i] = (uint64_t)Iup << 32 | Mup;
+                if (CKPT && i == next_ck) {  // lanes reach the column at different steps: each stores its own rows
+                    if (i < n) {
+                        const gu64 col = ck_col + (size_t)kck * P.H + j0;
+#pragma unroll
+                        for (int k = 0; k < kRows; ++k) col[k] = (uint64_t)Dp[k] << 32 | Mp[k];
+                        if (top) ck_row0[kck] = (uint64_t)r0D << 32 | r0M;
+                    }
+                    next_ck += (int)W.tile_cols;
+                    ++kck;
+                }
                 if (i == n && m > j0 && m <= j0 + kRows) {
                     uint32_t v = 0;
 #pragma unroll
@@ -213,6 +232,61 @@ struct WalkOut {
     int32_t nops;
 };
 
+// One step of the walk from (i, j, layer) (0 main, 1 insert, 2 delete) over that state's code c; o.status = 1 on a code that cannot be.
+__device__ __forceinline__ void walk_step(uint32_t c, const uint8_t* a, const uint8_t* b, uint8_t* ops, uint32_t cap, int64_t& i, int64_t& j,
+                                          int& layer, WalkOut& o) {
+    auto emit = [&](uint8_t op) {
+        if ((uint32_t)o.nops < cap) ops[o.nops] = op;
+        ++o.nops;
+    };
+    if (layer == 0) {
+        switch (c & 7u) {
+            case 0:
+                if (i == 0 || j == 0) {
+                    o.status = 1;
+                    break;
+                }
+                emit(a[i - 1] == b[j - 1] ? '=' : 'X');
+                --i;
+                --j;
+                break;
+            case 1:
+                if (j == 0) o.status = 1;
+                else {
+                    emit('I');
+                    --j;
+                }
+                break;
+            case 2:
+                if (i == 0) o.status = 1;
+                else {
+                    emit('D');
+                    --i;
+                }
+                break;
+            case 3: layer = 1; break;
+            case 4: layer = 2; break;
+            default: o.status = 1;
+        }
+    } else if (layer == 1) {
+        if (j == 0) {
+            o.status = 1;
+            return;
+        }
+        emit('I');
+        --j;
+        if (!(c & 8u)) layer = 0;
+    } else {
+        if (i == 0) {
+            o.status = 1;
+            return;
+        }
+        emit('D');
+        --i;
+        if (!(c & 16u)) layer = 0;
+    }
+}
+
 __global__ __launch_bounds__(64) void affine_walk_kernel(const Walk* __restrict__ walks, int nw, WalkOut* __restrict__ outs) {
     const int t = (int)(blockIdx.x * 64 + threadIdx.x);
     if (t >= nw) return;
@@ -223,61 +297,197 @@ __global__ __launch_bounds__(64) void affine_walk_kernel(const Walk* __restrict_
     WalkOut o;
     o.status = 0;
     o.nops = 0;
-    auto emit = [&](uint8_t op) {
-        if ((uint32_t)o.nops < Q.cap) Q.ops[o.nops] = op;
-        ++o.nops;
-    };
     while (o.status == 0 && (i > 0 || j > 0 || layer != 0)) {
         const uint32_t c = j > 0 ? Q.codes[(size_t)i * Q.H + (size_t)(j - 1)] : Q.codes[row0 + (size_t)i];
-        if (layer == 0) {
-            switch (c & 7u) {
-                case 0:
-                    if (i == 0 || j == 0) {
-                        o.status = 1;
-                        break;
-                    }
-                    emit(Q.a[i - 1] == Q.b[j - 1] ? '=' : 'X');
-                    --i;
-                    --j;
-                    break;
-                case 1:
-                    if (j == 0) o.status = 1;
-                    else {
-                        emit('I');
-                        --j;
-                    }
-                    break;
-                case 2:
-                    if (i == 0) o.status = 1;
-                    else {
-                        emit('D');
-                        --i;
-                    }
-                    break;
-                case 3: layer = 1; break;
-                case 4: layer = 2; break;
-                default: o.status = 1;
-            }
-        } else if (layer == 1) {
-            if (j == 0) {
-                o.status = 1;
-                break;
-            }
-            emit('I');
-            --j;
-            if (!(c & 8u)) layer = 0;
-        } else {
-            if (i == 0) {
-                o.status = 1;
-                break;
-            }
-            emit('D');
-            --i;
-            if (!(c & 16u)) layer = 0;
-        }
+        walk_step(c, Q.a, Q.b, Q.ops, Q.cap, i, j, layer, o);
     }
     if (o.status == 0 && (uint32_t)o.nops > Q.cap) o.status = 2;
     outs[t] = o;
+}
+
+// affine_kernel's row loop with its codes, for affine_tile_kernel: rows k = 0 .. kRows - 1 of one lane's column.  Mp / Dp hold the previous
+// column going in and this column coming out, Mdiag is M of the row above in the previous column, Mup / Iup enter as the row above in
+// this column and leave as the lane's last row.  (affine_kernel keeps the loop in its own body: called through this function its FILL
+// instance compiles to other machine code, 1562 instructions for 1624, and which of the two is faster has not been measured.)
+__device__ __forceinline__ void fill_rows(const Costs& C, const uint32_t (&bk)[kRows], uint32_t (&Mp)[kRows], uint32_t (&Dp)[kRows], uint32_t inC,
+                                          uint32_t Mdiag, uint32_t& Mup, uint32_t& Iup, uint32_t (&code)[kRows / 4]) {
+#pragma unroll
+    for (int k = 0; k < kRows; ++k) {
+        const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
+        const uint32_t iop = Mup + C.io;
+        const uint32_t I = umin(iop, Iup + C.ie);
+        const uint32_t dop = Mp[k] + C.dopen;
+        const uint32_t D = umin(dop, Dp[k] + C.de);
+        const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del, cI = I + C.ie, cD = D + C.de;
+        const uint32_t M = umin(umin3(cd, ci, cdl), umin3(cI, cD, kInf));
+        uint32_t c = M == cI ? 3u : 4u;
+        c = M == cdl ? 2u : c;
+        c = M == ci ? 1u : c;
+        c = M == cd ? 0u : c;
+        c |= I == iop ? 0u : 8u;
+        c |= D == dop ? 0u : 16u;
+        code[k >> 2] |= c << (8 * (k & 3));
+        Mdiag = Mp[k];
+        Mp[k] = M;
+        Dp[k] = D;
+        Mup = M;
+        Iup = I;
+    }
+}
+
+// ---- the tiled traceback: re-fill one tile of codes per pair and round, walk it, resume in the next tile ----
+//
+// Tiles: row tile rt of a state (i, j) is 0 for j = 0, else (j - 1) / (64 kRows), i.e. the strip that owns row j (the one row tile of a
+// packed pair); column tile ct is 0 for i = 0, else (i - 1) / C.  A tile job re-runs the FILL recurrence over the rows of strip rt and the
+// columns cs .. c1, where c0 = ct C, cs = c0 + 1 (0 for c0 = 0: column 0 is a border of column tile 0) and c1 is the column at which the
+// walk entered the tile.  The state to the left comes from the column checkpoint at c0, the row above from the row checkpoint of strip
+// rt - 1 or, on strip 0, from the row-0 recurrence restarted at its checkpoint; all of them hold the forward pass's own values, so
+// the tile's codes are those of the whole matrix.  Only lanes 0 .. rlast (the lane of the entry row) have to finish their columns.
+
+// The walk's state between tiles.
+struct WalkState {
+    int32_t i, j, layer;
+    int32_t nops;
+    int32_t status;  // as WalkOut::status
+    int32_t pad_;
+};
+static_assert(sizeof(WalkState) == 24, "WalkState layout");
+
+struct TileJob {
+    const uint8_t* a;
+    const uint8_t* b;
+    uint8_t* codes;         // the pair's tile: rows 1 .. Ht of column i at codes[(i - cs) Ht + j - 1 - rt 64 kRows], row 0 at codes[row0 + i - cs]
+    const uint64_t* left;   // c0 > 0: the strip's rows of the column checkpoint at c0
+    const uint64_t* left0;  // c0 > 0 and rt = 0: row 0 of that checkpoint
+    const uint64_t* above;  // rt > 0: the row checkpoint of strip rt - 1, columns 0 .. n
+    uint8_t* ops;
+    WalkState* state;
+    uint32_t m, Ht, rt, c0, c1, row0, cap, rlast;
+};
+static_assert(sizeof(TileJob) == 96, "TileJob layout");
+
+// One wavefront of the re-fill: jobs [first, first + np), all of segment width 1 << lg, for `steps` steps.
+struct TileWave {
+    uint32_t first, np, lg, steps;
+};
+
+__global__ __launch_bounds__(64 * kBlockWaves) void affine_tile_kernel(const TileWave* __restrict__ waves, int nwaves, const TileJob* __restrict__ jobs,
+                                                                       Costs C) {
+    const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
+    if (wave >= nwaves) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const TileWave W = waves[wave];
+    const int g = 1 << W.lg;
+    const int seg = lane >> W.lg, r = lane & (g - 1);
+    const bool present = (uint32_t)seg < W.np;
+    const bool first = r == 0;
+    TileJob J = TileJob();
+    if (present) J = jobs[W.first + seg];
+    const gcu8 ga = (gcu8)J.a;
+    const gcu8 gb = (gcu8)J.b;
+    const gu8 codes = (gu8)J.codes;
+    const gcu64 left = (gcu64)J.left, above = (gcu64)J.above;
+    const int cs = J.c0 ? (int)J.c0 + 1 : 0, c1 = (int)J.c1;
+    const bool resume = present && J.c0 > 0;           // the state left of the tile is a checkpoint, not column -1
+    const uint32_t j0 = (uint32_t)r * kRows;           // the lane's first row inside the tile
+    const uint32_t jb = J.rt * (64 * kRows) + j0;      // ... and its index into b
+    uint32_t bk[kRows], Mp[kRows], Dp[kRows];
+#pragma unroll
+    for (int k = 0; k < kRows; ++k) {
+        bk[k] = present && jb + k < J.m ? (uint32_t)gb[jb + k] : 0x200u;
+        Mp[k] = kInf;
+        Dp[k] = kInf;
+    }
+    const bool top = first && J.rt == 0;
+    const bool from_above = first && J.rt > 0;
+    uint32_t r0M = kInf, r0D = kInf;
+    if (top && resume) {
+        const uint64_t v = *(gcu64)J.left0;
+        r0M = (uint32_t)v;
+        r0D = (uint32_t)(v >> 32);
+    }
+    uint32_t topPrev = kInf;
+    uint32_t outM = kInf, outI = kInf, outC = 0x100u;
+    uint32_t nextC = first && present && cs > 0 ? (uint32_t)ga[cs - 1] : 0x100u;
+    uint64_t nextB = (uint64_t)kInf << 32 | kInf;
+    if (from_above && present) nextB = above[cs];
+    for (int t = 0; t < (int)W.steps; ++t) {
+        const int i = cs + t - r;  // column
+        const bool active = present && i >= cs && i <= c1;
+        uint32_t inM = dpp_wave_shr1(kInf, outM);
+        uint32_t inI = dpp_wave_shr1(kInf, outI);
+        uint32_t inC = dpp_wave_shr1(0x100u, outC);
+        if (resume && t == r) {  // the lane's first column: what it has computed so far gives way to the checkpoint at c0
+#pragma unroll
+            for (int k = 0; k < kRows; ++k) {
+                const uint64_t v = left[j0 + k];
+                Mp[k] = (uint32_t)v;
+                Dp[k] = (uint32_t)(v >> 32);
+            }
+            topPrev = top ? r0M : from_above ? (uint32_t)above[J.c0] : (uint32_t)left[j0 - 1];
+        }
+        if (first) {
+            inC = nextC;
+            if (top) {
+                const uint32_t nd = umin3(r0M + C.dopen, r0D + C.de, kInf);
+                const uint32_t nm = i == 0 ? 0u : umin3(r0M + C.del, nd + C.de, kInf);
+                if (active) {
+                    const uint32_t code = (nm == r0M + C.del ? 2u : 4u) | (nd == r0M + C.dopen ? 0u : 16u);
+                    codes[(size_t)J.row0 + (size_t)(i - cs)] = (uint8_t)code;
+                }
+                r0M = nm;
+                r0D = nd;
+                inM = nm;
+                inI = kInf;
+            } else {
+                inM = (uint32_t)nextB;
+                inI = (uint32_t)(nextB >> 32);
+            }
+            nextC = present && i + 1 <= c1 ? (uint32_t)ga[i] : 0x100u;
+            if (from_above && present && i + 1 <= c1) nextB = above[i + 1];
+        }
+        uint32_t Mdiag = topPrev;
+        topPrev = inM;
+        uint32_t Mup = inM, Iup = inI;
+        uint32_t code[kRows / 4] = {0, 0, 0, 0};
+        fill_rows(C, bk, Mp, Dp, inC, Mdiag, Mup, Iup, code);
+        if (active) {
+            const u32x4 w = {code[0], code[1], code[2], code[3]};
+            *reinterpret_cast<PA_GLOBAL u32x4*>(codes + (size_t)(i - cs) * J.Ht + j0) = w;
+        }
+        outM = Mup;
+        outI = Iup;
+        outC = inC;
+    }
+}
+
+// The walk inside a tile: affine_walk_kernel's loop from the pair's stored state, until the state leaves the tile (upwards, leftwards or
+// diagonally) or reaches (0, 0, main).  The layer travels with the state, so a gap that is open at a tile edge goes on in its layer.
+__global__ __launch_bounds__(64) void affine_tile_walk_kernel(const TileJob* __restrict__ jobs, int nj) {
+    const int t = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (t >= nj) return;
+    const TileJob J = jobs[t];
+    const WalkState S = *J.state;
+    int64_t i = S.i, j = S.j;
+    int layer = S.layer;
+    WalkOut o;
+    o.status = S.status;
+    o.nops = S.nops;
+    const int64_t cs = J.c0 ? (int64_t)J.c0 + 1 : 0;
+    const int64_t jt = (int64_t)J.rt * (64 * kRows), jmin = J.rt ? jt + 1 : 0;  // rows jmin .. of the pair are the tile's
+    while (o.status == 0 && (i > 0 || j > 0 || layer != 0) && i >= cs && j >= jmin) {
+        const uint32_t c = j > 0 ? J.codes[(size_t)(i - cs) * J.Ht + (size_t)(j - 1 - jt)] : J.codes[(size_t)J.row0 + (size_t)(i - cs)];
+        walk_step(c, J.a, J.b, J.ops, J.cap, i, j, layer, o);
+    }
+    if (o.status == 0 && i == 0 && j == 0 && layer == 0 && (uint32_t)o.nops > J.cap) o.status = 2;
+    WalkState R;
+    R.i = (int32_t)i;
+    R.j = (int32_t)j;
+    R.layer = layer;
+    R.nops = o.nops;
+    R.status = o.status;
+    R.pad_ = 0;
+    *J.state = R;
 }
 
 }  // namespace affine

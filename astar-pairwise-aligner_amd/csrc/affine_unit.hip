@@ -4,7 +4,9 @@
 // cost models AffineCost<0> and AffineCost<2> can express (pa-affine-types/src/cost_model.rs:112-190).  Every sequence is uploaded
 // once.  run() launches affine_kernel<false> (costs only) over a plan made at creation: short pairs packed into segments, longer ones a
 // wavefront each, most expensive waves first.  align() re-runs the pairs with affine_kernel<true> in chunks whose traceback codes (one
-// byte per cell) fit a device-memory budget, and walks every pair's codes on the GPU (affine_walk_kernel).
+// byte per cell) fit a device-memory budget, and walks every pair's codes on the GPU (affine_walk_kernel).  align_tiled() gives the same
+// CIGARs in bounded memory: a cost-only pass that keeps checkpoints (affine_ckpt_kernel), then rounds that re-fill the one tile of codes
+// each unfinished pair's walk stands in (affine_tile_kernel) and walk it (affine_tile_walk_kernel).
 #include "pa_hip_internal.hpp"
 #include "engine.hpp"
 #include "affine_kernel.hpp"
@@ -54,6 +56,9 @@ struct pa_affine_batch {
     DeviceBuf d_seq, d_cost;
     Plan fwd;
     double trace_chunks = 0;
+    struct {
+        double chunks = 0, rounds = 0, tile_jobs = 0, refill_cells = 0, chunk_bytes_max = 0;
+    } tiled;  // the last align_tiled()
 };
 
 namespace {
@@ -62,8 +67,44 @@ size_t strips_of(uint32_t m) { return m <= kStripRows ? 1 : (m + kStripRows - 1)
 size_t rows_of(uint32_t m) { return m <= kStripRows ? size_t(kRows) << seg_lg(m) : strips_of(m) * kStripRows; }  // H
 size_t code_bytes_of(uint32_t n, uint32_t m) { return (((size_t)n + 1) * (rows_of(m) + 1) + 15) & ~size_t(15); }
 
+// The tiled traceback ("Tiled traceback").  Column tiles of 1024 columns are as wide as the row tiles (a strip) are
+// high: the row and the column checkpoints then cost the same |a| |b| / 128 bytes each, a tile of codes is 1 MiB, and a path near the
+// diagonal crosses about as many column edges as row edges.
+constexpr uint32_t kTileColsDefault = 1024, kTileColsMin = 64, kTileColsMax = 1u << 20;
+
+size_t ckpt_cols_of(uint32_t n, uint32_t C) { return n ? (n - 1) / C : 0; }  // checkpointed columns C, 2C, .. < n
+size_t tile_rows_of(uint32_t m) { return std::min(rows_of(m), kStripRows); }
+size_t tile_cols_of(uint32_t n, uint32_t C) { return (size_t)std::min(n, C) + 1; }  // columns of the widest tile (column tile 0 has column 0 too)
+size_t tile_bytes_of(uint32_t n, uint32_t m, uint32_t C) { return (tile_cols_of(n, C) * (tile_rows_of(m) + 1) + 15) & ~size_t(15); }
+// Device bytes of one pair: row checkpoints, column checkpoints (row 0 included), one tile of codes, the ops.
+size_t tiled_bytes_of(uint32_t n, uint32_t m, uint32_t C) {
+    return (strips_of(m) - 1) * ((size_t)n + 1) * 8 + ckpt_cols_of(n, C) * (rows_of(m) + 1) * 8 + tile_bytes_of(n, m, C) + (size_t)n + m;
+}
+// Tiles a monotone path can visit: one more column tile or one more row tile per move.
+uint32_t tile_visits_max(uint32_t n, uint32_t m, uint32_t C) {
+    return (uint32_t)((n + (size_t)C - 1) / C + (std::max<uint32_t>(m, 1) + kStripRows - 1) / kStripRows);
+}
+
+// The CIGAR text of a walk's ops (recorded from the end backwards).
+std::string cigar_of(const uint8_t* op, int32_t nops) {
+    engine::Cigar cig;
+    for (int32_t x = 0; x < nops; ++x) {
+        const engine::CigarOp c = op[x] == '=' ? engine::CigarOp::Match
+                                  : op[x] == 'X' ? engine::CigarOp::Sub
+                                  : op[x] == 'D' ? engine::CigarOp::Del
+                                                 : engine::CigarOp::Ins;
+        cig.push_elem(engine::CigarElem{c, 1});
+    }
+    cig.reverse();
+    return cig.to_string();
+}
+
 // Waves over `ids` (in planner order): 64 / g packed pairs of one width per wave, a wave per strip pair; then most expensive first.
-int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan& P, uint8_t* codes_base, hipStream_t s) {
+// ck_base (the checkpoint pass of the tiled traceback, tile_cols columns apart): every pair gets its column checkpoints there, and
+// every strip but the last a boundary row of its own.
+int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan& P, uint8_t* codes_base, hipStream_t s, uint64_t* ck_base = nullptr,
+              uint32_t tile_cols = 0) {
+    size_t ck_words = 0;
     const uint8_t* seq = ab.d_seq.as<uint8_t>();
     std::vector<size_t> bnd_off;
     for (size_t x = 0; x < ids.size();) {
@@ -76,6 +117,7 @@ int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan&
         W.first = (uint32_t)P.pairs.size();
         W.lg = (uint32_t)lg;
         W.strips = (uint32_t)strips_of(ab.m[p0]);
+        W.tile_cols = tile_cols;
         while (x < ids.size() && W.np < per) {
             const uint32_t p = ids[x];
             if ((ab.m[p] <= kStripRows) != packed || (packed && seg_lg(ab.m[p]) != lg)) break;
@@ -91,6 +133,9 @@ int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan&
             if (codes_base) {
                 Q.codes = codes_base + P.code_bytes;
                 P.code_bytes += code_bytes_of(Q.n, Q.m);
+            } else if (ck_base) {
+                Q.codes = reinterpret_cast<uint8_t*>(ck_base + ck_words);
+                ck_words += ckpt_cols_of(Q.n, tile_cols) * ((size_t)Q.H + 1);
             }
             P.pairs.push_back(Q);
             P.lanes += (double)((std::max<uint32_t>(Q.m, 1) + kRows - 1) / kRows);
@@ -100,7 +145,7 @@ int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan&
         }
         P.slots += 64.0 * W.strips;
         bnd_off.push_back(W.strips > 1 ? P.bnd_words : SIZE_MAX);
-        if (W.strips > 1) P.bnd_words += W.nmax + 1;
+        if (W.strips > 1) P.bnd_words += (ck_base ? size_t(W.strips) - 1 : 1) * ((size_t)W.nmax + 1);
         P.waves.push_back(W);
     }
     if (!P.d_bnd.alloc(std::max<size_t>(P.bnd_words * 8, 16))) return PA_E_HIP;
@@ -310,17 +355,7 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
             const WalkOut& o = wout[k];
             if (o.status != 0)
                 return fail(PA_E_INTERNAL, "pa_affine_batch_align: pair %u: %s", P.pairs[k].out, o.status == 1 ? "bad traceback code" : "path longer than its buffer");
-            engine::Cigar cig;
-            const uint8_t* op = ops.data() + ops_off[k];
-            for (int32_t x = 0; x < o.nops; ++x) {
-                const engine::CigarOp c = op[x] == '=' ? engine::CigarOp::Match
-                                          : op[x] == 'X' ? engine::CigarOp::Sub
-                                          : op[x] == 'D' ? engine::CigarOp::Del
-                                                         : engine::CigarOp::Ins;
-                cig.push_elem(engine::CigarElem{c, 1});
-            }
-            cig.reverse();
-            cigars[P.pairs[k].out] = cig.to_string();
+            cigars[P.pairs[k].out] = cigar_of(ops.data() + ops_off[k], o.nops);
         }
         c0 = c1;
     }
@@ -331,6 +366,199 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
     if (forward_ms) *forward_ms = fwd_total;
     if (trace_ms) *trace_ms = trace_total;
     return cigar_out ? give_cstrings(cigars, cigar_out) : 0;
+}
+
+namespace {
+
+// One chunk of align_tiled: the forward plan with its row checkpoints, and where every pair (index k into plan.pairs) keeps its rest.
+struct TiledChunk {
+    Plan plan;
+    std::vector<const uint64_t*> ck;     // column checkpoints (affine_kernel.hpp, CKPT)
+    std::vector<const uint64_t*> rowck;  // row checkpoints: strip s at rowck + s (n + 1); nullptr for one strip
+    std::vector<size_t> tile_off, ops_off;
+    size_t ops_bytes = 0;
+    std::vector<WalkState> st;
+    std::vector<uint32_t> visits;
+    DeviceBuf d_ck, d_tiles, d_ops, d_state, d_jobs, d_twaves;
+};
+
+// The chunk's buffers, the checkpoint pass, and every walk at (n, m, main).
+int tiled_forward(pa_affine_batch& ab, const std::vector<uint32_t>& ids, uint32_t C, TiledChunk& ch, hipStream_t s, float* ms) {
+    Plan& P = ch.plan;
+    size_t ck_words = 0;
+    for (const uint32_t p : ids) ck_words += ckpt_cols_of(ab.n[p], C) * (rows_of(ab.m[p]) + 1);
+    if (!ch.d_ck.alloc(std::max<size_t>(ck_words * 8, 16))) return PA_E_HIP;
+    if (const int rc = make_plan(ab, ids, P, nullptr, s, ch.d_ck.as<uint64_t>(), C)) return rc;
+    const size_t np = P.pairs.size();
+    ch.ck.resize(np);
+    ch.rowck.assign(np, nullptr);
+    ch.tile_off.resize(np);
+    ch.ops_off.resize(np);
+    ch.st.resize(np);
+    ch.visits.assign(np, 0);
+    size_t tile_bytes = 0;
+    for (size_t k = 0; k < np; ++k) {
+        const Pair& Q = P.pairs[k];
+        ch.ck[k] = reinterpret_cast<const uint64_t*>(Q.codes);
+        ch.tile_off[k] = tile_bytes;
+        tile_bytes += tile_bytes_of(Q.n, Q.m, C);
+        ch.ops_off[k] = ch.ops_bytes;
+        ch.ops_bytes += (size_t)Q.n + Q.m;
+        ch.st[k] = WalkState{(int32_t)Q.n, (int32_t)Q.m, 0, 0, 0, 0};
+    }
+    if (!ch.d_tiles.alloc(std::max<size_t>(tile_bytes, 16)) || !ch.d_ops.alloc(std::max<size_t>(ch.ops_bytes, 16))) return PA_E_HIP;
+    for (const Wave& W : P.waves)
+        if (W.strips > 1) ch.rowck[W.first] = W.bnd;
+    Events ev;
+    if (!ev.make() || !upload(ch.d_state, ch.st.data(), np * sizeof(WalkState), s) || !hip_ok(hipEventRecord(ev.e[0], s), "event")) return PA_E_HIP;
+    const int grid = (int)((P.waves.size() + kBlockWaves - 1) / kBlockWaves);
+    hipLaunchKernelGGL((affine_kernel<false, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, P.d_waves.as<Wave>(), (int)P.waves.size(),
+                       P.d_pairs.as<Pair>(), ab.C, ab.d_cost.as<int32_t>());
+    if (!hip_ok(hipGetLastError(), "affine_kernel<CKPT> launch") || !hip_ok(hipEventRecord(ev.e[1], s), "event") ||
+        !hip_ok(hipStreamSynchronize(s), "sync") || !hip_ok(hipEventElapsedTime(ms, ev.e[0], ev.e[1]), "hipEventElapsedTime"))
+        return PA_E_HIP;
+    return 0;
+}
+
+// The tile job of every unfinished pair, grouped into waves like the planner's (consecutive packed pairs of one width share a wave).
+int tiled_jobs(pa_affine_batch& ab, uint32_t C, TiledChunk& ch, std::vector<TileJob>& jobs, std::vector<TileWave>& waves) {
+    jobs.clear();
+    waves.clear();
+    for (size_t k = 0; k < ch.plan.pairs.size(); ++k) {
+        const Pair& Q = ch.plan.pairs[k];
+        const WalkState& S = ch.st[k];
+        if (S.status != 0)
+            return fail(PA_E_INTERNAL, "pa_affine_batch_align_tiled: pair %u: %s", Q.out, S.status == 1 ? "bad traceback code" : "path longer than its buffer");
+        if (S.i == 0 && S.j == 0 && S.layer == 0) continue;
+        if (S.i < 0 || S.j < 0 || (uint32_t)S.i > Q.n || (uint32_t)S.j > Q.m || ++ch.visits[k] > tile_visits_max(Q.n, Q.m, C) + 1)
+            return fail(PA_E_INTERNAL, "pa_affine_batch_align_tiled: pair %u: the walk left its %u tiles at (%d, %d)", Q.out,
+                        tile_visits_max(Q.n, Q.m, C), S.i, S.j);
+        const uint32_t ct = S.i ? ((uint32_t)S.i - 1) / C : 0, rt = S.j ? ((uint32_t)S.j - 1) / (uint32_t)kStripRows : 0;
+        TileJob J;
+        std::memset(&J, 0, sizeof J);
+        J.a = Q.a;
+        J.b = Q.b;
+        J.codes = ch.d_tiles.as<uint8_t>() + ch.tile_off[k];
+        J.left = ct ? ch.ck[k] + (size_t)(ct - 1) * Q.H + (size_t)rt * kStripRows : nullptr;
+        J.left0 = ct ? ch.ck[k] + ckpt_cols_of(Q.n, C) * Q.H + (ct - 1) : nullptr;
+        J.above = rt ? ch.rowck[k] + (size_t)(rt - 1) * ((size_t)Q.n + 1) : nullptr;
+        J.ops = ch.d_ops.as<uint8_t>() + ch.ops_off[k];
+        J.state = ch.d_state.as<WalkState>() + k;
+        J.m = Q.m;
+        J.Ht = (uint32_t)tile_rows_of(Q.m);
+        J.rt = rt;
+        J.c0 = ct * C;
+        J.c1 = (uint32_t)S.i;
+        J.row0 = (uint32_t)(tile_cols_of(Q.n, C) * J.Ht);
+        J.cap = Q.n + Q.m;
+        J.rlast = S.j ? ((uint32_t)S.j - 1 - rt * (uint32_t)kStripRows) / kRows : 0;
+        const uint32_t cols = J.c1 - (J.c0 ? J.c0 + 1 : 0) + 1, steps = cols + J.rlast;
+        const bool packed = Q.m <= kStripRows;
+        const uint32_t lg = packed ? (uint32_t)seg_lg(Q.m) : 6;
+        if (waves.empty() || !packed || waves.back().lg != lg || waves.back().np == (64u >> lg))
+            waves.push_back(TileWave{(uint32_t)jobs.size(), 0, lg, 0});
+        waves.back().np += 1;
+        waves.back().steps = std::max(waves.back().steps, steps);
+        jobs.push_back(J);
+        ab.tiled.tile_jobs += 1;
+        ab.tiled.refill_cells += (double)cols * kRows * (J.rlast + 1);
+    }
+    return 0;
+}
+
+// One round: re-fill every job's tile, walk every job's pair through it, and fetch where the walks stand.
+int tiled_round(pa_affine_batch& ab, TiledChunk& ch, const std::vector<TileJob>& jobs, const std::vector<TileWave>& waves, Events& ev, hipStream_t s,
+                float* refill_ms, float* walk_ms) {
+    const int nj = (int)jobs.size(), nw = (int)waves.size();
+    if (!ch.d_jobs.reserve(jobs.size() * sizeof(TileJob)) || !ch.d_twaves.reserve(waves.size() * sizeof(TileWave)) ||
+        !hip_ok(hipMemcpyAsync(ch.d_jobs.ptr, jobs.data(), jobs.size() * sizeof(TileJob), hipMemcpyHostToDevice, s), "H2D") ||
+        !hip_ok(hipMemcpyAsync(ch.d_twaves.ptr, waves.data(), waves.size() * sizeof(TileWave), hipMemcpyHostToDevice, s), "H2D") ||
+        !hip_ok(hipEventRecord(ev.e[0], s), "event"))
+        return PA_E_HIP;
+    hipLaunchKernelGGL(affine_tile_kernel, dim3((nw + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, ch.d_twaves.as<TileWave>(), nw,
+                       ch.d_jobs.as<TileJob>(), ab.C);
+    if (!hip_ok(hipGetLastError(), "affine_tile_kernel launch") || !hip_ok(hipEventRecord(ev.e[1], s), "event")) return PA_E_HIP;
+    hipLaunchKernelGGL(affine_tile_walk_kernel, dim3((nj + 63) / 64), dim3(64), 0, s, ch.d_jobs.as<TileJob>(), nj);
+    float f = 0, w = 0;
+    if (!hip_ok(hipGetLastError(), "affine_tile_walk_kernel launch") || !hip_ok(hipEventRecord(ev.e[2], s), "event") ||
+        !hip_ok(hipMemcpyAsync(ch.st.data(), ch.d_state.ptr, ch.st.size() * sizeof(WalkState), hipMemcpyDeviceToHost, s), "D2H") ||
+        !hip_ok(hipStreamSynchronize(s), "sync") || !hip_ok(hipEventElapsedTime(&f, ev.e[0], ev.e[1]), "hipEventElapsedTime") ||
+        !hip_ok(hipEventElapsedTime(&w, ev.e[1], ev.e[2]), "hipEventElapsedTime"))
+        return PA_E_HIP;
+    *refill_ms += f;
+    *walk_ms += w;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int pa_affine_batch_align_tiled(pa_affine_batch* ab, uint32_t tile_cols, int32_t* cost_out, char** cigar_out, float* forward_ms,
+                                           float* refill_ms, float* walk_ms) {
+    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_align_tiled: NULL batch");
+    if (forward_ms) *forward_ms = 0;
+    if (refill_ms) *refill_ms = 0;
+    if (walk_ms) *walk_ms = 0;
+    if (cigar_out)
+        for (size_t p = 0; p < ab->np; ++p) cigar_out[p] = nullptr;
+    if (!ab->trace) return fail(PA_E_ARG, "pa_affine_batch_align_tiled: the batch was created without trace");
+    if (tile_cols != 0 && (tile_cols < kTileColsMin || tile_cols > kTileColsMax))
+        return fail(PA_E_ARG, "pa_affine_batch_align_tiled: tile_cols = %u outside [%u, %u] (0 = the default, %u)", tile_cols, kTileColsMin, kTileColsMax,
+                    kTileColsDefault);
+    const uint32_t C = tile_cols ? tile_cols : kTileColsDefault;
+    const size_t budget = trace_budget("PA_AFFINE_TRACE_BUDGET_MB");
+    for (size_t p = 0; p < ab->np; ++p)
+        if (tiled_bytes_of(ab->n[p], ab->m[p], C) > budget)
+            return fail(PA_E_ARG, "pa_affine_batch_align_tiled: pair %zu: %zu bytes of checkpoints, tile and ops exceed the budget of %zu bytes", p,
+                        tiled_bytes_of(ab->n[p], ab->m[p], C), budget);
+    hipStream_t s = 0;
+    std::vector<std::string> cigars(ab->np);
+    ab->tiled = {};
+    float fwd_total = 0, refill_total = 0, walk_total = 0;
+    std::vector<TileJob> jobs;
+    std::vector<TileWave> waves;
+    for (size_t c0 = 0; c0 < ab->np;) {
+        size_t c1 = c0, bytes = 0;
+        while (c1 < ab->np && (c1 == c0 || bytes + tiled_bytes_of(ab->n[ab->order[c1]], ab->m[ab->order[c1]], C) <= budget))
+            bytes += tiled_bytes_of(ab->n[ab->order[c1]], ab->m[ab->order[c1]], C), ++c1;
+        const std::vector<uint32_t> ids(ab->order.begin() + c0, ab->order.begin() + c1);
+        ab->tiled.chunks += 1;
+        ab->tiled.chunk_bytes_max = std::max(ab->tiled.chunk_bytes_max, (double)bytes);
+        TiledChunk ch;
+        float f = 0;
+        if (const int rc = tiled_forward(*ab, ids, C, ch, s, &f)) return rc;
+        fwd_total += f;
+        Events ev;
+        if (!ev.make()) return PA_E_HIP;
+        for (;;) {  // ends: every round moves each unfinished pair into another tile, and tiled_jobs() bounds the tiles of a pair
+            if (const int rc = tiled_jobs(*ab, C, ch, jobs, waves)) return rc;
+            if (jobs.empty()) break;
+            ab->tiled.rounds += 1;
+            if (const int rc = tiled_round(*ab, ch, jobs, waves, ev, s, &refill_total, &walk_total)) return rc;
+        }
+        std::vector<uint8_t> ops(ch.ops_bytes);
+        if (ch.ops_bytes && (!hip_ok(hipMemcpyAsync(ops.data(), ch.d_ops.ptr, ch.ops_bytes, hipMemcpyDeviceToHost, s), "D2H") ||
+                             !hip_ok(hipStreamSynchronize(s), "sync")))
+            return PA_E_HIP;
+        for (size_t k = 0; k < ch.plan.pairs.size(); ++k) cigars[ch.plan.pairs[k].out] = cigar_of(ops.data() + ch.ops_off[k], ch.st[k].nops);
+        c0 = c1;
+    }
+    std::vector<int32_t> c(std::max<size_t>(ab->np, 1));
+    if (ab->np && (!hip_ok(hipMemcpyAsync(c.data(), ab->d_cost.ptr, ab->np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync")))
+        return PA_E_HIP;
+    if (cost_out && ab->np) std::memcpy(cost_out, c.data(), ab->np * 4);
+    if (forward_ms) *forward_ms = fwd_total;
+    if (refill_ms) *refill_ms = refill_total;
+    if (walk_ms) *walk_ms = walk_total;
+    return cigar_out ? give_cstrings(cigars, cigar_out) : 0;
+}
+
+extern "C" void pa_affine_batch_tiled_info(const pa_affine_batch* ab, double* chunks, double* rounds, double* tile_jobs, double* refill_cells,
+                                           double* chunk_bytes_max) {
+    if (chunks) *chunks = ab ? ab->tiled.chunks : 0;
+    if (rounds) *rounds = ab ? ab->tiled.rounds : 0;
+    if (tile_jobs) *tile_jobs = ab ? ab->tiled.tile_jobs : 0;
+    if (refill_cells) *refill_cells = ab ? ab->tiled.refill_cells : 0;
+    if (chunk_bytes_max) *chunk_bytes_max = ab ? ab->tiled.chunk_bytes_max : 0;
 }
 
 extern "C" void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,

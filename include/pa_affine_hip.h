@@ -45,6 +45,20 @@ int pa_affine_batch_run(pa_affine_batch* ab, int32_t* cost_out, float* kernel_ms
  * quarter of the free device memory; a pair whose codes alone exceed it is PA_E_ARG.  forward_ms / trace_ms (optional): HIP-event time
  * of the forward kernels and of the walks, summed over the chunks. */
 int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, char** cigar_out, float* forward_ms, float* trace_ms);
+/* Costs and the same CIGARs as pa_affine_batch_align, in bounded device memory (trace batches only, else PA_E_ARG).  A cost-only pass
+ * keeps checkpoints: M and I of the last row of every strip of 1024 rows but the last, and M and D of every row after columns tile_cols,
+ * 2 tile_cols, ...  Then, round by round, the one tile (a strip's rows x tile_cols columns) in which each unfinished pair's walk stands is
+ * filled with codes from its checkpoints, up to the column where the walk entered it, and the walk goes on to the tile's edge.
+ * tile_cols: 0 for the default (1024), else in [64, 2^20] (PA_E_ARG otherwise).  A pair needs about |a| |b| / (8 tile_cols) +
+ * |a| |b| / 128 bytes of checkpoints, one tile of (min(|a|, tile_cols) + 1) * (min(rows, 1024) + 1) bytes and |a| + |b| ops; the pairs run
+ * in chunks within PA_AFFINE_TRACE_BUDGET_MB (or a quarter of the free device memory), and a pair that alone exceeds it is PA_E_ARG.
+ * forward_ms / refill_ms / walk_ms (optional): HIP-event time of the checkpoint passes, the tile fills and the walks, summed. */
+int pa_affine_batch_align_tiled(pa_affine_batch* ab, uint32_t tile_cols, int32_t* cost_out, char** cigar_out, float* forward_ms,
+                                float* refill_ms, float* walk_ms);
+/* The last pa_affine_batch_align_tiled: chunks, rounds (one fill and one walk launch each, summed over the chunks), tile jobs (tiles
+ * filled, summed over pairs), cells those fills computed, and the largest chunk's per-pair device bytes. */
+void pa_affine_batch_tiled_info(const pa_affine_batch* ab, double* chunks, double* rounds, double* tile_jobs, double* refill_cells,
+                                double* chunk_bytes_max);
 /* Plan shape of run(): wavefronts launched, pairs packed into segments (|b| <= 1024), pairs on strips of their own, lanes carrying rows
  * of b (sum of ceil(max(|b|, 1) / 16)) over lanes launched (64 per wavefront and strip), and the chunks of the last align(). */
 void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,

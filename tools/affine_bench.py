@@ -1,9 +1,12 @@
 """Batched gap-affine alignment (pa_affine_batch_*): kernel time, GCUPS and pairs/s, costs only and traced, for three shapes under
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
-    python tools/affine_bench.py [--shapes reads,10k,100k] [--no-trace-100k]
+    python tools/affine_bench.py [--shapes reads,10k,100k] [--trace-100k] [--tile-cols C] [--reps R]
 
-Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks."""
+Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
+tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
+the line shows the fastest repeat and lists them all.  The tiled route also traces what the untiled one leaves out: all pairs of the
+10 kbp shape and the 100 kbp shape (once, unwarmed: a pass over those takes seconds)."""
 from __future__ import annotations
 
 import argparse
@@ -123,10 +126,41 @@ def shape(name, rng):
     return "16 x 100 kbp at 5 %", pairs
 
 
+def traced(tp, cm, mname, untiled, tile_cols, reps, warm=True, note=""):
+    """The traced lines of one batch: the untiled route (if asked for) and the tiled one, alternating."""
+    tcells = float(sum(len(x) * len(y) for x, y in tp))
+    tb = AffineBatch(tp, cm, trace=True)
+    if warm:
+        if untiled:
+            tb.align()
+        tb.align_tiled(tile_cols)
+    u, t = [], []
+    for _ in range(reps):
+        if untiled:
+            tb.align()
+            u.append((tb.last_forward_ms, tb.last_trace_ms))
+        tb.align_tiled(tile_cols)
+        t.append((tb.last_forward_ms, tb.last_refill_ms, tb.last_trace_ms))
+    if untiled:
+        f, w = min(u, key=sum)
+        print(f"{'':44s} {mname:14s} traced:    {f + w:10.2f} ms {tcells / (f + w) / 1e6:8.1f} GCUPS {len(tp) / (f + w) * 1e3:12.0f} pairs/s"
+              f"  (forward {f:.2f} ms = {tcells / f / 1e6:.1f} GCUPS, walks {w:.2f} ms, {tb.info()['trace_chunks']} chunks, {len(tp)} pairs;"
+              f" repeats {' '.join(f'{sum(x):.2f}' for x in u)})", flush=True)
+    f, r, w = min(t, key=sum)
+    ti = tb.tiled_info()
+    print(f"{'':44s} {mname:14s} traced (tiled):{f + r + w:7.2f} ms {tcells / (f + r + w) / 1e6:8.1f} GCUPS {len(tp) / (f + r + w) * 1e3:12.0f} pairs/s"
+          f"  (forward {f:.2f} ms, fills {r:.2f} ms, walks {w:.2f} ms, {ti['chunks']} chunks, {ti['rounds']} rounds, {ti['tile_jobs']} tile jobs,"
+          f" {ti['refill_cells'] / tcells:.3f} of the cells filled, {ti['chunk_bytes_max'] / 2**20:.1f} MiB, {len(tp)} pairs{note};"
+          f" repeats {' '.join(f'{sum(x):.2f}' for x in t)})", flush=True)
+    tb.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="reads,10k,100k")
-    ap.add_argument("--trace-100k", action="store_true", help="also trace the 100 kbp pairs (10 GB of codes each)")
+    ap.add_argument("--trace-100k", action="store_true", help="also trace the 100 kbp pairs untiled (10 GB of codes each)")
+    ap.add_argument("--tile-cols", type=int, default=0, help="columns of a tile of the tiled route (0: the library's default)")
+    ap.add_argument("--reps", type=int, default=3, help="timed repeats of each traced route")
     ap.add_argument("--trace-pairs", type=int, default=512, help="traced runs of the 10 kbp shape use this many of its pairs")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -151,18 +185,15 @@ def main():
                     f"  (waves {info['waves']}, lane use {info['lane_use']:.3f})")
             print(line, flush=True)
             b.close()
-            if trace:
-                tp = pairs[: args.trace_pairs] if sname == "10k" else pairs
-                tcells = float(sum(len(x) * len(y) for x, y in tp))
-                tb = AffineBatch(tp, cm, trace=True)
-                tb.align()
-                f, t = tb.last_forward_ms, tb.last_trace_ms
-                print(f"{'':44s} {mname:14s} traced:    {f + t:10.2f} ms {tcells / (f + t) / 1e6:8.1f} GCUPS {len(tp) / (f + t) * 1e3:12.0f} pairs/s"
-                      f"  (forward {f:.2f} ms = {tcells / f / 1e6:.1f} GCUPS, walks {t:.2f} ms, {tb.info()['trace_chunks']} chunks, {len(tp)} pairs)",
-                      flush=True)
-                tb.close()
+            if sname == "10k":
+                traced(pairs[: args.trace_pairs], cm, mname, True, args.tile_cols, args.reps)
+                traced(pairs, cm, mname, False, args.tile_cols, args.reps)
+            elif sname == "100k":
+                if not trace:
+                    print(f"{'':44s} {mname:14s} traced:    not measured", flush=True)
+                traced(pairs, cm, mname, trace, args.tile_cols, 1, warm=False, note=", unwarmed")
             else:
-                print(f"{'':44s} {mname:14s} traced:    not measured", flush=True)
+                traced(pairs, cm, mname, True, args.tile_cols, args.reps)
             if L is not None:
                 done, c0, t0 = 0, 0.0, time.perf_counter()
                 for x, y in pairs:
