@@ -808,7 +808,7 @@ static pa_batch* batch_create(const BatchInput& in, bool trace, float band_hint 
     clock.mark("jobs + descriptors");
     if (cr.slice_rows) {
         p->sequential = false;
-        p->sliced = slice::create(p->n.data(), p->m.data(), in.pairs, p->code_off.data(), p->prof_off.data(), cr.slice_rows);
+        p->sliced = slice::create(p->n.data(), p->m.data(), in.pairs, p->a_off.data(), p->b_off.data(), cr.slice_rows);
         if (!p->sliced) return nullptr;
         clock.mark("bit-sliced plan");
     }
@@ -1107,12 +1107,17 @@ extern "C" int pa_batch_run(pa_batch* p, int32_t* cost_out, float* kernel_ms) {
         return rc;
     }
     hipStream_t s = p->stream;
-    if (p->sliced) {  // groups of 32 pairs, bit-sliced: profiles as always, then slice_unit.hip; d_sums receives the distances themselves
-        if (const int rc = batch_forward(p, false)) return rc;
-        if (const int rc = slice::run(p->sliced, s, p->d_codes.as<uint32_t>(), p->d_prof.as<uint64_t>(), p->d_sums.as<int32_t>(), p->d_misc.as<uint32_t>() + 4,
-                                      p->ev0, p->ev1))
+    if (p->sliced) {  // groups of 32 pairs, bit-sliced (slice_unit.hip); d_sums receives the distances themselves
+        // no encode kernels: the transposes read the sequences themselves.  What batch_forward sets up of the rest: d_misc (ticket, err, -,
+        // the bad-base flag, the sliced kernel's ticket and err) and d_sums start from zero
+        if (!hip_ok(hipMemsetAsync(p->d_misc.ptr, 0, 32, s), "memset") ||
+            !hip_ok(hipMemsetAsync(p->d_sums.ptr, 0, std::max<size_t>(p->pairs * 4, 16), s), "memset sums"))
+            return PA_E_HIP;
+        if (const int rc = slice::run(p->sliced, s, p->d_a.as<uint8_t>(), p->d_b.as<uint8_t>(), p->d_misc.as<uint32_t>() + 3, p->d_sums.as<int32_t>(),
+                                      p->d_misc.as<uint32_t>() + 4, p->ev0, p->ev1))
             return rc;
         if (const int rc = read_sums_and_errors(p, cost_out, 5, "device spin timeout in the bit-sliced kernel (err=%u)")) return rc;
+        slice::mark_clean(p->sliced);  // clean finish: every boundary row was handed back reset
         if (kernel_ms && !hip_ok(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1), "elapsed")) return PA_E_HIP;
         for (size_t i = 0; i < p->pairs; ++i)  // (a pair with an empty sequence is in no group)
             if (p->n[i] == 0 || p->m[i] == 0) cost_out[i] = (int32_t)(p->n[i] + p->m[i]);

@@ -142,6 +142,12 @@ bool build_b_device(const uint8_t* d_b, int m, uint64_t* d_prof, uint32_t* d_bad
 bool encode_pair_device(const uint8_t* d_a, int n, uint32_t* d_codes, int code_words, const uint8_t* d_b, int m, uint64_t* d_prof, uint32_t* bad,
                         hipStream_t s);
 // Batched forms (all pairs of a pa_batch): where each pair's sequences, codes and profile lie in the concatenated buffers.
+// rank in "ACGT" (bio RankTransform as used by BitProfile::build, profile.rs:113); -1 otherwise.  Shared by the encode kernels
+// (rect_unit.hip) and the bit-sliced batch's transposes (slice_kernel.hpp), which read the sequences themselves.
+__device__ __forceinline__ int rank_acgt(uint8_t c) {
+    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
+}
+
 struct PairDesc {
     unsigned long long a_off, b_off, code_off, prof_off;  // element offsets into the concatenated buffers
     int n, m;

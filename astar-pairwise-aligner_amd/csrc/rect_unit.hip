@@ -14,11 +14,6 @@ namespace pa {
 
 // ---- device kernels: profile building ---------------------------------------------------------
 
-// rank in "ACGT" (bio RankTransform as used by BitProfile::build, profile.rs:113); -1 otherwise
-__device__ __forceinline__ int rank_acgt(uint8_t c) {
-    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
-}
-
 // One thread per 16 columns: ASCII -> packed 2-bit codes.
 __global__ void encode_a_kernel(const uint8_t* __restrict__ a, int n, uint32_t* __restrict__ codes, int nwords,
                                 uint32_t* __restrict__ bad) {

@@ -25,7 +25,7 @@
 // wavefront are skewed one column per lane (lane l works on column t - l at step t), so a STRIP is 64 R rows; the bottom row's (hp, hm)
 // goes to the next lane through one DPP wave_shr:1 each per step.  Strips of a group hand their bottom row down through HBM, 8 bytes per
 // column -- (hp, hm) of the 32 pairs -- and run CONCURRENTLY one behind the other: a consumer polls the value itself ("data is the flag",
-// MI355X_MICROARCH.md R2: a boundary row is preset to hp = hm = ~0, which no real delta pair can be).  Jobs (group, strip) are claimed by an
+// MI355X_MICROARCH.md R2: a boundary row is preset to hp = hm = ~0, which no real delta pair can be, and the consumer puts that value back).  Jobs (group, strip) are claimed by an
 // atomic ticket in producer-before-consumer order, so a consumer's producer has always started; every poll is bounded.
 //
 // The step: 7 R + 11 VALU instructions in ONE basic block that every lane runs in every step -- eight DPP instructions (PA_SLICE_FEED), the
@@ -74,7 +74,7 @@ struct SliceJob {
     uint32_t group, strip;
 };
 struct SlicePair {  // per position of the sorted order
-    uint64_t code_off, prof_off;  // into the batch's packed codes (u32, 16 columns each) / profile (two u64 per 64 rows)
+    uint64_t a_off, b_off;  // byte offsets of the pair's a and b in the batch's concatenated sequences (16-byte aligned, padded to 16)
     int32_t n, m;
     uint32_t pair;  // index of the pair in the batch (where its cost goes)
     uint32_t pad_;
@@ -132,6 +132,24 @@ __device__ __forceinline__ void st_boundary(uint2* p, uint32_t hp, uint32_t hm) 
               [hmp_] "v"(hmp));                                                                                                         \
     } while (0)
 
+// One row alone: the seven instructions of row A above, same immediates, same operand order -- the last row of a lane whose number of rows
+// is odd (tests/test_slice_row_one_logic.py interprets this asm the way the pair's is).  Its z (zA -> hm) reads the instruction just
+// before it twice; that is one row in R.
+#define PA_SLICE_ROW_ONE(vpA, vmA, nb0A, nb1A, a0, a1, hpp, hmp, hpo, hmo)                                                              \
+    do {                                                                                                                                \
+        uint32_t zA_;                                                                                                                   \
+        asm volatile(                                                                                                                   \
+            "v_xor_b32 %[zA], %[a1_], %[nb1A_]\n\t"                                                                                     \
+            "v_bitop3_b32 %[zA], %[a0_], %[nb0A_], %[zA] bitop3:0x28\n\t"                                                               \
+            "v_bitop3_b32 %[zA], %[zA], %[vmA_], %[hmp_] bitop3:0xfe\n\t"                                                               \
+            "v_and_b32 %[hmA], %[zA], %[vpA_]\n\t"                                                                                      \
+            "v_bitop3_b32 %[hpA], %[vmA_], %[zA], %[vpA_] bitop3:0xf1\n\t"                                                              \
+            "v_bitop3_b32 %[vpA_], %[hmp_], %[zA], %[hpp_] bitop3:0xf1\n\t"                                                             \
+            "v_and_b32 %[vmA_], %[hpp_], %[zA]"                                                                                          \
+            : [zA] "=&v"(zA_), [hmA] "=&v"(hmo), [hpA] "=&v"(hpo), [vpA_] "+v"(vpA), [vmA_] "+v"(vmA)                                   \
+            : [a0_] "v"(a0), [a1_] "v"(a1), [nb0A_] "v"(nb0A), [nb1A_] "v"(nb1A), [hpp_] "v"(hpp), [hmp_] "v"(hmp));                    \
+    } while (0)
+
 // The top of a step: every lane takes what the lane above it had a step ago -- the column's two code planes (a0, a1, in place) and the
 // bottom row's (hp, hm) of the column (from ohp / ohm into hpp / hmp) --, lane 0 the chunk registers' value of its own lane, and the four
 // chunk registers rotate one lane.  v_cndmask_b32_dpp does the first in ONE instruction a register: vcc = 1 selects the second source in
@@ -160,7 +178,6 @@ template <int R>
 __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict__ jobs, int njobs, const SliceGroup* __restrict__ groups,
                                                       const SliceEvent* __restrict__ events, const uint2* __restrict__ A, const uint2* __restrict__ B,
                                                       uint2* H, uint2* V, uint32_t* ticket_err, unsigned long long* dbg) {
-    static_assert(R % 2 == 0, "rows are stepped in pairs");
     const int lane = (int)threadIdx.x;
     const uint32_t wave_slot = (uint32_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 4) & 15u;  // HW_REG_HW_ID[3:0]: this wavefront's slot on its SIMD
     for (;;) {
@@ -281,6 +298,12 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
                     t_parked += __builtin_amdgcn_s_memrealtime() - t_p0;
                     n_parks += 1;
                 }
+                // This chunk's columns of the boundary row are consumed (they sit in cH): hand them back "not written" (hp = hm = ~0), so
+                // that the host resets the boundary rows only before a plan's first pass and after a pass that did not finish (Plan::h_dirty)
+                // -- the strip kernels' granules do the same.  Every column below n belongs to exactly one chunk and one lane of this strip,
+                // the producer wrote it once in this pass and this strip is its only reader.  One coalesced store per chunk, through to
+                // memory like the producer's; it is older than the prefetch loads below, so the wait for them covers it as well.
+                if (col < n) st_boundary(const_cast<uint2*>(Hin) + col, ~0u, ~0u);
             }
             // the next chunk's values, a whole chunk ahead of their use (issued after the test above: a wait for THIS chunk's values must not
             // cover loads that have only just been issued)
@@ -304,9 +327,15 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
                 uint32_t hpp, hmp;
                 PA_SLICE_FEED(a0, a1, hpp, hmp, o_hp, o_hm, cA.x, cA.y, cH.x, cH.y);
 #pragma unroll
-                for (int i = 0; i < R; i += 2) {
+                for (int i = 0; i + 1 < R; i += 2) {
                     uint32_t hpo, hmo;
                     PA_SLICE_ROW_PAIR(vp[i], vm[i], vp[i + 1], vm[i + 1], nb0[i], nb1[i], nb0[i + 1], nb1[i + 1], a0, a1, hpp, hmp, hpo, hmo);
+                    hpp = hpo;
+                    hmp = hmo;
+                }
+                if constexpr (R & 1) {  // an odd number of rows: the last one alone
+                    uint32_t hpo, hmo;
+                    PA_SLICE_ROW_ONE(vp[R - 1], vm[R - 1], nb0[R - 1], nb1[R - 1], a0, a1, hpp, hmp, hpo, hmo);
                     hpp = hpo;
                     hmp = hmo;
                 }
@@ -353,21 +382,41 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
     }
 }
 
-// ---- transposes: the batch's packed 2-bit codes of a (16 columns per u32) and the profile of b (the reference's negated bit planes, two u64
-//      per 64 rows: profile.rs:127-132) -> bit planes over the 32 pairs of a group ----
+// ---- transposes: the batch's sequences as uploaded (ASCII; every pair's a and b start 16-byte aligned and are padded to 16 bytes in the
+//      concatenated buffers: layout_pairs) -> bit planes over the 32 pairs of a group.  A sliced batch runs no encode kernels: the bytes are
+//      read once, here, ranked with the encode kernels' rank_acgt, and a byte outside ACGT ORs the batch's bad-base word as it does there.
+//      Bytes at or beyond a pair's length count for nothing, neither for the planes nor as invalid.  blockIdx.x = block of columns / rows
+//      (the long dimension), blockIdx.y = group. ----
 
-// one wavefront: 32 columns (two code words per pair; lanes 0..31 = the group's pairs for the first word, lanes 32..63 for the second)
-__global__ __launch_bounds__(256) void slice_pack_a_kernel(const SliceGroup* __restrict__ groups, const SlicePair* __restrict__ spairs,
-                                                           const uint32_t* __restrict__ codes, uint2* __restrict__ A) {
-    const SliceGroup grp = groups[blockIdx.x];
-    const int lane = (int)(threadIdx.x & 63), q = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));  // columns [32 q, 32 q + 32)
-    if (q * 32 >= grp.n) return;
-    const int p = lane & 31, half = lane >> 5, word = 2 * q + half;
+// 16 bases -> 2-bit codes, position k at bits 2 k (an invalid one as code 3, like encode_a_batch_kernel); `count` of them are real
+__device__ __forceinline__ uint32_t slice_rank16(const uint4 v, int count, bool& invalid) {
+    const uint32_t q[4] = {v.x, v.y, v.z, v.w};
     uint32_t w = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int r = rank_acgt((uint8_t)(q[k >> 2] >> (8 * (k & 3))));
+        if (k < count) {
+            invalid |= r < 0;
+            w |= (uint32_t)(r & 3) << (2 * k);
+        }
+    }
+    return w;
+}
+
+// one wavefront: 32 columns (lane (p, half) reads the 16 bases of pair p at column 32 q + 16 half: one 16-byte load)
+__global__ __launch_bounds__(256) void slice_pack_a_kernel(const SliceGroup* __restrict__ groups, const SlicePair* __restrict__ spairs,
+                                                           const uint8_t* __restrict__ a_cat, uint2* __restrict__ A, uint32_t* __restrict__ bad) {
+    const SliceGroup grp = groups[blockIdx.y];
+    const int lane = (int)(threadIdx.x & 63), q = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));  // columns [32 q, 32 q + 32)
+    if ((long long)q * 32 >= (long long)grp.n) return;
+    const int p = lane & 31, half = lane >> 5, c0 = 32 * q + 16 * half;
+    uint32_t w = 0;
+    bool invalid = false;
     if (p < grp.npairs) {
         const SlicePair sp = spairs[grp.first_pos + p];
-        if (word < (sp.n + 15) / 16) w = codes[sp.code_off + word];
+        if (c0 < sp.n) w = slice_rank16(*(const uint4*)(a_cat + sp.a_off + c0), sp.n - c0, invalid);
     }
+    if (invalid) atomicOr(bad, 1u);
     uint32_t a0 = 0, a1 = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -381,22 +430,40 @@ __global__ __launch_bounds__(256) void slice_pack_a_kernel(const SliceGroup* __r
     if (lane < 32 && c < grp.n) A[grp.a_off + kPad + c] = make_uint2(a0, a1);
 }
 
-// one wavefront: 64 rows (one profile word per pair; lanes 0..31 take the low halves, lanes 32..63 the high halves)
+// one wavefront: 64 rows (lane (p, half) reads the 32 bases of pair p at row 64 j + 32 half: two 16-byte loads, each only if it starts
+// below |b|) -> the NEGATED code bits of the rows, as the profile has them (profile.rs:127-132); rows at or beyond |b| are (0, 0)
 __global__ __launch_bounds__(256) void slice_pack_b_kernel(const SliceGroup* __restrict__ groups, const SlicePair* __restrict__ spairs,
-                                                           const uint64_t* __restrict__ prof, uint2* __restrict__ B, int rows_per_strip) {
-    const SliceGroup grp = groups[blockIdx.x];
-    const int lane = (int)(threadIdx.x & 63), j = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));  // rows [64 j, 64 j + 64)
+                                                           const uint8_t* __restrict__ b_cat, uint2* __restrict__ B, int rows_per_strip,
+                                                           uint32_t* __restrict__ bad) {
+    const SliceGroup grp = groups[blockIdx.y];
+    const int lane = (int)(threadIdx.x & 63), j = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));  // rows [64 j, 64 j + 64)
     if ((long long)j * 64 >= (long long)grp.nstrips * rows_per_strip) return;
     const int p = lane & 31, half = lane >> 5;
+    const long long r0 = (long long)j * 64 + 32 * half;
     uint32_t x0 = 0, x1 = 0;
+    bool invalid = false;
     if (p < grp.npairs) {
         const SlicePair sp = spairs[grp.first_pos + p];
-        if (j < (sp.m + 63) / 64) {
-            const uint64_t p0 = prof[2 * (sp.prof_off + j)], p1 = prof[2 * (sp.prof_off + j) + 1];
-            x0 = (uint32_t)(p0 >> (32 * half));
-            x1 = (uint32_t)(p1 >> (32 * half));
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const long long r = r0 + 16 * h;
+            if (r < (long long)sp.m) {
+                const int count = (int)min((long long)sp.m - r, 16ll);
+                const uint32_t w = slice_rank16(*(const uint4*)(b_cat + sp.b_off + r), count, invalid);
+                // the real rows' negated code bits, de-interleaved: bit k of e / o = bit 0 / bit 1 of ~code k
+                const uint32_t real = count >= 16 ? ~0u : (1u << (2 * count)) - 1u, nw = ~w & real;
+                uint32_t e = 0, o = 0;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    e |= ((nw >> (2 * k)) & 1u) << k;
+                    o |= ((nw >> (2 * k + 1)) & 1u) << k;
+                }
+                x0 |= e << (16 * h);
+                x1 |= o << (16 * h);
+            }
         }
     }
+    if (invalid) atomicOr(bad, 1u);
     uint32_t nb0 = 0, nb1 = 0;
 #pragma unroll
     for (int k = 0; k < 32; ++k) {

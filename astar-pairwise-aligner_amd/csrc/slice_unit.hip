@@ -21,8 +21,9 @@ struct Plan {
     std::vector<SliceGroup> groups;
     std::vector<SliceJob> jobs;
     size_t a_elems = 0, b_elems = 0, h_elems = 0;
-    unsigned max_col_blocks = 0, max_row_blocks = 0;  // grid.y of the transposes
+    unsigned max_col_blocks = 0, max_row_blocks = 0;  // grid.x of the transposes (grid.y = the groups)
     double valu = 0, computed = 0;
+    bool h_dirty = false;  // the boundary rows must be reset before the next pass (a pass was queued and nobody has seen it finish)
     DeviceBuf d_groups, d_events, d_jobs, d_spairs, d_A, d_B, d_V, d_H;
 };
 
@@ -50,6 +51,7 @@ int choose_rows_per_lane(const size_t* a_len, const size_t* b_len, size_t pairs,
         if (a_len[i] >= (size_t(1) << 27) || b_len[i] >= (size_t(1) << 27)) return 0;
     }
     const bool forced = getenv("PA_SLICE") && atoi(getenv("PA_SLICE")) > 0;
+    if ((live + 31) / 32 > 65535) return 0;  // (the groups are gridDim.y of the transposes)
     if (live < 64 && !forced) return 0;
     // groups of 32 in the order of the lengths; a group costs its longest a times the strips of its longest b
     std::vector<uint32_t> order;
@@ -89,7 +91,7 @@ int choose_rows_per_lane(const size_t* a_len, const size_t* b_len, size_t pairs,
     return best_r;
 }
 
-Plan* create(const size_t* a_len, const size_t* b_len, size_t pairs, const size_t* code_off, const size_t* prof_off, int rows_per_lane) {
+Plan* create(const size_t* a_len, const size_t* b_len, size_t pairs, const size_t* a_off, const size_t* b_off, int rows_per_lane) {
     auto p = std::make_unique<Plan>();
     p->R = rows_per_lane;
     p->pairs = pairs;
@@ -114,7 +116,7 @@ Plan* create(const size_t* a_len, const size_t* b_len, size_t pairs, const size_
             const uint32_t i = order[g * 32 + t];
             n = std::max(n, a_len[i]);
             m = std::max(m, b_len[i]);
-            spairs[g * 32 + t] = SlicePair{(uint64_t)code_off[i], (uint64_t)prof_off[i], (int32_t)a_len[i], (int32_t)b_len[i], i, 0u};
+            spairs[g * 32 + t] = SlicePair{(uint64_t)a_off[i], (uint64_t)b_off[i], (int32_t)a_len[i], (int32_t)b_len[i], i, 0u};
         }
         grp.n = (int32_t)n;
         grp.nstrips = strips_for(m, R);
@@ -156,12 +158,17 @@ Plan* create(const size_t* a_len, const size_t* b_len, size_t pairs, const size_
         !hip_ok(hipMemcpy(p->d_jobs.ptr, p->jobs.data(), p->jobs.size() * sizeof(SliceJob), hipMemcpyHostToDevice), "H2D slice jobs") ||
         !hip_ok(hipMemcpy(p->d_spairs.ptr, spairs.data(), spairs.size() * sizeof(SlicePair), hipMemcpyHostToDevice), "H2D slice pairs") ||
         // the pads of the column planes are read (by lanes that are not at a column yet) and never used; they are written once all the same
-        !hip_ok(hipMemset(p->d_A.ptr, 0, a_at * 8), "memset slice A"))
+        !hip_ok(hipMemset(p->d_A.ptr, 0, a_at * 8), "memset slice A") ||
+        // boundary rows: "not written yet" = hp = hm = ~0 in every pair.  Once, here: a pass that finishes hands them back in that state
+        // (every strip resets the columns it consumed: slice_kernel.hpp), run() resets them again only after one that did not (h_dirty)
+        (h_at && !hip_ok(hipMemset(p->d_H.ptr, 0xFF, h_at * 8), "memset slice boundaries")))
         return nullptr;
     return p.release();
 }
 
 void destroy(Plan* p) { delete p; }
+
+void mark_clean(Plan* p) { p->h_dirty = false; }
 
 template <int R>
 static hipError_t launch_slice(int grid, hipStream_t s, const Plan* p, uint32_t* d_ticket_err, unsigned long long* dbg) {
@@ -170,21 +177,23 @@ static hipError_t launch_slice(int grid, hipStream_t s, const Plan* p, uint32_t*
     return hipGetLastError();
 }
 
-int run(Plan* p, hipStream_t s, const uint32_t* d_codes, const uint64_t* d_prof, int32_t* d_costs, uint32_t* d_ticket_err, hipEvent_t ev0, hipEvent_t ev1) {
+int run(Plan* p, hipStream_t s, const uint8_t* d_a, const uint8_t* d_b, uint32_t* d_bad, int32_t* d_costs, uint32_t* d_ticket_err, hipEvent_t ev0,
+        hipEvent_t ev1) {
     if (!hip_ok(hipMemsetAsync(d_ticket_err, 0, 8, s), "memset slice ticket")) return PA_E_HIP;
     if (p->groups.empty()) {
         if (ev0 && (!hip_ok(hipEventRecord(ev0, s), "event") || !hip_ok(hipEventRecord(ev1, s), "event"))) return PA_E_HIP;
         return 0;
     }
     const unsigned G = (unsigned)p->groups.size();
-    hipLaunchKernelGGL(slice_pack_a_kernel, dim3(G, p->max_col_blocks), dim3(256), 0, s, p->d_groups.as<SliceGroup>(), p->d_spairs.as<SlicePair>(), d_codes,
-                       p->d_A.as<uint2>());
-    hipLaunchKernelGGL(slice_pack_b_kernel, dim3(G, p->max_row_blocks), dim3(256), 0, s, p->d_groups.as<SliceGroup>(), p->d_spairs.as<SlicePair>(), d_prof,
-                       p->d_B.as<uint2>(), 64 * p->R);
+    hipLaunchKernelGGL(slice_pack_a_kernel, dim3(p->max_col_blocks, G), dim3(256), 0, s, p->d_groups.as<SliceGroup>(), p->d_spairs.as<SlicePair>(), d_a,
+                       p->d_A.as<uint2>(), d_bad);
+    hipLaunchKernelGGL(slice_pack_b_kernel, dim3(p->max_row_blocks, G), dim3(256), 0, s, p->d_groups.as<SliceGroup>(), p->d_spairs.as<SlicePair>(), d_b,
+                       p->d_B.as<uint2>(), 64 * p->R, d_bad);
     if (!hip_ok(hipGetLastError(), "slice transposes")) return PA_E_HIP;
     if (!hip_ok(hipMemsetAsync(p->d_V.ptr, 0, p->b_elems * 8, s), "memset slice V")) return PA_E_HIP;  // captured columns are OR-ed in
-    // boundary rows: "not written yet" = hp = hm = ~0 in every pair
-    if (p->h_elems && !hip_ok(hipMemsetAsync(p->d_H.ptr, 0xFF, p->h_elems * 8, s), "memset slice boundaries")) return PA_E_HIP;
+    // boundary rows: the pass before left them "not written yet" unless it did not finish (create(), mark_clean())
+    if (p->h_elems && p->h_dirty && !hip_ok(hipMemsetAsync(p->d_H.ptr, 0xFF, p->h_elems * 8, s), "memset slice boundaries")) return PA_E_HIP;
+    p->h_dirty = true;
     const int grid = (int)std::min<size_t>(p->jobs.size(), (size_t)device_cus() * 8);  // two wavefronts per SIMD, one wavefront per workgroup
     // diagnostics: PA_SLICE_JOBTIMES=1 prints, per pass, how long the (group, strip) jobs took their wavefronts and how much of that they slept
     static const bool jobtimes = getenv("PA_SLICE_JOBTIMES") != nullptr;
@@ -197,9 +206,13 @@ int run(Plan* p, hipStream_t s, const uint32_t* d_codes, const uint64_t* d_prof,
     hipError_t e = hipSuccess;
     switch (p->R) {
         case 52: e = launch_slice<52>(grid, s, p, d_ticket_err, dbg); break;
+        case 51: e = launch_slice<51>(grid, s, p, d_ticket_err, dbg); break;
         case 50: e = launch_slice<50>(grid, s, p, d_ticket_err, dbg); break;
+        case 49: e = launch_slice<49>(grid, s, p, d_ticket_err, dbg); break;
         case 48: e = launch_slice<48>(grid, s, p, d_ticket_err, dbg); break;
+        case 47: e = launch_slice<47>(grid, s, p, d_ticket_err, dbg); break;
         case 46: e = launch_slice<46>(grid, s, p, d_ticket_err, dbg); break;
+        case 45: e = launch_slice<45>(grid, s, p, d_ticket_err, dbg); break;
         case 44: e = launch_slice<44>(grid, s, p, d_ticket_err, dbg); break;
         case 42: e = launch_slice<42>(grid, s, p, d_ticket_err, dbg); break;
         case 40: e = launch_slice<40>(grid, s, p, d_ticket_err, dbg); break;
