@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "pa_search_batch_create", "pa_search_batch_run", "pa_search_batch_rows", "pa_search_batch_trace", "pa_search_batch_info",
     "pa_search_batch_destroy",
     "pa_affine_batch_create", "pa_affine_batch_run", "pa_affine_batch_align", "pa_affine_batch_info", "pa_affine_batch_destroy",
-    "pa_affine_batch_align_tiled", "pa_affine_batch_tiled_info",
+    "pa_affine_batch_align_tiled", "pa_affine_batch_tiled_info", "pa_affine_batch_set_chain", "pa_affine_batch_chain_info",
 ]
 
 _lib = None
@@ -103,6 +103,10 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine_batch_align_tiled.argtypes = [vp, C.c_uint32, vp, vp] + [C.POINTER(C.c_float)] * 3
         L.pa_affine_batch_tiled_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
         L.pa_affine_batch_tiled_info.restype = None
+    if hasattr(L, "pa_affine_batch_set_chain"):
+        L.pa_affine_batch_set_chain.argtypes = [vp, C.c_int]
+        L.pa_affine_batch_chain_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
+        L.pa_affine_batch_chain_info.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -533,9 +537,10 @@ class AffineCost:
 
 class AffineBatch:
     """Gap-affine global alignment of many pairs on the GPU (pa_affine_batch_*): NW::new(cm, false, false).align(a, b) of pa-base-algos
-    for every pair, a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align()."""
+    for every pair, a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align().  chain=True runs every
+    pair with |b| > 1024 on a wavefront per strip of 1024 rows in run() and align_tiled() (set_chain); the results are the same."""
 
-    def __init__(self, pairs, cm: AffineCost, trace: bool = False):
+    def __init__(self, pairs, cm: AffineCost, trace: bool = False, chain: bool = False):
         pairs = list(pairs)
         if any(not isinstance(x, bytes) or not isinstance(y, bytes) for x, y in pairs):
             raise ValueError("pairs must be (bytes, bytes)")
@@ -566,6 +571,20 @@ class AffineBatch:
         self.last_forward_ms = 0.0
         self.last_refill_ms = 0.0
         self.last_trace_ms = 0.0
+        if chain:
+            self.set_chain(True)
+
+    def set_chain(self, on: bool) -> None:
+        """Chained strips for pairs with |b| > 1024 in run() and align_tiled() (align() ignores it).  Off by default."""
+        self._check(load().pa_affine_batch_set_chain(self._h, 1 if on else 0), "pa_affine_batch_set_chain")
+
+    def chain_info(self) -> dict:
+        """The setting, and the last chained pass: pairs and strip jobs run chained, chunks, boundary-row bytes of the largest chunk."""
+        vals = [C.c_double(0) for _ in range(5)]
+        load().pa_affine_batch_chain_info(self._h, *[C.byref(v) for v in vals])
+        d = {k: int(v.value) for k, v in zip(("on", "chain_pairs", "chain_jobs", "chunks", "bnd_bytes_max"), vals)}
+        d["on"] = bool(d["on"])
+        return d
 
     def _check(self, rc: int, what: str) -> None:
         if rc == -4:
@@ -641,10 +660,13 @@ class AffineBatch:
             pass
 
 
-def align_affine(pairs, cm: AffineCost, tiled: bool = False) -> list[tuple[int, str]]:
+def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False) -> list[tuple[int, str]]:
     """[(cost, CIGAR)] of every pair under the gap-affine cost model `cm` (one traced AffineBatch); tiled=True takes the
-    bounded-memory route (AffineBatch.align_tiled), for pairs whose whole code matrix would not fit."""
-    b = AffineBatch(pairs, cm, trace=True)
+    bounded-memory route (AffineBatch.align_tiled), for pairs whose whole code matrix would not fit.  chain=True (with tiled=True only:
+    the untiled route has no chained form) chains the strips of the pairs with |b| > 1024 in the checkpoint pass."""
+    if chain and not tiled:
+        raise ValueError("chain=True needs tiled=True: the untiled traced route has no chained form")
+    b = AffineBatch(pairs, cm, trace=True, chain=chain)
     try:
         return b.align_tiled() if tiled else b.align()
     finally:

@@ -17,7 +17,8 @@
 // on strip 0, the boundary row the previous strip left in global memory (8 B per column: M, I of its last row) on the others.
 //   * Short pairs (|b| <= 64 kRows) run in SEGMENTS of g lanes (g the smallest power of two with g kRows >= |b|), 64 / g pairs per
 //     wavefront; each segment's first lane starts its own pair.  The planner sorts by (g, |a|), like seg_kernel's.
-//   * Longer pairs take a whole wavefront that runs all their strips top to bottom, one after the other.
+//   * Longer pairs take a whole wavefront that runs all their strips top to bottom, one after the other -- or, on request, a wavefront
+//     per strip (affine_chain_kernel, at the end of this file).
 // Lanes that have not reached column 0 yet compute on kInf inputs and keep kInf-ish state, so no step needs predication: only the
 // stores are guarded.
 //
@@ -488,6 +489,187 @@ __global__ __launch_bounds__(64) void affine_tile_walk_kernel(const TileJob* __r
     R.status = o.status;
     R.pad_ = 0;
     *J.state = R;
+}
+
+// ---- chained strips: every strip of a pair with |b| > 64 kRows is a job of its own, run by its own wavefront ----
+//
+// The recurrence, the lane layout and the unpredicated steps are affine_kernel's; the strips of a pair no longer run one after the other
+// but side by side, strip s + 1 a few dozen columns behind strip s.
+//   * Jobs.  A wavefront claims job `ticket++` when it starts.  The host lists every pair's strips 0, 1, .. S - 1 next to each other in
+//     that order (affine_chain_plan.hpp), so the producer of a job holds the ticket just below it.  A ticket is only ever taken by a
+//     wavefront that is already running, so whoever holds a lower ticket is running or done, never waiting for a slot on the chip:
+//     strip 0 waits for nobody, and by induction every strip's producer makes progress.  That is the whole deadlock argument, and it
+//     asks for nothing from the scheduler.  The wavefronts of a block are unrelated jobs: there is no workgroup barrier in this kernel.
+//   * Boundary rows.  Strip s < S - 1 owns a row of n + 1 8-byte values M | I << 32 (the CKPT layout of affine_kernel, for both
+//     variants).  The host fills every row with 0xFF bytes before the pass.  All-ones is never a value: M <= kInf, and
+//     I = min(M' + io, I' + ie) <= kInf + io <= 2 kInf = 2^31 with an absent io at kInf, so the high word is never 0xFFFFFFFF.  The
+//     producer's last lane stores its column's value with one relaxed agent-scope 8-byte atomic store per step, the consumer loads with
+//     the matching atomic load: the data is the flag, as in strip_kernel.hpp's granules.  (A plain load of a row that another CU writes
+//     may be served stale from this CU's caches for ever.)
+//   * Consuming.  Every 64 steps each lane loads column 64 q + lane of the row above (and the byte of a of that column); the first lane
+//     takes step t's value out of lane t & 63 with v_readlane.  Chunk q + 1 is requested while chunk q is consumed.  A chunk with an
+//     all-ones value in it is polled out of line (chain_wait), with resolve_granule's back-off and its bound on the wall clock.
+//   * Bounded wait.  On a timeout the wavefront sets the launch's error word and leaves; every poll also reads that word and leaves when
+//     it is set, so one lost producer ends the launch after one timeout.  The host then reports PA_E_INTERNAL and no result is valid.
+// CKPT stores the column checkpoints of the strip's own rows exactly as affine_kernel<false, true> does; the boundary rows are the row
+// checkpoints.
+constexpr uint64_t kChainEmpty = ~uint64_t(0);                      // what the host fills the rows with
+constexpr uint64_t kChainPad = (uint64_t)kInf << 32 | kInf;         // columns past n
+static_assert(2ull * kInf < 0xFFFFFFFFull, "I <= 2 kInf: the high word of a boundary value is never all ones");
+
+struct ChainJob {
+    uint32_t pair, strip;    // pair: index into the Pair array
+    const uint64_t* bnd_in;  // strip > 0: the row of the strip above
+    uint64_t* bnd_out;       // every strip but the last: its own row
+};
+static_assert(sizeof(ChainJob) == 24, "ChainJob layout");
+
+// Columns col (<= n) of `row`, once none of them is all-ones any more.  kChainEmpty in every lane when the producer never delivered
+// (error word set by this wavefront) or when another wavefront has set the error word.  Out of line for the reason above
+// pace_top_strip: inlined, its loads share registers with the step loop's.
+__device__ __attribute__((noinline)) uint64_t chain_wait(const uint64_t* row, uint32_t col, uint32_t n, uint32_t* err) {
+    const gcu64 g = (gcu64)row;
+    const gu32 e = (gu32)err;
+    const bool in = col <= n;
+    uint64_t v = kChainPad;
+    const uint64_t t0 = wall_clock64();
+    uint32_t spins = 0;
+    for (;;) {
+        if (in) v = __hip_atomic_load(g + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__builtin_amdgcn_ballot_w64(in && v == kChainEmpty) == 0) return v;
+        if (rfl(__hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != PA_ERR_NONE) return kChainEmpty;
+        if ((++spins & 255u) == 0 && wall_clock64() - t0 > kSpinTimeoutTicks) {
+            if ((threadIdx.x & 63) == 0) __hip_atomic_store(e, (uint32_t)PA_ERR_SPIN_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return kChainEmpty;
+        }
+        const uint32_t naps = spins < 8u ? 1u : (spins < 64u ? 4u : 16u);  // resolve_granule's back-off
+        for (uint32_t k = 0; k < naps; ++k) __builtin_amdgcn_s_sleep(8);
+    }
+}
+
+// ticket_err[0]: the job ticket, ticket_err[1]: the error word; both zero at launch.
+template <bool CKPT>
+__global__ __launch_bounds__(64 * kBlockWaves) void affine_chain_kernel(const ChainJob* __restrict__ jobs, int njobs, const Pair* __restrict__ pairs,
+                                                                        Costs C, uint32_t tile_cols, uint32_t* ticket_err,
+                                                                        int32_t* __restrict__ cost_out) {
+    const int lane = (int)(threadIdx.x & 63);
+    uint32_t tk = 0;
+    if (lane == 0) tk = __hip_atomic_fetch_add(ticket_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tk = rfl(tk);
+    if (tk >= (uint32_t)njobs) return;
+    const ChainJob J = jobs[tk];
+    const Pair P = pairs[J.pair];
+    const int s = (int)J.strip;
+    const int n = (int)P.n;
+    const uint32_t m = P.m;
+    const gcu8 ga = (gcu8)P.a;
+    const gcu8 gb = (gcu8)P.b;
+    const gi32 out = (gi32)cost_out;
+    const gcu64 bin = (gcu64)J.bnd_in;
+    const gu64 bout = (gu64)J.bnd_out;
+    const gu64 ck_col = (gu64)P.codes;
+    const gu64 ck_row0 = CKPT && P.n ? ck_col + (size_t)((P.n - 1) / tile_cols) * P.H : ck_col;
+    const bool below = s > 0;  // the row above is another strip's
+    const bool first = lane == 0, last = lane == 63;
+    const bool top = first && !below;
+    const uint32_t j0 = (uint32_t)(64 * s + lane) * kRows;
+    uint32_t bk[kRows], Mp[kRows], Dp[kRows];
+#pragma unroll
+    for (int k = 0; k < kRows; ++k) {
+        bk[k] = j0 + k < m ? (uint32_t)gb[j0 + k] : 0x200u;
+        Mp[k] = kInf;
+        Dp[k] = kInf;
+    }
+    const int T = n + 64;  // the last lane reaches column n at step n + 63
+    int next_ck = (int)tile_cols;
+    uint32_t kck = 0;
+    uint32_t r0M = kInf, r0D = kInf;
+    uint32_t topPrev = kInf;
+    uint32_t outM = kInf, outI = kInf, outC = 0x100u;
+    // this lane's column of the next chunk: the byte of a, and the value of the row above
+    uint32_t ac_next = lane >= 1 && lane <= n ? (uint32_t)ga[lane - 1] : 0x100u;
+    uint64_t pre = kChainPad;
+    if (below && lane <= n) pre = __hip_atomic_load(bin + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        uint64_t cur = pre;
+        if (below && t0 <= n) {
+            if (__builtin_amdgcn_ballot_w64(t0 + lane <= n && cur == kChainEmpty) != 0) {
+                cur = chain_wait(J.bnd_in, (uint32_t)(t0 + lane), (uint32_t)n, ticket_err + 1);
+                if (rfl((uint32_t)(cur >> 32)) == 0xFFFFFFFFu) return;  // lane 0's column is in range: all-ones there is chain_wait's failure
+            }
+            const int c = t0 + 64 + lane;
+            pre = kChainPad;
+            if (c <= n) pre = __hip_atomic_load(bin + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        const uint32_t ac = ac_next;
+        {
+            const int c = t0 + 64 + lane;
+            ac_next = c <= n ? (uint32_t)ga[c - 1] : 0x100u;
+        }
+        const uint32_t curM = (uint32_t)cur, curI = (uint32_t)(cur >> 32);
+        const int t1 = t0 + 64 < T ? t0 + 64 : T;
+        for (int t = t0; t < t1; ++t) {
+            const int i = t - lane;  // column
+            const bool active = i >= 0 && i <= n;
+            const int u = t - t0;
+            const uint32_t fC = (uint32_t)__builtin_amdgcn_readlane((int)ac, u);
+            uint32_t fM, fI;
+            if (below) {
+                fM = (uint32_t)__builtin_amdgcn_readlane((int)curM, u);
+                fI = (uint32_t)__builtin_amdgcn_readlane((int)curI, u);
+            } else {  // row 0 of column t, the same in every lane
+                const uint32_t nd = umin3(r0M + C.dopen, r0D + C.de, kInf);
+                const uint32_t nm = t == 0 ? 0u : umin3(r0M + C.del, nd + C.de, kInf);
+                r0M = nm;
+                r0D = nd;
+                fM = nm;
+                fI = kInf;
+            }
+            const uint32_t inM = dpp_wave_shr1(fM, outM);  // the first lane keeps the `old` operand
+            const uint32_t inI = dpp_wave_shr1(fI, outI);
+            const uint32_t inC = dpp_wave_shr1(fC, outC);
+            uint32_t Mdiag = topPrev;
+            topPrev = inM;
+            uint32_t Mup = inM, Iup = inI;
+#pragma unroll
+            for (int k = 0; k < kRows; ++k) {
+                const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
+                const uint32_t iop = Mup + C.io;
+                const uint32_t I = umin(iop, Iup + C.ie);
+                const uint32_t dop = Mp[k] + C.dopen;
+                const uint32_t D = umin(dop, Dp[k] + C.de);
+                const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del, cI = I + C.ie, cD = D + C.de;
+                const uint32_t M = umin(umin3(cd, ci, cdl), umin3(cI, cD, kInf));
+                Mdiag = Mp[k];
+                Mp[k] = M;
+                Dp[k] = D;
+                Mup = M;
+                Iup = I;
+            }
+            if (active) {
+                if (last && bout) __hip_atomic_store(bout + i, (uint64_t)Iup << 32 | Mup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (CKPT && i == next_ck) {
+                    if (i < n) {
+                        const gu64 col = ck_col + (size_t)kck * P.H + j0;
+#pragma unroll
+                        for (int k = 0; k < kRows; ++k) col[k] = (uint64_t)Dp[k] << 32 | Mp[k];
+                        if (top) ck_row0[kck] = (uint64_t)r0D << 32 | r0M;
+                    }
+                    next_ck += (int)tile_cols;
+                    ++kck;
+                }
+                if (i == n && m > j0 && m <= j0 + kRows) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
+                    out[P.out] = (int32_t)v;
+                }
+            }
+            outM = Mup;
+            outI = Iup;
+            outC = inC;
+        }
+    }
 }
 
 }  // namespace affine

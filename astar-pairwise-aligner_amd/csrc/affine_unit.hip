@@ -6,10 +6,13 @@
 // wavefront each, most expensive waves first.  align() re-runs the pairs with affine_kernel<true> in chunks whose traceback codes (one
 // byte per cell) fit a device-memory budget, and walks every pair's codes on the GPU (affine_walk_kernel).  align_tiled() gives the same
 // CIGARs in bounded memory: a cost-only pass that keeps checkpoints (affine_ckpt_kernel), then rounds that re-fill the one tile of codes
-// each unfinished pair's walk stands in (affine_tile_kernel) and walk it (affine_tile_walk_kernel).
+// each unfinished pair's walk stands in (affine_tile_kernel) and walk it (affine_tile_walk_kernel).  set_chain(1) sends the pairs with
+// |b| > 1024 through affine_chain_kernel in run() and in align_tiled()'s checkpoint pass: a wavefront per strip, the strips of a pair
+// chained through their boundary rows (planned by affine_chain_plan.hpp).
 #include "pa_hip_internal.hpp"
 #include "engine.hpp"
 #include "affine_kernel.hpp"
+#include "affine_chain_plan.hpp"
 #include "../../include/pa_affine_hip.h"
 
 #include <algorithm>
@@ -59,6 +62,15 @@ struct pa_affine_batch {
     struct {
         double chunks = 0, rounds = 0, tile_jobs = 0, refill_cells = 0, chunk_bytes_max = 0;
     } tiled;  // the last align_tiled()
+    // The chained route (set_chain): the packed pairs keep a plan of their own, the others are listed in planner order.
+    struct {
+        bool on = false, built = false;
+        std::vector<uint32_t> ids;  // pairs with |b| > 1024, in planner order
+        Plan packed;                // the plan of the rest
+        DeviceBuf d_pairs;          // Pair of every id
+        DeviceBuf d_jobs, d_bnd, d_ticket_err;
+        double pairs = 0, jobs = 0, chunks = 0, bnd_bytes_max = 0;  // the last chained pass
+    } chain;
 };
 
 namespace {
@@ -181,6 +193,109 @@ struct Events {
     }
 };
 
+// The chained launch over jobs [0, njobs) of d_jobs: ticket and error word cleared and the boundary rows set to all-ones on the stream first.
+template <bool CKPT>
+bool launch_chain(const pa_affine_batch& ab, const ChainJob* d_jobs, size_t njobs, const Pair* d_pairs, uint32_t tile_cols, void* rows, size_t row_bytes,
+                  uint32_t* d_ticket_err, hipStream_t s) {
+    if (njobs == 0) return true;
+    if (!hip_ok(hipMemsetAsync(d_ticket_err, 0, 8, s), "hipMemsetAsync") || (row_bytes && !hip_ok(hipMemsetAsync(rows, 0xFF, row_bytes, s), "hipMemsetAsync")))
+        return false;
+    const int grid = (int)((njobs + kBlockWaves - 1) / kBlockWaves);
+    hipLaunchKernelGGL(affine_chain_kernel<CKPT>, dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs, (int)njobs, d_pairs, ab.C, tile_cols, d_ticket_err,
+                       ab.d_cost.as<int32_t>());
+    return hip_ok(hipGetLastError(), CKPT ? "affine_chain_kernel<CKPT> launch" : "affine_chain_kernel launch");
+}
+
+// The device jobs of a plan's chunk, its rows at `rows`, pair p of the plan at pair index pair0 + p of the kernel's Pair array.
+void chain_jobs_of(const affine_chain::Plan& cp, const affine_chain::Chunk& c, const std::vector<affine_chain::Shape>& shapes, uint64_t* rows,
+                   uint32_t pair0, std::vector<ChainJob>& jobs) {
+    for (size_t j = c.first_job; j < c.first_job + c.njobs; ++j) {
+        const affine_chain::Job& q = cp.jobs[j];
+        const size_t S = affine_chain::strips_of(shapes[q.pair].m), w = affine_chain::row_words(shapes[q.pair].n);
+        uint64_t* row0 = rows + cp.row_off[q.pair];
+        ChainJob J;
+        J.pair = pair0 + q.pair;
+        J.strip = q.strip;
+        J.bnd_in = q.strip ? row0 + (size_t)(q.strip - 1) * w : nullptr;
+        J.bnd_out = q.strip + 1 < S ? row0 + (size_t)q.strip * w : nullptr;
+        jobs.push_back(J);
+    }
+}
+
+int chain_failed(const char* fn, uint32_t err) {
+    return fail(PA_E_INTERNAL, "%s: chained route: a strip never received its boundary row (device spin timeout, err=%u); no result of this call is valid", fn,
+                err);
+}
+
+// What set_chain(1) needs once: the chained pairs, their Pair array and the plan of the packed rest.
+int chain_build(pa_affine_batch& ab, hipStream_t s) {
+    if (ab.chain.built) return 0;
+    std::vector<uint32_t> rest;
+    ab.chain.ids.clear();  // (an earlier attempt may have failed half-way)
+    for (const uint32_t p : ab.order) (ab.m[p] > kStripRows ? ab.chain.ids : rest).push_back(p);
+    std::vector<Pair> pairs;
+    const uint8_t* seq = ab.d_seq.as<uint8_t>();
+    for (const uint32_t p : ab.chain.ids) {
+        Pair Q;
+        std::memset(&Q, 0, sizeof Q);
+        Q.a = seq + ab.aoff[p];
+        Q.b = seq + ab.boff[p];
+        Q.n = ab.n[p];
+        Q.m = ab.m[p];
+        Q.H = (uint32_t)rows_of(ab.m[p]);
+        Q.out = p;
+        pairs.push_back(Q);
+    }
+    if (!upload(ab.chain.d_pairs, pairs.data(), pairs.size() * sizeof(Pair), s) || !ab.chain.d_ticket_err.alloc(16)) return PA_E_HIP;
+    if (!ab.chain.ids.empty())  // (without chained pairs run() keeps the batch's own plan)
+        if (const int rc = make_plan(ab, rest, ab.chain.packed, nullptr, s)) return rc;
+    if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
+    ab.chain.built = true;
+    return 0;
+}
+
+// run() with chaining on: the packed pairs' launch, then the chained pairs in chunks whose boundary rows fit the budget.
+int run_chained(pa_affine_batch& ab, Events& ev, hipStream_t s, uint32_t* err_out) {
+    ab.chain.pairs = ab.chain.jobs = ab.chain.chunks = ab.chain.bnd_bytes_max = 0;
+    *err_out = 0;
+    if (ab.chain.ids.empty()) {
+        if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(ab, ab.fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event")) return PA_E_HIP;
+        return 0;
+    }
+    std::vector<affine_chain::Shape> shapes;
+    for (const uint32_t p : ab.chain.ids) shapes.push_back(affine_chain::Shape{ab.n[p], ab.m[p]});
+    const size_t budget = trace_budget("PA_AFFINE_TRACE_BUDGET_MB");
+    const affine_chain::Plan cp = affine_chain::plan(shapes, budget);
+    if (cp.refused >= 0)
+        return fail(PA_E_ARG, "pa_affine_batch_run: pair %u: %zu bytes of boundary rows of the chained route exceed the budget of %zu bytes",
+                    ab.chain.ids[(size_t)cp.refused], affine_chain::pair_words(shapes[(size_t)cp.refused]) * 8, budget);
+    if (!ab.chain.d_bnd.reserve(std::max<size_t>(cp.words_max * 8, 16))) return PA_E_HIP;
+    std::vector<ChainJob> jobs;
+    jobs.reserve(cp.jobs.size());
+    for (const affine_chain::Chunk& c : cp.chunks) chain_jobs_of(cp, c, shapes, ab.chain.d_bnd.as<uint64_t>(), 0, jobs);
+    if (!ab.chain.d_jobs.reserve(jobs.size() * sizeof(ChainJob)) ||
+        !hip_ok(hipMemcpyAsync(ab.chain.d_jobs.ptr, jobs.data(), jobs.size() * sizeof(ChainJob), hipMemcpyHostToDevice, s), "H2D") ||
+        !hip_ok(hipStreamSynchronize(s), "sync") ||  // (jobs is pageable memory of this call)
+        !hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(ab, ab.chain.packed, s))
+        return PA_E_HIP;
+    std::vector<uint32_t> errs(cp.chunks.size(), 0);
+    for (size_t k = 0; k < cp.chunks.size(); ++k) {
+        const affine_chain::Chunk& c = cp.chunks[k];
+        if (!launch_chain<false>(ab, ab.chain.d_jobs.as<ChainJob>() + c.first_job, c.njobs, ab.chain.d_pairs.as<Pair>(), 0, ab.chain.d_bnd.ptr, c.words * 8,
+                                 ab.chain.d_ticket_err.as<uint32_t>(), s) ||
+            !hip_ok(hipMemcpyAsync(&errs[k], ab.chain.d_ticket_err.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, s), "D2H"))
+            return PA_E_HIP;
+    }
+    if (!hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
+    for (const uint32_t e : errs)
+        if (e) *err_out = e;
+    ab.chain.pairs = (double)shapes.size();
+    ab.chain.jobs = (double)cp.jobs.size();
+    ab.chain.chunks = (double)cp.chunks.size();
+    ab.chain.bnd_bytes_max = (double)cp.words_max * 8;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" pa_affine_batch* pa_affine_batch_create(const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b, const size_t* b_len,
@@ -277,7 +392,12 @@ extern "C" int pa_affine_batch_run(pa_affine_batch* ab, int32_t* cost_out, float
     if (ab->np == 0) return 0;
     hipStream_t s = 0;
     Events ev;
-    if (!ev.make() || !hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(*ab, ab->fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event"))
+    if (!ev.make()) return PA_E_HIP;
+    if (ab->chain.on) {
+        uint32_t err = 0;
+        if (const int rc = run_chained(*ab, ev, s, &err)) return rc;
+        if (err) return chain_failed("pa_affine_batch_run", err);
+    } else if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(*ab, ab->fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event"))
         return PA_E_HIP;
     std::vector<int32_t> c(ab->np);
     if (!hip_ok(hipMemcpyAsync(c.data(), ab->d_cost.ptr, ab->np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
@@ -380,6 +500,7 @@ struct TiledChunk {
     std::vector<WalkState> st;
     std::vector<uint32_t> visits;
     DeviceBuf d_ck, d_tiles, d_ops, d_state, d_jobs, d_twaves;
+    DeviceBuf d_pwaves, d_cjobs;  // chained: the plan's one-strip waves, and the chain jobs of the others
 };
 
 // The chunk's buffers, the checkpoint pass, and every walk at (n, m, main).
@@ -410,13 +531,59 @@ int tiled_forward(pa_affine_batch& ab, const std::vector<uint32_t>& ids, uint32_
     for (const Wave& W : P.waves)
         if (W.strips > 1) ch.rowck[W.first] = W.bnd;
     Events ev;
-    if (!ev.make() || !upload(ch.d_state, ch.st.data(), np * sizeof(WalkState), s) || !hip_ok(hipEventRecord(ev.e[0], s), "event")) return PA_E_HIP;
-    const int grid = (int)((P.waves.size() + kBlockWaves - 1) / kBlockWaves);
-    hipLaunchKernelGGL((affine_kernel<false, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, P.d_waves.as<Wave>(), (int)P.waves.size(),
-                       P.d_pairs.as<Pair>(), ab.C, ab.d_cost.as<int32_t>());
-    if (!hip_ok(hipGetLastError(), "affine_kernel<CKPT> launch") || !hip_ok(hipEventRecord(ev.e[1], s), "event") ||
-        !hip_ok(hipStreamSynchronize(s), "sync") || !hip_ok(hipEventElapsedTime(ms, ev.e[0], ev.e[1]), "hipEventElapsedTime"))
+    if (!ev.make() || !upload(ch.d_state, ch.st.data(), np * sizeof(WalkState), s)) return PA_E_HIP;
+    const Wave* d_waves = P.d_waves.as<Wave>();
+    size_t nwaves = P.waves.size();
+    std::vector<ChainJob> cjobs;
+    size_t row_words = 0;
+    if (ab.chain.on) {  // the strip pairs leave the plan's launch for the chained one; their rows stay where make_plan put them
+        std::vector<Wave> one;
+        std::vector<affine_chain::Shape> shapes;
+        std::vector<uint32_t> at;  // index into P.pairs
+        for (const Wave& W : P.waves)
+            if (W.strips == 1) one.push_back(W);
+        for (size_t k = 0; k < np; ++k)  // (P.pairs keeps the order of ids; the waves are sorted by cost)
+            if (P.pairs[k].m > kStripRows) {
+                shapes.push_back(affine_chain::Shape{P.pairs[k].n, P.pairs[k].m});
+                at.push_back((uint32_t)k);
+            }
+        const affine_chain::Plan cp = affine_chain::plan(shapes, SIZE_MAX);  // (this chunk was cut by tiled_bytes_of, which counts the rows)
+        for (size_t x = 0; x < shapes.size(); ++x)
+            if (cp.chunks.size() != 1 || ch.rowck[at[x]] != P.d_bnd.as<uint64_t>() + cp.row_off[x] || cp.words_max != P.bnd_words)
+                return fail(PA_E_INTERNAL, "pa_affine_batch_align_tiled: chained route: the planner and the checkpoint plan disagree on pair %u's rows",
+                            P.pairs[at[x]].out);
+        if (!shapes.empty()) {
+            chain_jobs_of(cp, cp.chunks[0], shapes, P.d_bnd.as<uint64_t>(), 0, cjobs);
+            for (ChainJob& J : cjobs) J.pair = at[J.pair];
+            row_words = cp.words_max;
+            ab.chain.pairs += (double)shapes.size();
+            ab.chain.jobs += (double)cjobs.size();
+            ab.chain.chunks += 1;
+            ab.chain.bnd_bytes_max = std::max(ab.chain.bnd_bytes_max, (double)row_words * 8);
+        }
+        if (!upload(ch.d_pwaves, one.data(), one.size() * sizeof(Wave), s) || !upload(ch.d_cjobs, cjobs.data(), cjobs.size() * sizeof(ChainJob), s) ||
+            !hip_ok(hipStreamSynchronize(s), "sync"))
+            return PA_E_HIP;
+        d_waves = ch.d_pwaves.as<Wave>();
+        nwaves = one.size();
+    }
+    if (!hip_ok(hipEventRecord(ev.e[0], s), "event")) return PA_E_HIP;
+    if (nwaves) {
+        const int grid = (int)((nwaves + kBlockWaves - 1) / kBlockWaves);
+        hipLaunchKernelGGL((affine_kernel<false, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_waves, (int)nwaves, P.d_pairs.as<Pair>(), ab.C,
+                           ab.d_cost.as<int32_t>());
+        if (!hip_ok(hipGetLastError(), "affine_kernel<CKPT> launch")) return PA_E_HIP;
+    }
+    uint32_t err = 0;
+    if (!cjobs.empty() &&
+        (!launch_chain<true>(ab, ch.d_cjobs.as<ChainJob>(), cjobs.size(), P.d_pairs.as<Pair>(), C, P.d_bnd.ptr, row_words * 8,
+                             ab.chain.d_ticket_err.as<uint32_t>(), s) ||
+         !hip_ok(hipMemcpyAsync(&err, ab.chain.d_ticket_err.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, s), "D2H")))
         return PA_E_HIP;
+    if (!hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync") ||
+        !hip_ok(hipEventElapsedTime(ms, ev.e[0], ev.e[1]), "hipEventElapsedTime"))
+        return PA_E_HIP;
+    if (err) return chain_failed("pa_affine_batch_align_tiled", err);
     return 0;
 }
 
@@ -513,6 +680,7 @@ extern "C" int pa_affine_batch_align_tiled(pa_affine_batch* ab, uint32_t tile_co
     hipStream_t s = 0;
     std::vector<std::string> cigars(ab->np);
     ab->tiled = {};
+    if (ab->chain.on) ab->chain.pairs = ab->chain.jobs = ab->chain.chunks = ab->chain.bnd_bytes_max = 0;
     float fwd_total = 0, refill_total = 0, walk_total = 0;
     std::vector<TileJob> jobs;
     std::vector<TileWave> waves;
@@ -559,6 +727,24 @@ extern "C" void pa_affine_batch_tiled_info(const pa_affine_batch* ab, double* ch
     if (tile_jobs) *tile_jobs = ab ? ab->tiled.tile_jobs : 0;
     if (refill_cells) *refill_cells = ab ? ab->tiled.refill_cells : 0;
     if (chunk_bytes_max) *chunk_bytes_max = ab ? ab->tiled.chunk_bytes_max : 0;
+}
+
+extern "C" int pa_affine_batch_set_chain(pa_affine_batch* ab, int on) {
+    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_set_chain: NULL batch");
+    if (on != 0 && on != 1) return fail(PA_E_ARG, "pa_affine_batch_set_chain: on = %d is neither 0 nor 1", on);
+    if (on)
+        if (const int rc = chain_build(*ab, 0)) return rc;
+    ab->chain.on = on != 0;
+    return 0;
+}
+
+extern "C" void pa_affine_batch_chain_info(const pa_affine_batch* ab, double* on, double* chain_pairs, double* chain_jobs, double* chunks,
+                                           double* bnd_bytes_max) {
+    if (on) *on = ab && ab->chain.on ? 1 : 0;
+    if (chain_pairs) *chain_pairs = ab ? ab->chain.pairs : 0;
+    if (chain_jobs) *chain_jobs = ab ? ab->chain.jobs : 0;
+    if (chunks) *chunks = ab ? ab->chain.chunks : 0;
+    if (bnd_bytes_max) *bnd_bytes_max = ab ? ab->chain.bnd_bytes_max : 0;
 }
 
 extern "C" void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,

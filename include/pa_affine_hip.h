@@ -59,7 +59,21 @@ int pa_affine_batch_align_tiled(pa_affine_batch* ab, uint32_t tile_cols, int32_t
  * filled, summed over pairs), cells those fills computed, and the largest chunk's per-pair device bytes. */
 void pa_affine_batch_tiled_info(const pa_affine_batch* ab, double* chunks, double* rounds, double* tile_jobs, double* refill_cells,
                                 double* chunk_bytes_max);
-/* Plan shape of run(): wavefronts launched, pairs packed into segments (|b| <= 1024), pairs on strips of their own, lanes carrying rows
+/* The chained route for pairs with |b| > 1024.  on = 0 (the default): the routes above, a wavefront per such pair.  on = 1: in
+ * pa_affine_batch_run and in the checkpoint pass of pa_affine_batch_align_tiled every strip of 1024 rows of such a pair is a job of its
+ * own, run by its own wavefront, and strip s + 1 reads the last row of strip s while strip s is still writing it; pairs with |b| <= 1024
+ * keep their launch.  Costs and CIGARs are those of on = 0.  pa_affine_batch_align (a code byte per cell) has no chained form and
+ * ignores the setting.  A chained pair needs (strips - 1) * (|a| + 1) * 8 bytes of boundary rows: pa_affine_batch_run cuts the chained
+ * pairs into chunks within PA_AFFINE_TRACE_BUDGET_MB (or a quarter of the free device memory), and a pair whose rows alone exceed it is
+ * PA_E_ARG naming the pair; pa_affine_batch_align_tiled counts these rows among its checkpoints already.  A strip waits for its rows for
+ * a bounded time: should a strip never receive them, the call returns PA_E_INTERNAL, pa_last_error() names the chained route, and every
+ * cost_out and cigar_out of that call is invalid.  A NULL batch, or a value other than 0 and 1, is PA_E_ARG. */
+int pa_affine_batch_set_chain(pa_affine_batch* ab, int on);
+/* The setting, and the last chained pass (a run, or the checkpoint passes of an align_tiled, with chaining on): pairs and strip jobs it
+ * ran chained, its chunks, and the largest chunk's boundary-row bytes.  Every pointer may be NULL. */
+void pa_affine_batch_chain_info(const pa_affine_batch* ab, double* on, double* chain_pairs, double* chain_jobs, double* chunks,
+                                double* bnd_bytes_max);
+/* Plan shape of run() with chaining off (the setting does not change it): wavefronts launched, pairs packed into segments (|b| <= 1024), pairs on strips of their own, lanes carrying rows
  * of b (sum of ceil(max(|b|, 1) / 16)) over lanes launched (64 per wavefront and strip), and the chunks of the last align(). */
 void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,
                           double* trace_chunks);

@@ -1,12 +1,16 @@
 """Batched gap-affine alignment (pa_affine_batch_*): kernel time, GCUPS and pairs/s, costs only and traced, for three shapes under
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
-    python tools/affine_bench.py [--shapes reads,10k,100k] [--trace-100k] [--tile-cols C] [--reps R]
+    python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
 tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
 the line shows the fastest repeat and lists them all.  The tiled route also traces what the untiled one leaves out: all pairs of the
-10 kbp shape and the 100 kbp shape (once, unwarmed: a pass over those takes seconds)."""
+10 kbp shape and the 100 kbp shape (once, unwarmed: a pass over those takes seconds).
+
+--chain measures the chained route (AffineBatch.set_chain) instead: for each shape the cost-only pass and the tiled traced pass with
+chaining off and on, on one batch in one process, alternating, each warmed once and then R times; it prints both routes' fastest
+repeats, their ratio and chain_info().  The shape 100k1 is one 100 kbp pair."""
 from __future__ import annotations
 
 import argparse
@@ -120,10 +124,43 @@ def shape(name, rng):
             pairs.append((mutate(rng, y, 0.05), y))
         return "4096 x 10 kbp at 5 %", pairs
     pairs = []
-    for _ in range(16):
+    for _ in range(1 if name == "100k1" else 16):
         y = rand_seq(rng, 100_000)
         pairs.append((mutate(rng, y, 0.05), y))
-    return "16 x 100 kbp at 5 %", pairs
+    return f"{len(pairs)} x 100 kbp at 5 %", pairs
+
+
+def chain_legs(title, pairs, cm, mname, tile_cols, reps):
+    """Chaining off and on, alternating on one traced batch: run() and align_tiled()."""
+    cells = float(sum(len(x) * len(y) for x, y in pairs))
+    b = AffineBatch(pairs, cm, trace=True)
+    cost = {False: [], True: []}
+    tiled = {False: [], True: []}
+    results = {}
+    for rep in range(reps + 1):  # the first round warms both routes
+        for on in (False, True):
+            b.set_chain(on)
+            c = b.run()
+            k = b.last_kernel_ms
+            t = b.align_tiled(tile_cols)
+            results.setdefault("cost", c.tolist())
+            results.setdefault("tiled", t)
+            if c.tolist() != results["cost"] or t != results["tiled"]:
+                raise SystemExit(f"{title} {mname}: the chained and the unchained route disagree")
+            if rep:
+                cost[on].append(k)
+                tiled[on].append((b.last_forward_ms, b.last_refill_ms, b.last_trace_ms))
+    ci = b.chain_info()
+    b.close()
+    k0, k1 = min(cost[False]), min(cost[True])
+    print(f"{title:44s} {mname:14s} cost-only: unchained {k0:10.2f} ms {cells / k0 / 1e6:8.1f} GCUPS | chained {k1:10.2f} ms {cells / k1 / 1e6:8.1f} GCUPS"
+          f" | ratio {k0 / k1:7.2f}  (repeats {' '.join(f'{x:.2f}' for x in cost[False])} | {' '.join(f'{x:.2f}' for x in cost[True])})", flush=True)
+    (f0, r0, w0), (f1, r1, w1) = min(tiled[False], key=sum), min(tiled[True], key=sum)
+    print(f"{'':44s} {mname:14s} tiled:     unchained forward {f0:10.2f} ms, all {f0 + r0 + w0:10.2f} ms | chained forward {f1:10.2f} ms, all"
+          f" {f1 + r1 + w1:10.2f} ms | ratio forward {f0 / f1:7.2f}, all {(f0 + r0 + w0) / (f1 + r1 + w1):7.2f}"
+          f"  (fills {r1:.2f} ms, walks {w1:.2f} ms; repeats {' '.join(f'{sum(x):.2f}' for x in tiled[False])} |"
+          f" {' '.join(f'{sum(x):.2f}' for x in tiled[True])})", flush=True)
+    print(f"{'':44s} {mname:14s} chain_info: {ci}", flush=True)
 
 
 def traced(tp, cm, mname, untiled, tile_cols, reps, warm=True, note=""):
@@ -162,17 +199,23 @@ def main():
     ap.add_argument("--tile-cols", type=int, default=0, help="columns of a tile of the tiled route (0: the library's default)")
     ap.add_argument("--reps", type=int, default=3, help="timed repeats of each traced route")
     ap.add_argument("--trace-pairs", type=int, default=512, help="traced runs of the 10 kbp shape use this many of its pairs")
+    ap.add_argument("--chain", action="store_true", help="measure the chained route against the unchained one instead (see above)")
+    ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
     pa.require_gpu()
     L = cpu_lib()
     rng = np.random.default_rng(1)
     models = {"affine(4,6,2)": AffineCost.affine(4, 6, 2), "unit()": AffineCost.unit()}
+    models = {k: v for k, v in models.items() if k.split("(")[0] in args.models.split(",")}
     for sname in args.shapes.split(","):
         title, pairs = shape(sname, rng)
         cells = float(sum(len(x) * len(y) for x, y in pairs))
         for mname, cm in models.items():
-            trace = sname != "100k" or args.trace_100k
+            if args.chain:
+                chain_legs(title, pairs, cm, mname, args.tile_cols, args.reps)
+                continue
+            trace = not sname.startswith("100k") or args.trace_100k
             b = AffineBatch(pairs, cm)
             info = b.info()
             b.run()  # warm-up
@@ -188,7 +231,7 @@ def main():
             if sname == "10k":
                 traced(pairs[: args.trace_pairs], cm, mname, True, args.tile_cols, args.reps)
                 traced(pairs, cm, mname, False, args.tile_cols, args.reps)
-            elif sname == "100k":
+            elif sname.startswith("100k"):
                 if not trace:
                     print(f"{'':44s} {mname:14s} traced:    not measured", flush=True)
                 traced(pairs, cm, mname, trace, args.tile_cols, 1, warm=False, note=", unwarmed")
