@@ -41,6 +41,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "slice_job_order.hpp"
+
 namespace pa {
 namespace slice {
 
@@ -70,9 +72,7 @@ struct SliceEvent {
     int32_t col;    // capture AFTER this many columns (= |a| of the pairs in mask)
     uint32_t mask;  // the pairs (bits) whose a ends there
 };
-struct SliceJob {
-    uint32_t group, strip;
-};
+// (SliceJob, one (group, strip) unit, and the order of the job list: slice_job_order.hpp)
 struct SlicePair {  // per position of the sorted order
     uint64_t a_off, b_off;  // byte offsets of the pair's a and b in the batch's concatenated sequences (16-byte aligned, padded to 16)
     int32_t n, m;

@@ -38,6 +38,7 @@ void mark_clean(Plan* p);
 struct Info {
     int rows_per_lane;
     size_t groups, jobs;          // jobs = (group, strip) units
+    int chain;                    // strips of a group in one band of the ticket order (slice_job_order.hpp); 0 = all of them
     double valu_instructions;     // wavefront VALU instructions of the DP kernel per pass (ISA model: (7 R + kStepOverheadInstr) per strip step)
     double computed_rows_cells;   // cells actually computed (rows padded to whole strips, columns to the group's longest a)
     double device_bytes;          // the plan's own device memory

@@ -23,6 +23,7 @@ struct Plan {
     size_t a_elems = 0, b_elems = 0, h_elems = 0;
     unsigned max_col_blocks = 0, max_row_blocks = 0;  // grid.x of the transposes (grid.y = the groups)
     double valu = 0, computed = 0;
+    int chain = 0;         // strips of a group in one band of the job list (slice_job_order.hpp)
     bool h_dirty = false;  // the boundary rows must be reset before the next pass (a pass was queued and nobody has seen it finish)
     DeviceBuf d_groups, d_events, d_jobs, d_spairs, d_A, d_B, d_V, d_H;
 };
@@ -36,8 +37,29 @@ static int strips_for(size_t m, int R) { return (int)((m + (size_t)64 * R - 1) /
 // against 342.2-342.6 ms a launch = 884.3 against 855.5 ns a step; on that box a row step is 884.3 / 53.31 = 16.59 ns, so the 28.8 ns
 // that went leave 55.0 - 28.8 = 26.2 ns = 1.58 row steps = 25.6 ns at 16.2 ns a row step.
 // kChainPenalty: what a strip loses per strip of its group's chain (asleep behind the strip above, filling and draining the chain) -- 36 strips
-// of 44 rows against 32 of 50 for 16 384 x 100 kbp: 789 against 760 ms where the plain count of instructions calls it a tie.
+// of 44 rows against 32 of 50 for 16 384 x 100 kbp: 789 against 760 ms where the plain count of instructions calls it a tie.  A chain is
+// the strips of a group that are in flight together (chain_in_flight below), 8 and not 32 for the bench batch since the job list is
+// strip-major: 321.14 -> 305.98 ms (profiles/r12_runs/band_order_ab.log) is (1 + 31 p) / (1 + 7 p) at p = 0.0021, one-strip groups against
+// chains of 32 (chain_gate.log) give 0.0016, the time asleep 4.42 % / 31 = 0.0014 and 0.46 % / 7 = 0.0007: the constant stays.  It is the
+// same factor for every R of a batch now unless a group has fewer strips than fit in flight, so it ranks the sliced kernel against the
+// other batch shapes more than it chooses R.
 static constexpr double kNsPerRowStep = 16.2, kNsStepOverhead = 25.6, kChainPenalty = 0.0015;
+
+// The ticket order (slice_job_order.hpp): PA_SLICE_CHAIN=<C> asks for bands of C strips of every group, 0 = one band, group after group.
+// Unset: bands of ONE strip -- all groups' strip 0, then all groups' strip 1, .. -- which for any C is also "the bands of C, strip-major
+// within a band".  The strips of a group that run at the same time are then the automatic C of the header all the same, but they start
+// one after the other as the slots of the strips C above them fall free, a chunk or so apart, instead of all at once with C - 1 of them
+// asleep until the chain has filled: bench batch 308.6-309.1 ms a step against 311.3-311.5 with bands of 8 group-major and 323.2-324.2
+// with one band (profiles/r12_runs/band_order_ab.log).
+static constexpr int kDefaultChain = 1;
+static int chain_setting() {
+    const char* e = getenv("PA_SLICE_CHAIN");
+    return e && *e ? std::max(0, atoi(e)) : kDefaultChain;
+}
+// How many strips of a group run at the same time, one behind the other, under that order: the band, or what fits the wave slots if that is more
+static int chain_in_flight(int chain, size_t slots, size_t ngroups, int longest) {
+    return chain == 0 ? longest : std::min(std::max(chain, auto_chain(ngroups, longest, slots)), longest);
+}
 
 int choose_rows_per_lane(const size_t* a_len, const size_t* b_len, size_t pairs, double simds, double* est_ns) {
     if (const char* e = getenv("PA_SLICE")) {
@@ -64,6 +86,12 @@ int choose_rows_per_lane(const size_t* a_len, const size_t* b_len, size_t pairs,
     for (const int R : kRowsPerLane) {
         if (forced && atoi(getenv("PA_SLICE")) > 1 && atoi(getenv("PA_SLICE")) != R) continue;
         double work = 0, longest = 0, jobs = 0;
+        // the chain: the strips of a group that run at the same time, as create() will order the jobs
+        const size_t ngroups = (order.size() + 31) / 32;
+        size_t m_max = 0;
+        for (const uint32_t i : order) m_max = std::max(m_max, b_len[i]);
+        const int S_max = strips_for(m_max, R);
+        const int C = chain_in_flight(chain_setting(), (size_t)slots, ngroups, S_max);
         for (size_t g = 0; g * 32 < order.size(); ++g) {
             size_t n = 0, m = 0;
             for (size_t t = g * 32; t < std::min(order.size(), g * 32 + 32); ++t) {
@@ -71,7 +99,7 @@ int choose_rows_per_lane(const size_t* a_len, const size_t* b_len, size_t pairs,
                 m = std::max(m, b_len[order[t]]);
             }
             const int S = strips_for(m, R);
-            const double per_strip = ((double)n + 63.0) * (R * kNsPerRowStep + kNsStepOverhead) * (1.0 + kChainPenalty * (S - 1));
+            const double per_strip = ((double)n + 63.0) * (R * kNsPerRowStep + kNsStepOverhead) * (1.0 + kChainPenalty * (std::min(S, C) - 1));
             work += per_strip * S;
             jobs += S;
             longest = std::max(longest, per_strip + 128.0 * (S - 1) * (R * kNsPerRowStep + kNsStepOverhead));  // the chain of a group's strips
@@ -137,10 +165,17 @@ Plan* create(const size_t* a_len, const size_t* b_len, size_t pairs, const size_
         grp.ev_count = (uint32_t)events.size() - grp.ev_first;
         max_n = std::max(max_n, n);
         max_rows = std::max(max_rows, (size_t)grp.nstrips * 64 * R);
-        for (int s = 0; s < grp.nstrips; ++s) p->jobs.push_back(SliceJob{(uint32_t)p->groups.size(), (uint32_t)s});
         p->valu += (double)grp.nstrips * ((double)n + 63.0) * (7.0 * R + kStepOverheadInstr);
         p->computed += (double)grp.nstrips * 64.0 * R * (double)n * 32.0;
         p->groups.push_back(grp);
+    }
+    // the ticket order: bands of `chain` strips of every group; `slots` = the grid run() launches
+    {
+        std::vector<int> nstrips;
+        for (const SliceGroup& g : p->groups) nstrips.push_back(g.nstrips);
+        const size_t slots = (size_t)device_cus() * 8;
+        p->chain = chain_setting();
+        p->jobs = job_order(nstrips, slots, p->chain);
     }
     p->a_elems = a_at;
     p->b_elems = b_at;
@@ -194,7 +229,10 @@ int run(Plan* p, hipStream_t s, const uint8_t* d_a, const uint8_t* d_b, uint32_t
     // boundary rows: the pass before left them "not written yet" unless it did not finish (create(), mark_clean())
     if (p->h_elems && p->h_dirty && !hip_ok(hipMemsetAsync(p->d_H.ptr, 0xFF, p->h_elems * 8, s), "memset slice boundaries")) return PA_E_HIP;
     p->h_dirty = true;
-    const int grid = (int)std::min<size_t>(p->jobs.size(), (size_t)device_cus() * 8);  // two wavefronts per SIMD, one wavefront per workgroup
+    int grid = (int)std::min<size_t>(p->jobs.size(), (size_t)device_cus() * 8);  // two wavefronts per SIMD, one wavefront per workgroup
+    // PA_SLICE_GRID=<n> caps it (tests: a small batch then has more jobs than wavefronts, and the ticket order decides who runs beside whom)
+    const int grid_cap = getenv("PA_SLICE_GRID") ? atoi(getenv("PA_SLICE_GRID")) : 0;
+    if (grid_cap > 0) grid = std::min(grid, grid_cap);
     // diagnostics: PA_SLICE_JOBTIMES=1 prints, per pass, how long the (group, strip) jobs took their wavefronts and how much of that they slept
     static const bool jobtimes = getenv("PA_SLICE_JOBTIMES") != nullptr;
     unsigned long long* dbg = nullptr;
@@ -229,8 +267,8 @@ int run(Plan* p, hipStream_t s, const uint8_t* d_a, const uint8_t* d_b, uint32_t
             std::fprintf(stderr, "[slice jobs] awake us per job by XCD:");
             for (int x = 0; x < 8; ++x) std::fprintf(stderr, " %d: %.0f (%llu)", x, h[9 + 2 * x] ? h[8 + 2 * x] * 0.01 / (double)h[9 + 2 * x] : 0.0, h[9 + 2 * x]);
             std::fprintf(stderr, "\n");
-            std::fprintf(stderr, "[slice jobs] R %d: %llu jobs, us per job: min %.1f mean %.1f max %.1f (first strips: min %.1f max %.1f); asleep behind the strip above: %.2f %% of the job time, %.1f waits per job\n",
-                         p->R, h[3], h[0] * 0.01, h[2] * 0.01 / (double)h[3], h[1] * 0.01, h[6] * 0.01, h[7] * 0.01, 100.0 * (double)h[4] / (double)h[2], (double)h[5] / (double)h[3]);
+            std::fprintf(stderr, "[slice jobs] R %d chain %d: %llu jobs, us per job: min %.1f mean %.1f max %.1f (first strips: min %.1f max %.1f); asleep behind the strip above: %.2f %% of the job time, %.1f waits per job\n",
+                         p->R, p->chain, h[3], h[0] * 0.01, h[2] * 0.01 / (double)h[3], h[1] * 0.01, h[6] * 0.01, h[7] * 0.01, 100.0 * (double)h[4] / (double)h[2], (double)h[5] / (double)h[3]);
         }
         (void)hipFree(dbg);
     }
@@ -244,6 +282,7 @@ Info info(const Plan* p) {
     i.rows_per_lane = p->R;
     i.groups = p->groups.size();
     i.jobs = p->jobs.size();
+    i.chain = p->chain;
     i.valu_instructions = p->valu;
     i.computed_rows_cells = p->computed;
     i.device_bytes = (double)(p->a_elems + 2 * p->b_elems + p->h_elems) * 8.0;
