@@ -77,6 +77,69 @@ static_assert(sizeof(Wave) == 32, "Wave layout");
 __device__ __forceinline__ uint32_t umin(uint32_t x, uint32_t y) { return x < y ? x : y; }
 __device__ __forceinline__ uint32_t umin3(uint32_t x, uint32_t y, uint32_t z) { return umin(umin(x, y), z); }
 
+// ---- what every fill of the matrix shares (affine_kernel, affine_tile_kernel, affine_chain_kernel) ----
+
+// Row 0 of one column from (r0M, r0D) of the column before it; `origin`: the column is column 0, where M = 0.  code is the state's
+// traceback byte, for the kernels that store it.  (Costs by value here and by reference in rows_step: with these the kernels compile
+// to the instructions they had with the step written out in each of them.)
+struct Row0 {
+    uint32_t M, D, code;
+};
+__device__ __forceinline__ Row0 row0_step(const Costs C, uint32_t r0M, uint32_t r0D, bool origin) {
+    Row0 R;
+    R.D = umin3(r0M + C.dopen, r0D + C.de, kInf);
+    R.M = origin ? 0u : umin3(r0M + C.del, R.D + C.de, kInf);
+    R.code = (R.M == r0M + C.del ? 2u : 4u) | (R.D == r0M + C.dopen ? 0u : 16u);
+    return R;
+}
+
+// The recurrence over rows k = 0 .. kRows - 1 of one lane's column.  Mp / Dp hold the previous column going in and this column coming
+// out, Mdiag is M of the row above in the previous column, Mup / Iup enter as the row above in this column and leave as the lane's last
+// row.  FILL also ORs the rows' traceback bytes into code[], four to a word.
+//
+// affine_kernel<true> alone keeps this loop, and its row-0 step, written out in its body: at 229 VGPRs its instance is other machine
+// code with either of them called.  Forward pass of 512 pairs of 10 kbp under affine(4, 6, 2) on one MI355X, each form alternated three
+// times with the written-out one: 139.2 to 140.0 ms written out; 142.7 to 142.9 ms with both called (1617 instructions for 1679);
+// 145.9 to 146.4 ms with only row0_step called (one v_mov more, other registers).  Every other kernel is the same instructions
+// either way.
+template <bool FILL>
+__device__ __forceinline__ void rows_step(const Costs& C, const uint32_t (&bk)[kRows], uint32_t (&Mp)[kRows], uint32_t (&Dp)[kRows], uint32_t inC,
+                                          uint32_t Mdiag, uint32_t& Mup, uint32_t& Iup, uint32_t (&code)[kRows / 4]) {
+#pragma unroll
+    for (int k = 0; k < kRows; ++k) {
+        const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
+        const uint32_t iop = Mup + C.io;
+        const uint32_t I = umin(iop, Iup + C.ie);
+        const uint32_t dop = Mp[k] + C.dopen;
+        const uint32_t D = umin(dop, Dp[k] + C.de);
+        const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del, cI = I + C.ie, cD = D + C.de;
+        const uint32_t M = umin(umin3(cd, ci, cdl), umin3(cI, cD, kInf));
+        if (FILL) {
+            uint32_t c = M == cI ? 3u : 4u;
+            c = M == cdl ? 2u : c;
+            c = M == ci ? 1u : c;
+            c = M == cd ? 0u : c;
+            c |= I == iop ? 0u : 8u;
+            c |= D == dop ? 0u : 16u;
+            code[k >> 2] |= c << (8 * (k & 3));
+        }
+        Mdiag = Mp[k];
+        Mp[k] = M;
+        Dp[k] = D;
+        Mup = M;
+        Iup = I;
+    }
+}
+
+// One column checkpoint of a lane (CKPT, layout below): (M | D << 32) of its rows to col[0 .. kRows), and row 0's to *row0 from the lane
+// that owns row 0.
+__device__ __forceinline__ void store_col_ckpt(gu64 col, gu64 row0, const uint32_t (&Mp)[kRows], const uint32_t (&Dp)[kRows], bool top, uint32_t r0M,
+                                               uint32_t r0D) {
+#pragma unroll
+    for (int k = 0; k < kRows; ++k) col[k] = (uint64_t)Dp[k] << 32 | Mp[k];
+    if (top) *row0 = (uint64_t)r0D << 32 | r0M;
+}
+
 // CKPT, the checkpoint pass of the tiled traceback: the cost-only recurrence, which also keeps
 //   * the row checkpoints: the boundary row of every strip but the last, strip s at bnd + s (nmax + 1);
 //   * the column checkpoints, in Pair::codes as 8-byte values: (M | D << 32) of rows 1 .. H after columns C, 2C, .. < n (C = tile_cols),
@@ -140,15 +203,20 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
             if (first) {
                 inC = nextC;
                 if (top) {
-                    const uint32_t nd = umin3(r0M + C.dopen, r0D + C.de, kInf);
-                    const uint32_t nm = t == 0 ? 0u : umin3(r0M + C.del, nd + C.de, kInf);
-                    if (FILL && active) {
-                        const uint32_t code = (nm == r0M + C.del ? 2u : 4u) | (nd == r0M + C.dopen ? 0u : 16u);
-                        codes[(size_t)(n + 1) * P.H + (size_t)i] = (uint8_t)code;
+                    Row0 R;
+                    if (FILL) {  // row0_step, written out: see the note above rows_step
+                        R.D = umin3(r0M + C.dopen, r0D + C.de, kInf);
+                        R.M = t == 0 ? 0u : umin3(r0M + C.del, R.D + C.de, kInf);
+                        if (active) {
+                            const uint32_t code = (R.M == r0M + C.del ? 2u : 4u) | (R.D == r0M + C.dopen ? 0u : 16u);
+                            codes[(size_t)(n + 1) * P.H + (size_t)i] = (uint8_t)code;
+                        }
+                    } else {
+                        R = row0_step(C, r0M, r0D, t == 0);
                     }
-                    r0M = nm;
-                    r0D = nd;
-                    inM = nm;
+                    r0M = R.M;
+                    r0D = R.D;
+                    inM = R.M;
                     inI = kInf;
                 } else {
                     inM = (uint32_t)nextB;
@@ -163,16 +231,16 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
             topPrev = inM;
             uint32_t Mup = inM, Iup = inI;
             uint32_t code[kRows / 4] = {0, 0, 0, 0};  // FILL: the step's 16 code bytes
+            if (FILL) {  // rows_step<true>, written out: see the note above rows_step
 #pragma unroll
-            for (int k = 0; k < kRows; ++k) {
-                const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
-                const uint32_t iop = Mup + C.io;
-                const uint32_t I = umin(iop, Iup + C.ie);
-                const uint32_t dop = Mp[k] + C.dopen;
-                const uint32_t D = umin(dop, Dp[k] + C.de);
-                const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del, cI = I + C.ie, cD = D + C.de;
-                const uint32_t M = umin(umin3(cd, ci, cdl), umin3(cI, cD, kInf));
-                if (FILL) {
+                for (int k = 0; k < kRows; ++k) {
+                    const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
+                    const uint32_t iop = Mup + C.io;
+                    const uint32_t I = umin(iop, Iup + C.ie);
+                    const uint32_t dop = Mp[k] + C.dopen;
+                    const uint32_t D = umin(dop, Dp[k] + C.de);
+                    const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del, cI = I + C.ie, cD = D + C.de;
+                    const uint32_t M = umin(umin3(cd, ci, cdl), umin3(cI, cD, kInf));
                     uint32_t c = M == cI ? 3u : 4u;
                     c = M == cdl ? 2u : c;
                     c = M == ci ? 1u : c;
@@ -180,12 +248,14 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
                     c |= I == iop ? 0u : 8u;
                     c |= D == dop ? 0u : 16u;
                     code[k >> 2] |= c << (8 * (k & 3));
+                    Mdiag = Mp[k];
+                    Mp[k] = M;
+                    Dp[k] = D;
+                    Mup = M;
+                    Iup = I;
                 }
-                Mdiag = Mp[k];
-                Mp[k] = M;
-                Dp[k] = D;
-                Mup = M;
-                Iup = I;
+            } else {
+                rows_step<false>(C, bk, Mp, Dp, inC, Mdiag, Mup, Iup, code);
             }
             if (active) {
                 if (FILL) {
@@ -194,12 +264,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
                 }
                 if (last && s + 1 < (int)W.strips) ((gu64)(CKPT ? W.bnd + (size_t)s * bnd_stride : W.bnd))[i] = (uint64_t)Iup << 32 | Mup;
                 if (CKPT && i == next_ck) {  // lanes reach the column at different steps: each stores its own rows
-                    if (i < n) {
-                        const gu64 col = ck_col + (size_t)kck * P.H + j0;
-#pragma unroll
-                        for (int k = 0; k < kRows; ++k) col[k] = (uint64_t)Dp[k] << 32 | Mp[k];
-                        if (top) ck_row0[kck] = (uint64_t)r0D << 32 | r0M;
-                    }
+                    if (i < n) store_col_ckpt(ck_col + (size_t)kck * P.H + j0, ck_row0 + kck, Mp, Dp, top, r0M, r0D);
                     next_ck += (int)W.tile_cols;
                     ++kck;
                 }
@@ -306,36 +371,6 @@ __global__ __launch_bounds__(64) void affine_walk_kernel(const Walk* __restrict_
     outs[t] = o;
 }
 
-// affine_kernel's row loop with its codes, for affine_tile_kernel: rows k = 0 .. kRows - 1 of one lane's column.  Mp / Dp hold the previous
-// column going in and this column coming out, Mdiag is M of the row above in the previous column, Mup / Iup enter as the row above in
-// this column and leave as the lane's last row.  (affine_kernel keeps the loop in its own body: called through this function its FILL
-// instance compiles to other machine code, 1562 instructions for 1624, and which of the two is faster has not been measured.)
-__device__ __forceinline__ void fill_rows(const Costs& C, const uint32_t (&bk)[kRows], uint32_t (&Mp)[kRows], uint32_t (&Dp)[kRows], uint32_t inC,
-                                          uint32_t Mdiag, uint32_t& Mup, uint32_t& Iup, uint32_t (&code)[kRows / 4]) {
-#pragma unroll
-    for (int k = 0; k < kRows; ++k) {
-        const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
-        const uint32_t iop = Mup + C.io;
-        const uint32_t I = umin(iop, Iup + C.ie);
-        const uint32_t dop = Mp[k] + C.dopen;
-        const uint32_t D = umin(dop, Dp[k] + C.de);
-        const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del, cI = I + C.ie, cD = D + C.de;
-        const uint32_t M = umin(umin3(cd, ci, cdl), umin3(cI, cD, kInf));
-        uint32_t c = M == cI ? 3u : 4u;
-        c = M == cdl ? 2u : c;
-        c = M == ci ? 1u : c;
-        c = M == cd ? 0u : c;
-        c |= I == iop ? 0u : 8u;
-        c |= D == dop ? 0u : 16u;
-        code[k >> 2] |= c << (8 * (k & 3));
-        Mdiag = Mp[k];
-        Mp[k] = M;
-        Dp[k] = D;
-        Mup = M;
-        Iup = I;
-    }
-}
-
 // ---- the tiled traceback: re-fill one tile of codes per pair and round, walk it, resume in the next tile ----
 //
 // Tiles: row tile rt of a state (i, j) is 0 for j = 0, else (j - 1) / (64 kRows), i.e. the strip that owns row j (the one row tile of a
@@ -401,7 +436,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_tile_kernel(const Til
     }
     const bool top = first && J.rt == 0;
     const bool from_above = first && J.rt > 0;
-    uint32_t r0M = kInf, r0D = kInf;
+    uint32_t r0D = kInf, r0M = kInf;
     if (top && resume) {
         const uint64_t v = *(gcu64)J.left0;
         r0M = (uint32_t)v;
@@ -430,15 +465,11 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_tile_kernel(const Til
         if (first) {
             inC = nextC;
             if (top) {
-                const uint32_t nd = umin3(r0M + C.dopen, r0D + C.de, kInf);
-                const uint32_t nm = i == 0 ? 0u : umin3(r0M + C.del, nd + C.de, kInf);
-                if (active) {
-                    const uint32_t code = (nm == r0M + C.del ? 2u : 4u) | (nd == r0M + C.dopen ? 0u : 16u);
-                    codes[(size_t)J.row0 + (size_t)(i - cs)] = (uint8_t)code;
-                }
-                r0M = nm;
-                r0D = nd;
-                inM = nm;
+                const Row0 R = row0_step(C, r0M, r0D, i == 0);
+                if (active) codes[(size_t)J.row0 + (size_t)(i - cs)] = (uint8_t)R.code;
+                r0M = R.M;
+                r0D = R.D;
+                inM = R.M;
                 inI = kInf;
             } else {
                 inM = (uint32_t)nextB;
@@ -451,7 +482,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_tile_kernel(const Til
         topPrev = inM;
         uint32_t Mup = inM, Iup = inI;
         uint32_t code[kRows / 4] = {0, 0, 0, 0};
-        fill_rows(C, bk, Mp, Dp, inC, Mdiag, Mup, Iup, code);
+        rows_step<true>(C, bk, Mp, Dp, inC, Mdiag, Mup, Iup, code);
         if (active) {
             const u32x4 w = {code[0], code[1], code[2], code[3]};
             *reinterpret_cast<PA_GLOBAL u32x4*>(codes + (size_t)(i - cs) * J.Ht + j0) = w;
@@ -618,11 +649,10 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_chain_kernel(const Ch
                 fM = (uint32_t)__builtin_amdgcn_readlane((int)curM, u);
                 fI = (uint32_t)__builtin_amdgcn_readlane((int)curI, u);
             } else {  // row 0 of column t, the same in every lane
-                const uint32_t nd = umin3(r0M + C.dopen, r0D + C.de, kInf);
-                const uint32_t nm = t == 0 ? 0u : umin3(r0M + C.del, nd + C.de, kInf);
-                r0M = nm;
-                r0D = nd;
-                fM = nm;
+                const Row0 R = row0_step(C, r0M, r0D, t == 0);
+                r0M = R.M;
+                r0D = R.D;
+                fM = R.M;
                 fI = kInf;
             }
             const uint32_t inM = dpp_wave_shr1(fM, outM);  // the first lane keeps the `old` operand
@@ -631,30 +661,12 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_chain_kernel(const Ch
             uint32_t Mdiag = topPrev;
             topPrev = inM;
             uint32_t Mup = inM, Iup = inI;
-#pragma unroll
-            for (int k = 0; k < kRows; ++k) {
-                const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
-                const uint32_t iop = Mup + C.io;
-                const uint32_t I = umin(iop, Iup + C.ie);
-                const uint32_t dop = Mp[k] + C.dopen;
-                const uint32_t D = umin(dop, Dp[k] + C.de);
-                const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del, cI = I + C.ie, cD = D + C.de;
-                const uint32_t M = umin(umin3(cd, ci, cdl), umin3(cI, cD, kInf));
-                Mdiag = Mp[k];
-                Mp[k] = M;
-                Dp[k] = D;
-                Mup = M;
-                Iup = I;
-            }
+            uint32_t code[kRows / 4];  // (no codes here: rows_step<false> leaves it alone)
+            rows_step<false>(C, bk, Mp, Dp, inC, Mdiag, Mup, Iup, code);
             if (active) {
                 if (last && bout) __hip_atomic_store(bout + i, (uint64_t)Iup << 32 | Mup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (CKPT && i == next_ck) {
-                    if (i < n) {
-                        const gu64 col = ck_col + (size_t)kck * P.H + j0;
-#pragma unroll
-                        for (int k = 0; k < kRows; ++k) col[k] = (uint64_t)Dp[k] << 32 | Mp[k];
-                        if (top) ck_row0[kck] = (uint64_t)r0D << 32 | r0M;
-                    }
+                    if (i < n) store_col_ckpt(ck_col + (size_t)kck * P.H + j0, ck_row0 + kck, Mp, Dp, top, r0M, r0D);
                     next_ck += (int)tile_cols;
                     ++kck;
                 }

@@ -111,13 +111,25 @@ std::string cigar_of(const uint8_t* op, int32_t nops) {
     return cig.to_string();
 }
 
+// Pair p of the batch, without codes.
+Pair make_pair(const pa_affine_batch& ab, uint32_t p) {
+    Pair Q;
+    std::memset(&Q, 0, sizeof Q);
+    Q.a = ab.d_seq.as<uint8_t>() + ab.aoff[p];
+    Q.b = ab.d_seq.as<uint8_t>() + ab.boff[p];
+    Q.n = ab.n[p];
+    Q.m = ab.m[p];
+    Q.H = (uint32_t)rows_of(ab.m[p]);
+    Q.out = p;
+    return Q;
+}
+
 // Waves over `ids` (in planner order): 64 / g packed pairs of one width per wave, a wave per strip pair; then most expensive first.
 // ck_base (the checkpoint pass of the tiled traceback, tile_cols columns apart): every pair gets its column checkpoints there, and
 // every strip but the last a boundary row of its own.
 int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan& P, uint8_t* codes_base, hipStream_t s, uint64_t* ck_base = nullptr,
               uint32_t tile_cols = 0) {
     size_t ck_words = 0;
-    const uint8_t* seq = ab.d_seq.as<uint8_t>();
     std::vector<size_t> bnd_off;
     for (size_t x = 0; x < ids.size();) {
         const uint32_t p0 = ids[x];
@@ -134,14 +146,7 @@ int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan&
             const uint32_t p = ids[x];
             if ((ab.m[p] <= kStripRows) != packed || (packed && seg_lg(ab.m[p]) != lg)) break;
             ++x;
-            Pair Q;
-            std::memset(&Q, 0, sizeof Q);
-            Q.a = seq + ab.aoff[p];
-            Q.b = seq + ab.boff[p];
-            Q.n = ab.n[p];
-            Q.m = ab.m[p];
-            Q.H = (uint32_t)rows_of(ab.m[p]);
-            Q.out = p;
+            Pair Q = make_pair(ab, p);
             if (codes_base) {
                 Q.codes = codes_base + P.code_bytes;
                 P.code_bytes += code_bytes_of(Q.n, Q.m);
@@ -171,13 +176,17 @@ int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan&
     return 0;
 }
 
+// affine_kernel over nwaves device waves; a whole plan's, or (the checkpoint pass with chaining on) the one-strip waves of a plan.
+template <bool FILL, bool CKPT = false>
+bool launch(const pa_affine_batch& ab, const Wave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s) {
+    if (nwaves == 0) return true;
+    const int grid = (int)((nwaves + kBlockWaves - 1) / kBlockWaves);
+    hipLaunchKernelGGL((affine_kernel<FILL, CKPT>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_waves, (int)nwaves, d_pairs, ab.C, ab.d_cost.as<int32_t>());
+    return hip_ok(hipGetLastError(), FILL ? "affine_kernel<FILL> launch" : CKPT ? "affine_kernel<CKPT> launch" : "affine_kernel launch");
+}
 template <bool FILL>
 bool launch(const pa_affine_batch& ab, const Plan& P, hipStream_t s) {
-    if (P.waves.empty()) return true;
-    const int grid = (int)((P.waves.size() + kBlockWaves - 1) / kBlockWaves);
-    hipLaunchKernelGGL(affine_kernel<FILL>, dim3(grid), dim3(64 * kBlockWaves), 0, s, P.d_waves.as<Wave>(), (int)P.waves.size(),
-                       P.d_pairs.as<Pair>(), ab.C, ab.d_cost.as<int32_t>());
-    return hip_ok(hipGetLastError(), FILL ? "affine_kernel<FILL> launch" : "affine_kernel launch");
+    return launch<FILL>(ab, P.d_waves.as<Wave>(), P.waves.size(), P.d_pairs.as<Pair>(), s);
 }
 
 struct Events {
@@ -193,36 +202,56 @@ struct Events {
     }
 };
 
-// The chained launch over jobs [0, njobs) of d_jobs: ticket and error word cleared and the boundary rows set to all-ones on the stream first.
-template <bool CKPT>
-bool launch_chain(const pa_affine_batch& ab, const ChainJob* d_jobs, size_t njobs, const Pair* d_pairs, uint32_t tile_cols, void* rows, size_t row_bytes,
-                  uint32_t* d_ticket_err, hipStream_t s) {
-    if (njobs == 0) return true;
-    if (!hip_ok(hipMemsetAsync(d_ticket_err, 0, 8, s), "hipMemsetAsync") || (row_bytes && !hip_ok(hipMemsetAsync(rows, 0xFF, row_bytes, s), "hipMemsetAsync")))
-        return false;
-    const int grid = (int)((njobs + kBlockWaves - 1) / kBlockWaves);
-    hipLaunchKernelGGL(affine_chain_kernel<CKPT>, dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs, (int)njobs, d_pairs, ab.C, tile_cols, d_ticket_err,
-                       ab.d_cost.as<int32_t>());
-    return hip_ok(hipGetLastError(), CKPT ? "affine_chain_kernel<CKPT> launch" : "affine_chain_kernel launch");
-}
-
-// The device jobs of a plan's chunk, its rows at `rows`, pair p of the plan at pair index pair0 + p of the kernel's Pair array.
-void chain_jobs_of(const affine_chain::Plan& cp, const affine_chain::Chunk& c, const std::vector<affine_chain::Shape>& shapes, uint64_t* rows,
-                   uint32_t pair0, std::vector<ChainJob>& jobs) {
-    for (size_t j = c.first_job; j < c.first_job + c.njobs; ++j) {
-        const affine_chain::Job& q = cp.jobs[j];
+// The device jobs of a chain plan, chunk after chunk, every chunk's rows at `rows`.  Pair p of the plan is pair at[p] of the kernel's Pair
+// array (p itself without `at`).
+std::vector<ChainJob> chain_jobs_of(const affine_chain::Plan& cp, const std::vector<affine_chain::Shape>& shapes, uint64_t* rows,
+                                    const std::vector<uint32_t>* at = nullptr) {
+    std::vector<ChainJob> jobs;
+    jobs.reserve(cp.jobs.size());
+    for (const affine_chain::Job& q : cp.jobs) {
         const size_t S = affine_chain::strips_of(shapes[q.pair].m), w = affine_chain::row_words(shapes[q.pair].n);
         uint64_t* row0 = rows + cp.row_off[q.pair];
         ChainJob J;
-        J.pair = pair0 + q.pair;
+        J.pair = at ? (*at)[q.pair] : q.pair;
         J.strip = q.strip;
         J.bnd_in = q.strip ? row0 + (size_t)(q.strip - 1) * w : nullptr;
         J.bnd_out = q.strip + 1 < S ? row0 + (size_t)q.strip * w : nullptr;
         jobs.push_back(J);
     }
+    return jobs;
 }
 
-int chain_failed(const char* fn, uint32_t err) {
+// One chained pass, a launch per chunk of the plan: ticket and error word cleared and the chunk's rows (at `rows`) set to all-ones on the
+// stream, the kernel over the chunk's jobs at d_jobs (chain_jobs_of), and the copy of its error word to errs, for chain_check to read once
+// the stream is synchronised.  Counts the pass in chain.*.
+template <bool CKPT>
+bool launch_chain(pa_affine_batch& ab, const affine_chain::Plan& cp, const ChainJob* d_jobs, const Pair* d_pairs, uint32_t tile_cols, void* rows,
+                  std::vector<uint32_t>& errs, hipStream_t s) {
+    uint32_t* te = ab.chain.d_ticket_err.as<uint32_t>();
+    errs.assign(cp.chunks.size(), 0);
+    for (size_t k = 0; k < cp.chunks.size(); ++k) {
+        const affine_chain::Chunk& c = cp.chunks[k];
+        if (!hip_ok(hipMemsetAsync(te, 0, 8, s), "hipMemsetAsync") || (c.words && !hip_ok(hipMemsetAsync(rows, 0xFF, c.words * 8, s), "hipMemsetAsync")))
+            return false;
+        const int grid = (int)((c.njobs + kBlockWaves - 1) / kBlockWaves);
+        hipLaunchKernelGGL(affine_chain_kernel<CKPT>, dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs + c.first_job, (int)c.njobs, d_pairs, ab.C, tile_cols,
+                           te, ab.d_cost.as<int32_t>());
+        if (!hip_ok(hipGetLastError(), CKPT ? "affine_chain_kernel<CKPT> launch" : "affine_chain_kernel launch") ||
+            !hip_ok(hipMemcpyAsync(&errs[k], te + 1, 4, hipMemcpyDeviceToHost, s), "D2H"))
+            return false;
+    }
+    ab.chain.pairs += (double)cp.row_off.size();
+    ab.chain.jobs += (double)cp.jobs.size();
+    ab.chain.chunks += (double)cp.chunks.size();
+    ab.chain.bnd_bytes_max = std::max(ab.chain.bnd_bytes_max, (double)cp.words_max * 8);
+    return true;
+}
+
+int chain_check(const char* fn, const std::vector<uint32_t>& errs) {
+    uint32_t err = 0;
+    for (const uint32_t e : errs)
+        if (e) err = e;
+    if (!err) return 0;
     return fail(PA_E_INTERNAL, "%s: chained route: a strip never received its boundary row (device spin timeout, err=%u); no result of this call is valid", fn,
                 err);
 }
@@ -234,18 +263,7 @@ int chain_build(pa_affine_batch& ab, hipStream_t s) {
     ab.chain.ids.clear();  // (an earlier attempt may have failed half-way)
     for (const uint32_t p : ab.order) (ab.m[p] > kStripRows ? ab.chain.ids : rest).push_back(p);
     std::vector<Pair> pairs;
-    const uint8_t* seq = ab.d_seq.as<uint8_t>();
-    for (const uint32_t p : ab.chain.ids) {
-        Pair Q;
-        std::memset(&Q, 0, sizeof Q);
-        Q.a = seq + ab.aoff[p];
-        Q.b = seq + ab.boff[p];
-        Q.n = ab.n[p];
-        Q.m = ab.m[p];
-        Q.H = (uint32_t)rows_of(ab.m[p]);
-        Q.out = p;
-        pairs.push_back(Q);
-    }
+    for (const uint32_t p : ab.chain.ids) pairs.push_back(make_pair(ab, p));
     if (!upload(ab.chain.d_pairs, pairs.data(), pairs.size() * sizeof(Pair), s) || !ab.chain.d_ticket_err.alloc(16)) return PA_E_HIP;
     if (!ab.chain.ids.empty())  // (without chained pairs run() keeps the batch's own plan)
         if (const int rc = make_plan(ab, rest, ab.chain.packed, nullptr, s)) return rc;
@@ -254,14 +272,8 @@ int chain_build(pa_affine_batch& ab, hipStream_t s) {
     return 0;
 }
 
-// run() with chaining on: the packed pairs' launch, then the chained pairs in chunks whose boundary rows fit the budget.
-int run_chained(pa_affine_batch& ab, Events& ev, hipStream_t s, uint32_t* err_out) {
-    ab.chain.pairs = ab.chain.jobs = ab.chain.chunks = ab.chain.bnd_bytes_max = 0;
-    *err_out = 0;
-    if (ab.chain.ids.empty()) {
-        if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(ab, ab.fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event")) return PA_E_HIP;
-        return 0;
-    }
+// run() with chaining on and pairs to chain: the packed pairs' launch, then the chained pairs in chunks whose boundary rows fit the budget.
+int run_chained(pa_affine_batch& ab, Events& ev, hipStream_t s) {
     std::vector<affine_chain::Shape> shapes;
     for (const uint32_t p : ab.chain.ids) shapes.push_back(affine_chain::Shape{ab.n[p], ab.m[p]});
     const size_t budget = trace_budget("PA_AFFINE_TRACE_BUDGET_MB");
@@ -270,30 +282,36 @@ int run_chained(pa_affine_batch& ab, Events& ev, hipStream_t s, uint32_t* err_ou
         return fail(PA_E_ARG, "pa_affine_batch_run: pair %u: %zu bytes of boundary rows of the chained route exceed the budget of %zu bytes",
                     ab.chain.ids[(size_t)cp.refused], affine_chain::pair_words(shapes[(size_t)cp.refused]) * 8, budget);
     if (!ab.chain.d_bnd.reserve(std::max<size_t>(cp.words_max * 8, 16))) return PA_E_HIP;
-    std::vector<ChainJob> jobs;
-    jobs.reserve(cp.jobs.size());
-    for (const affine_chain::Chunk& c : cp.chunks) chain_jobs_of(cp, c, shapes, ab.chain.d_bnd.as<uint64_t>(), 0, jobs);
+    const std::vector<ChainJob> jobs = chain_jobs_of(cp, shapes, ab.chain.d_bnd.as<uint64_t>());
+    std::vector<uint32_t> errs;
     if (!ab.chain.d_jobs.reserve(jobs.size() * sizeof(ChainJob)) ||
         !hip_ok(hipMemcpyAsync(ab.chain.d_jobs.ptr, jobs.data(), jobs.size() * sizeof(ChainJob), hipMemcpyHostToDevice, s), "H2D") ||
         !hip_ok(hipStreamSynchronize(s), "sync") ||  // (jobs is pageable memory of this call)
-        !hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(ab, ab.chain.packed, s))
+        !hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(ab, ab.chain.packed, s) ||
+        !launch_chain<false>(ab, cp, ab.chain.d_jobs.as<ChainJob>(), ab.chain.d_pairs.as<Pair>(), 0, ab.chain.d_bnd.ptr, errs, s) ||
+        !hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync"))
         return PA_E_HIP;
-    std::vector<uint32_t> errs(cp.chunks.size(), 0);
-    for (size_t k = 0; k < cp.chunks.size(); ++k) {
-        const affine_chain::Chunk& c = cp.chunks[k];
-        if (!launch_chain<false>(ab, ab.chain.d_jobs.as<ChainJob>() + c.first_job, c.njobs, ab.chain.d_pairs.as<Pair>(), 0, ab.chain.d_bnd.ptr, c.words * 8,
-                                 ab.chain.d_ticket_err.as<uint32_t>(), s) ||
-            !hip_ok(hipMemcpyAsync(&errs[k], ab.chain.d_ticket_err.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, s), "D2H"))
-            return PA_E_HIP;
-    }
-    if (!hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
-    for (const uint32_t e : errs)
-        if (e) *err_out = e;
-    ab.chain.pairs = (double)shapes.size();
-    ab.chain.jobs = (double)cp.jobs.size();
-    ab.chain.chunks = (double)cp.chunks.size();
-    ab.chain.bnd_bytes_max = (double)cp.words_max * 8;
+    return chain_check("pa_affine_batch_run", errs);
+}
+
+// The costs of every pair, to the caller; the end of run(), align() and align_tiled().
+int costs_out(const pa_affine_batch& ab, int32_t* cost_out, hipStream_t s) {
+    if (ab.np == 0) return 0;
+    std::vector<int32_t> c(ab.np);
+    if (!hip_ok(hipMemcpyAsync(c.data(), ab.d_cost.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
+        return PA_E_HIP;
+    if (cost_out) std::memcpy(cost_out, c.data(), ab.np * 4);
     return 0;
+}
+
+// The next chunk of align() and align_tiled(): the pairs ab.order[c0 .. c1), as many as fit the budget by size_of(pair) and at least one;
+// *bytes is their sum.
+template <class SizeOf>
+std::vector<uint32_t> next_chunk(const pa_affine_batch& ab, size_t c0, size_t budget, SizeOf size_of, size_t* bytes) {
+    size_t c1 = c0;
+    *bytes = 0;
+    while (c1 < ab.np && (c1 == c0 || *bytes + size_of(ab.order[c1]) <= budget)) *bytes += size_of(ab.order[c1]), ++c1;
+    return std::vector<uint32_t>(ab.order.begin() + c0, ab.order.begin() + c1);
 }
 
 }  // namespace
@@ -393,17 +411,13 @@ extern "C" int pa_affine_batch_run(pa_affine_batch* ab, int32_t* cost_out, float
     hipStream_t s = 0;
     Events ev;
     if (!ev.make()) return PA_E_HIP;
-    if (ab->chain.on) {
-        uint32_t err = 0;
-        if (const int rc = run_chained(*ab, ev, s, &err)) return rc;
-        if (err) return chain_failed("pa_affine_batch_run", err);
+    if (ab->chain.on) ab->chain.pairs = ab->chain.jobs = ab->chain.chunks = ab->chain.bnd_bytes_max = 0;
+    if (ab->chain.on && !ab->chain.ids.empty()) {
+        if (const int rc = run_chained(*ab, ev, s)) return rc;
     } else if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(*ab, ab->fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event"))
         return PA_E_HIP;
-    std::vector<int32_t> c(ab->np);
-    if (!hip_ok(hipMemcpyAsync(c.data(), ab->d_cost.ptr, ab->np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
-        return PA_E_HIP;
+    if (const int rc = costs_out(*ab, cost_out, s)) return rc;
     if (kernel_ms && !hip_ok(hipEventElapsedTime(kernel_ms, ev.e[0], ev.e[1]), "hipEventElapsedTime")) return PA_E_HIP;
-    if (cost_out) std::memcpy(cost_out, c.data(), ab->np * 4);
     return 0;
 }
 
@@ -424,11 +438,8 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
     ab->trace_chunks = 0;
     float fwd_total = 0, trace_total = 0;
     DeviceBuf d_codes, d_ops, d_walk, d_wout;
-    for (size_t c0 = 0; c0 < ab->np;) {
-        size_t c1 = c0, bytes = 0;
-        while (c1 < ab->np && (c1 == c0 || bytes + code_bytes_of(ab->n[ab->order[c1]], ab->m[ab->order[c1]]) <= budget))
-            bytes += code_bytes_of(ab->n[ab->order[c1]], ab->m[ab->order[c1]]), ++c1;
-        const std::vector<uint32_t> ids(ab->order.begin() + c0, ab->order.begin() + c1);
+    for (size_t c0 = 0, bytes; c0 < ab->np;) {
+        const std::vector<uint32_t> ids = next_chunk(*ab, c0, budget, [&](uint32_t p) { return code_bytes_of(ab->n[p], ab->m[p]); }, &bytes);
         ab->trace_chunks += 1;
         if (!d_codes.reserve(std::max<size_t>(bytes, 16))) return PA_E_HIP;
         Plan P;
@@ -477,12 +488,9 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
                 return fail(PA_E_INTERNAL, "pa_affine_batch_align: pair %u: %s", P.pairs[k].out, o.status == 1 ? "bad traceback code" : "path longer than its buffer");
             cigars[P.pairs[k].out] = cigar_of(ops.data() + ops_off[k], o.nops);
         }
-        c0 = c1;
+        c0 += ids.size();
     }
-    std::vector<int32_t> c(std::max<size_t>(ab->np, 1));
-    if (ab->np && (!hip_ok(hipMemcpyAsync(c.data(), ab->d_cost.ptr, ab->np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync")))
-        return PA_E_HIP;
-    if (cost_out && ab->np) std::memcpy(cost_out, c.data(), ab->np * 4);
+    if (const int rc = costs_out(*ab, cost_out, s)) return rc;
     if (forward_ms) *forward_ms = fwd_total;
     if (trace_ms) *trace_ms = trace_total;
     return cigar_out ? give_cstrings(cigars, cigar_out) : 0;
@@ -534,8 +542,7 @@ int tiled_forward(pa_affine_batch& ab, const std::vector<uint32_t>& ids, uint32_
     if (!ev.make() || !upload(ch.d_state, ch.st.data(), np * sizeof(WalkState), s)) return PA_E_HIP;
     const Wave* d_waves = P.d_waves.as<Wave>();
     size_t nwaves = P.waves.size();
-    std::vector<ChainJob> cjobs;
-    size_t row_words = 0;
+    affine_chain::Plan cp;
     if (ab.chain.on) {  // the strip pairs leave the plan's launch for the chained one; their rows stay where make_plan put them
         std::vector<Wave> one;
         std::vector<affine_chain::Shape> shapes;
@@ -547,44 +554,25 @@ int tiled_forward(pa_affine_batch& ab, const std::vector<uint32_t>& ids, uint32_
                 shapes.push_back(affine_chain::Shape{P.pairs[k].n, P.pairs[k].m});
                 at.push_back((uint32_t)k);
             }
-        const affine_chain::Plan cp = affine_chain::plan(shapes, SIZE_MAX);  // (this chunk was cut by tiled_bytes_of, which counts the rows)
+        cp = affine_chain::plan(shapes, SIZE_MAX);  // (this chunk was cut by tiled_bytes_of, which counts the rows)
         for (size_t x = 0; x < shapes.size(); ++x)
             if (cp.chunks.size() != 1 || ch.rowck[at[x]] != P.d_bnd.as<uint64_t>() + cp.row_off[x] || cp.words_max != P.bnd_words)
                 return fail(PA_E_INTERNAL, "pa_affine_batch_align_tiled: chained route: the planner and the checkpoint plan disagree on pair %u's rows",
                             P.pairs[at[x]].out);
-        if (!shapes.empty()) {
-            chain_jobs_of(cp, cp.chunks[0], shapes, P.d_bnd.as<uint64_t>(), 0, cjobs);
-            for (ChainJob& J : cjobs) J.pair = at[J.pair];
-            row_words = cp.words_max;
-            ab.chain.pairs += (double)shapes.size();
-            ab.chain.jobs += (double)cjobs.size();
-            ab.chain.chunks += 1;
-            ab.chain.bnd_bytes_max = std::max(ab.chain.bnd_bytes_max, (double)row_words * 8);
-        }
+        const std::vector<ChainJob> cjobs = chain_jobs_of(cp, shapes, P.d_bnd.as<uint64_t>(), &at);
         if (!upload(ch.d_pwaves, one.data(), one.size() * sizeof(Wave), s) || !upload(ch.d_cjobs, cjobs.data(), cjobs.size() * sizeof(ChainJob), s) ||
             !hip_ok(hipStreamSynchronize(s), "sync"))
             return PA_E_HIP;
         d_waves = ch.d_pwaves.as<Wave>();
         nwaves = one.size();
     }
-    if (!hip_ok(hipEventRecord(ev.e[0], s), "event")) return PA_E_HIP;
-    if (nwaves) {
-        const int grid = (int)((nwaves + kBlockWaves - 1) / kBlockWaves);
-        hipLaunchKernelGGL((affine_kernel<false, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_waves, (int)nwaves, P.d_pairs.as<Pair>(), ab.C,
-                           ab.d_cost.as<int32_t>());
-        if (!hip_ok(hipGetLastError(), "affine_kernel<CKPT> launch")) return PA_E_HIP;
-    }
-    uint32_t err = 0;
-    if (!cjobs.empty() &&
-        (!launch_chain<true>(ab, ch.d_cjobs.as<ChainJob>(), cjobs.size(), P.d_pairs.as<Pair>(), C, P.d_bnd.ptr, row_words * 8,
-                             ab.chain.d_ticket_err.as<uint32_t>(), s) ||
-         !hip_ok(hipMemcpyAsync(&err, ab.chain.d_ticket_err.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, s), "D2H")))
-        return PA_E_HIP;
-    if (!hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync") ||
+    std::vector<uint32_t> errs;
+    if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false, true>(ab, d_waves, nwaves, P.d_pairs.as<Pair>(), s) ||
+        !launch_chain<true>(ab, cp, ch.d_cjobs.as<ChainJob>(), P.d_pairs.as<Pair>(), C, P.d_bnd.ptr, errs, s) ||
+        !hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync") ||
         !hip_ok(hipEventElapsedTime(ms, ev.e[0], ev.e[1]), "hipEventElapsedTime"))
         return PA_E_HIP;
-    if (err) return chain_failed("pa_affine_batch_align_tiled", err);
-    return 0;
+    return chain_check("pa_affine_batch_align_tiled", errs);
 }
 
 // The tile job of every unfinished pair, grouped into waves like the planner's (consecutive packed pairs of one width share a wave).
@@ -684,11 +672,8 @@ extern "C" int pa_affine_batch_align_tiled(pa_affine_batch* ab, uint32_t tile_co
     float fwd_total = 0, refill_total = 0, walk_total = 0;
     std::vector<TileJob> jobs;
     std::vector<TileWave> waves;
-    for (size_t c0 = 0; c0 < ab->np;) {
-        size_t c1 = c0, bytes = 0;
-        while (c1 < ab->np && (c1 == c0 || bytes + tiled_bytes_of(ab->n[ab->order[c1]], ab->m[ab->order[c1]], C) <= budget))
-            bytes += tiled_bytes_of(ab->n[ab->order[c1]], ab->m[ab->order[c1]], C), ++c1;
-        const std::vector<uint32_t> ids(ab->order.begin() + c0, ab->order.begin() + c1);
+    for (size_t c0 = 0, bytes; c0 < ab->np;) {
+        const std::vector<uint32_t> ids = next_chunk(*ab, c0, budget, [&](uint32_t p) { return tiled_bytes_of(ab->n[p], ab->m[p], C); }, &bytes);
         ab->tiled.chunks += 1;
         ab->tiled.chunk_bytes_max = std::max(ab->tiled.chunk_bytes_max, (double)bytes);
         TiledChunk ch;
@@ -708,12 +693,9 @@ extern "C" int pa_affine_batch_align_tiled(pa_affine_batch* ab, uint32_t tile_co
                              !hip_ok(hipStreamSynchronize(s), "sync")))
             return PA_E_HIP;
         for (size_t k = 0; k < ch.plan.pairs.size(); ++k) cigars[ch.plan.pairs[k].out] = cigar_of(ops.data() + ch.ops_off[k], ch.st[k].nops);
-        c0 = c1;
+        c0 += ids.size();
     }
-    std::vector<int32_t> c(std::max<size_t>(ab->np, 1));
-    if (ab->np && (!hip_ok(hipMemcpyAsync(c.data(), ab->d_cost.ptr, ab->np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync")))
-        return PA_E_HIP;
-    if (cost_out && ab->np) std::memcpy(cost_out, c.data(), ab->np * 4);
+    if (const int rc = costs_out(*ab, cost_out, s)) return rc;
     if (forward_ms) *forward_ms = fwd_total;
     if (refill_ms) *refill_ms = refill_total;
     if (walk_ms) *walk_ms = walk_total;

@@ -234,3 +234,47 @@ def test_align_affine_convenience():
     pairs = [(b"ACGTTGCA", b"ACGTGCA"), (b"", b"AC"), (b"AC", b"")]
     cm = AffineCost.affine(4, 6, 2)
     check(pairs, cm, pa.align_affine(pairs, cm))
+
+
+ROUTE_MODELS = {
+    "affine": AffineCost.affine(4, 6, 2),
+    "unit": AffineCost.unit(),
+    # deletions go through the delete layer only (no linear deletion edge), insertions have both edges
+    "delete_layer_only": AffineCost(3, 2, None, [("ins", 4, 1), ("del", 5, 2)]),
+}
+# (|a|, |b|): empty b, empty a; segment width 1 and 2; 1024 rows are the widest packed pair, 1025 the first with two strips (and the first
+# that is chained); |a| = 63, 64, 65 around the chained kernel's 64-column chunk and the first column checkpoint of 64-column tiles;
+# |a| = 129 has two column checkpoints (packed, chained, and in a narrow segment)
+ROUTE_SHAPES = [(5, 0), (0, 7), (20, 16), (20, 17), (129, 1024), (129, 1025), (63, 2049), (64, 2049), (65, 2049), (129, 300)]
+
+
+@pytest.fixture(scope="module")
+def route_pairs():
+    rng = np.random.default_rng(14)
+    pairs = []
+    for n, m in ROUTE_SHAPES:
+        y = rand_seq(rng, m)
+        off = int(rng.integers(0, max(m - n, 0) + 1))
+        x = (mutate(rng, y[off:off + n], 0.1) + rand_seq(rng, n))[:n]
+        pairs.append((x, y))
+    assert [(len(x), len(y)) for x, y in pairs] == ROUTE_SHAPES
+    return pairs
+
+
+@pytest.mark.parametrize("name", sorted(ROUTE_MODELS))
+def test_all_four_routes_agree(name, route_pairs):
+    """One batch through run(), align(), align_tiled(64) and align_tiled(64) with chained strips: the costs and CIGARs of the plain DP
+    from each of them."""
+    cm = ROUTE_MODELS[name]
+    want = [ap.affine_nw(x, y, cm) for x, y in route_pairs]
+    b = AffineBatch(route_pairs, cm, trace=True)
+    try:
+        assert b.run().tolist() == [c for c, _ in want]
+        assert b.align() == want
+        assert b.align_tiled(64) == want
+        b.set_chain(True)
+        assert b.align_tiled(64) == want
+        assert b.chain_info()["chain_pairs"] == sum(m > 64 * R for _, m in ROUTE_SHAPES) == 4
+        assert b.run().tolist() == [c for c, _ in want]
+    finally:
+        b.close()
