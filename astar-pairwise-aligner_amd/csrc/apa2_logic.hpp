@@ -27,8 +27,6 @@
 // f <= f_max, and both loops end exactly on the first / last such row of the interval (the emulation backend runs the literal
 // loops, so the CPU tests check this equivalence on every block).
 #pragma once
-#include <math.h>
-
 #include "sweep_logic.hpp"
 
 namespace pa {
@@ -41,8 +39,8 @@ using sweep::NextDecision;
 using sweep::kBlockW;
 using sweep::kNone;
 
-enum : int32_t { kDoublingBand = 1, kDoublingLinear = 2 };             // engine.hpp DoublingKind
-enum : int32_t { kStartZero = 0, kStartGap = 1, kStartH0 = 2 };       // engine.hpp DoublingStart
+enum : int32_t { kDoublingBand = (int32_t)band::DoublingKind::BandDoubling, kDoublingLinear = (int32_t)band::DoublingKind::LinearSearch };
+enum : int32_t { kStartZero = (int32_t)band::DoublingStart::Zero, kStartGap = (int32_t)band::DoublingStart::Gap, kStartH0 = (int32_t)band::DoublingStart::H0 };
 
 // Uniform parameters of a launch (AstarPa2Params as far as this path reads them).
 struct SearchParams {
@@ -52,6 +50,7 @@ struct SearchParams {
     int32_t start;     // kStart*
     float factor;      // BandDoubling
     int32_t delta;     // LinearSearch
+    PA_HD band::Schedule schedule() const { return band::Schedule{(band::DoublingKind)doubling, (band::DoublingStart)start, factor, delta}; }
 };
 
 // Why a pair was handed back to the host engine (the reference would panic there, or the program met a case it leaves alone).
@@ -95,7 +94,7 @@ struct PairProg {
     // Blocks state that survives a pass (blocks.rs:86-108)
     int32_t last_block_idx = 0, blocks_len = 0;
     // statistics (domain.rs:31-43, blocks.rs:76-84)
-    uint32_t f_max_tries = 0, sanity = 0, num_blocks = 0, num_incremental = 0;
+    uint32_t f_max_tries = 0, num_blocks = 0, num_incremental = 0;
     uint64_t computed_lanes = 0, unique_lanes = 0;
     int32_t err = kOk;
 
@@ -233,55 +232,25 @@ struct PairProg {
         return true;
     }
 
-    PA_HD int32_t next_bound(int32_t s, int32_t offset) const {
-        if (sp.doubling == kDoublingLinear) return s + sp.delta;
-        const float x = ceilf(sp.factor * (float)(s - offset));  // band.rs:138, f32 arithmetic
-        const int32_t c = be.uniform((int32_t)x);               // (the float unit is a vector unit: keep the bound scalar)
-        return (c > 1 ? c : 1) + offset;
-    }
-
-    // lib.rs:122-175 + band.rs:100-182 (engine.hpp cost_or_align / band_search).
+    // lib.rs:122-175 + band.rs:100-182: the schedule of band_search.hpp around pass().
     PA_HD void run(PairResult* out) {
         const int32_t h0 = sweep::heur_h(hp, 0, 0);
-        int32_t start_f = 0, start_inc = 1;  // band.rs:13-23
-        if (sp.start == kStartGap) {
-            start_f = start_inc = sweep::iabs32(n - m);
-        } else if (sp.start == kStartH0) {
-            start_f = h0;
-            start_inc = 1;
-        }
-        int32_t s, offset = start_f;
-        if (sp.doubling == kDoublingLinear) {
-            s = start_f;
-        } else {
-            if (start_inc < kBlockW) start_inc = kBlockW;  // lib.rs:142
-            s = offset + start_inc;
-        }
-        int32_t last_s = -1, maxs = INT32_MAX, cost = 0, f_ok = 0;
+        const band::Schedule sc = sp.schedule();
+        band::Search bs;
+        bs.begin(sc, h0, sweep::iabs32(n - m), kBlockW);
+        int32_t cost = 0, f_ok = 0;
         bool done = false;
-        for (int32_t it = 0; it < kMaxPasses && !done && err == kOk; ++it) {
+        for (int32_t it = 0; it < kMaxPasses && err == kOk; ++it) {
             int32_t dist = 0;
-            const bool some = pass(s, &dist);
+            const bool some = pass(bs.s, &dist);
             if (err != kOk) break;
-            if (some) {
-                if (dist > maxs) sanity += 1;  // band.rs:118-121
-                if (dist <= s) {
-                    if (dist <= last_s) sanity += 1;  // band.rs:123-126
-                    cost = dist;
-                    f_ok = s;
-                    done = true;
-                    break;
-                }
-                if (dist < maxs) maxs = dist;
-            } else if (maxs != INT32_MAX) {
-                sanity += 1;  // band.rs:132-135
+            if (bs.record(sc, some, dist, be)) {
+                cost = dist;
+                f_ok = bs.s;
+                done = true;
+                break;
             }
-            const int32_t before = s;
-            last_s = s;
-            const int32_t nx = next_bound(s, offset);
-            s = nx < maxs ? nx : maxs;
-            if (s <= before) s = next_bound(before, offset);  // never stall (engine.hpp band_search)
-            if (bound_runaway(s, n, m)) break;
+            if (bound_runaway(bs.s, n, m)) break;
         }
         if (err == kOk && !done) err = kErrTooManyPasses;
         if (err == kOk && h0 > cost) err = kErrH0;
@@ -289,7 +258,7 @@ struct PairProg {
         out->cost = cost;
         out->f_max = f_ok;
         out->f_max_tries = f_max_tries;
-        out->sanity_violations = sanity;
+        out->sanity_violations = bs.sanity;
         out->num_blocks = num_blocks;
         out->num_incremental_blocks = num_incremental;
         out->pad0 = 0;

@@ -31,6 +31,8 @@
 #include <utility>
 #include <vector>
 
+#include "band_search.hpp"
+
 namespace pa {
 namespace engine {
 
@@ -138,8 +140,8 @@ struct Cigar {
 // ---- parameters (params.rs:8-42, blocks.rs:31-74, band.rs:5-63) -----------------------------------
 enum class DomainKind : int32_t { Full = 0, GapStart = 1, GapGap = 2, Astar = 3 };
 enum class HeuristicKind : int32_t { None = 0, Gap = 1, SH = 2, GCSH = 3 };  // NoCost (Dijkstra) / GapCost / SH / GCSH (exact matches)
-enum class DoublingKind : int32_t { None = 0, BandDoubling = 1, LinearSearch = 2 };
-enum class DoublingStart : int32_t { Zero = 0, Gap = 1, H0 = 2 };
+using band::DoublingKind;   // None / BandDoubling / LinearSearch
+using band::DoublingStart;  // Zero / Gap / H0
 
 struct BlockParams {
     bool sparse = true;
@@ -206,6 +208,8 @@ struct AstarPa2Params {
     }
 };
 
+inline band::Schedule schedule_of(const AstarPa2Params& p) { return band::Schedule{p.doubling, p.start, p.factor, (int32_t)p.delta}; }
+
 struct BlockStats {  // blocks.rs:76-84
     size_t num_blocks = 0, num_incremental_blocks = 0, computed_lanes = 0, unique_lanes = 0;
     double t_compute = 0;
@@ -219,7 +223,7 @@ struct AstarPa2Stats {  // domain.rs:31-43
     BlockStats block_stats;
     TraceStats trace_stats;
     size_t f_max_tries = 0;
-    size_t sanity_violations = 0;  // see band_search
+    size_t sanity_violations = 0;  // see band_search.hpp
     double t_precomp = 0, t_j_range = 0, t_fixed_j_range = 0, t_pruning = 0, t_contours_update = 0;
 };
 
@@ -1185,38 +1189,14 @@ class AstarPa2Instance {
     }
 };
 
-// band.rs:100-141 / 143-182 : shared search skeleton.
-//
-// Deviation (documented in DESIGN.md): the reference guards this loop with three sanity `assert!`s
-// (band.rs:117-135).  They can fire on legal inputs -- a block reused across iterations keeps its old
-// `original_j_range` (blocks.rs:190-197) which clips `fixed_j_range` (domain.rs:298), so with small block
-// widths the band for f_max == d may miss the optimal path and a later, larger f_max finds
-// cost <= last_s.  The reference aborts there; we keep every band decision identical, count the event in
-// `sanity_violations`, and return the (exact, since cost <= s) answer instead of aborting.
+// band.rs:100-141 / 143-182 over the schedule of band_search.hpp (the deviations from the reference are described there): f(s) is
+// one align_for_bounded_dist pass.
 template <class F>
-std::pair<Cost, std::optional<Cigar>> band_search(Cost first_s, std::function<Cost(Cost)> next_s, F&& f,
-                                                  size_t* sanity_violations) {
-    Cost last_s = -1;
-    Cost s = first_s;
-    Cost maxs = COST_MAX;
+std::pair<Cost, std::optional<Cigar>> band_search(const band::Schedule& sc, band::Search& bs, F&& f) {
     for (;;) {
-        auto r = f(s);
-        if (std::getenv("PA_ENGINE_DEBUG")) std::fprintf(stderr, "band_search s=%d -> %s %d\n", s, r ? "some" : "none", r ? r->first : -1);
-        if (r) {
-            const Cost cost = r->first;
-            if (cost > maxs) *sanity_violations += 1;  // band.rs:118-121
-            if (cost <= s) {
-                if (cost <= last_s) *sanity_violations += 1;  // band.rs:123-126
-                return *r;
-            }
-            maxs = std::min(maxs, cost);
-        } else if (maxs != COST_MAX) {
-            *sanity_violations += 1;  // band.rs:132-135
-        }
-        const Cost prev = s;
-        last_s = s;
-        s = std::min(next_s(s), maxs);
-        if (s <= prev) s = next_s(prev);  // never stall (the reference's "potential infinite loop" TODO, band.rs:110)
+        auto r = f(bs.s);
+        if (std::getenv("PA_ENGINE_DEBUG")) std::fprintf(stderr, "band_search s=%d -> %s %d\n", bs.s, r ? "some" : "none", r ? r->first : -1);
+        if (bs.record(sc, r.has_value(), r ? r->first : 0, band::HostUniform{})) return *r;
     }
 }
 
@@ -1240,29 +1220,13 @@ AlignResult cost_or_align(const AstarPa2Params& params, Backend& be, bool trace,
         }
         case DoublingKind::LinearSearch:
         case DoublingKind::BandDoubling: {
-            Cost start_f = 0, start_inc = 1;  // band.rs:13-23
-            if (params.start == DoublingStart::Gap) {
-                start_f = start_inc = unit_gap_cost(0, 0, be.n(), be.m());
-            } else if (params.start == DoublingStart::H0) {
-                start_f = h0;
-                start_inc = 1;
-            }
             Blocks<Backend> blocks(params.front, trace, be);
             blocks.self_check = self_check;
-            auto f = [&](Cost s) { return nw.align_for_bounded_dist(s, trace, &blocks); };
-            if (params.doubling == DoublingKind::LinearSearch) {
-                const Cost delta = (Cost)params.delta;
-                r = band_search(start_f, [delta](Cost s) { return s + delta; }, f, &nw.stats.sanity_violations);
-            } else {
-                start_inc = std::max(start_inc, params.block_width);  // lib.rs:142
-                const float factor = params.factor;
-                const Cost offset = start_f;
-                r = band_search(offset + start_inc,
-                                [factor, offset](Cost s) {  // band.rs:138
-                                    return std::max((Cost)std::ceil(factor * (float)(s - offset)), 1) + offset;
-                                },
-                                f, &nw.stats.sanity_violations);
-            }
+            const band::Schedule sc = schedule_of(params);
+            band::Search bs;
+            bs.begin(sc, h0, unit_gap_cost(0, 0, be.n(), be.m()), params.block_width);
+            r = band_search(sc, bs, [&](Cost s) { return nw.align_for_bounded_dist(s, trace, &blocks); });
+            nw.stats.sanity_violations += bs.sanity;
             // Only the BandDoubling arm hands the Blocks' own counters to the caller (lib.rs:158); after a LinearSearch the
             // reference's block statistics stay at their defaults (lib.rs:132-140).  Found by oracle/astarpa2_restated.py.
             if (params.doubling == DoublingKind::BandDoubling) nw.stats.block_stats = blocks.stats;

@@ -254,7 +254,7 @@ class SweepAligner {
         return cg;
     }
 
-    // The band search (band.rs:100-182, engine.hpp band_search) with the passes PIPELINED: while the pass for bound s runs, the
+    // The band search (band.rs:100-182, the schedule of band_search.hpp) with the passes PIPELINED: while the pass for bound s runs, the
     // passes for next_s(s), next_s(next_s(s)), ... are prepared and launched under the assumptions that (a) the pass before
     // them finds no path or a cost above its bound that does not cap the next bound, and (b) it gets at least as far as every
     // pass before it, so that no stale block record reaches the first column (the quirk of domain.rs:395-404).  Both hold for
@@ -264,13 +264,12 @@ class SweepAligner {
         Prepared p;
         int waves;
     };
-    std::pair<Cost, std::optional<engine::Cigar>> search(Cost first_s, const std::function<Cost(Cost)>& next_s) {
+    std::pair<Cost, std::optional<engine::Cigar>> search(const band::Schedule& sc, band::Search& bs) {
         static const bool no_pipe = std::getenv("PA_SWEEP_NO_PIPELINE") != nullptr;
         std::vector<InFlight> fl;  // launched, oldest first
         size_t head = 0;
         int waves_in_flight = 0;
         Carry spec;                // the carry after the newest launched pass, as assumed
-        Cost last_s = -1, s = first_s, maxs = engine::COST_MAX;
         auto give_up = [&]() {  // every launched pass behind the head's predecessor
             if (head < fl.size()) dev.cancel_after(fl[head].p.seq - 1);
             fl.resize(head);
@@ -280,11 +279,11 @@ class SweepAligner {
             std::optional<std::pair<Cost, std::optional<engine::Cigar>>> r;
             stats.f_max_tries += 1;
             if (head == fl.size()) {  // nothing launched for this bound: prepare it from the real state
-                Prepared p = prepare(s, carry, stale_of(carry));
+                Prepared p = prepare(bs.s, carry, stale_of(carry));
                 apply_prepared(carry, p);
                 if (!p.early_none) {
                     launch(p, carry.seq);
-                    fl.push_back(InFlight{p, dev.pass_waves(s)});
+                    fl.push_back(InFlight{p, dev.pass_waves(bs.s)});
                     waves_in_flight = fl.back().waves;
                     spec = carry;
                     spec.blocks_len = spec.blocks_len < 2 ? 2 : spec.blocks_len;  // the pass reaches block 1 at least
@@ -300,7 +299,7 @@ class SweepAligner {
                 if (!no_pipe) {
                     Cost sa = fl.back().p.f_max;
                     while ((int)(fl.size() - head) < dev.max_in_flight()) {
-                        const Cost sn = next_s(sa);
+                        const Cost sn = bs.next(sc, sa, band::HostUniform{});
                         if (sn <= sa) break;
                         const int w = dev.pass_waves(sn);
                         if (waves_in_flight + w > dev.wave_budget()) break;
@@ -352,23 +351,11 @@ class SweepAligner {
                 }
             }
             // ---- band.rs:100-182 ----
-            if (r) {
-                const Cost cost = r->first;
-                if (cost > maxs) stats.sanity_violations += 1;  // band.rs:118-121
-                if (cost <= s) {
-                    if (cost <= last_s) stats.sanity_violations += 1;  // band.rs:123-126
-                    give_up();
-                    return *r;
-                }
-                maxs = std::min(maxs, cost);
-            } else if (maxs != engine::COST_MAX) {
-                stats.sanity_violations += 1;  // band.rs:132-135
+            if (bs.record(sc, r.has_value(), r ? r->first : 0, band::HostUniform{})) {
+                give_up();
+                return *r;
             }
-            const Cost prev = s;
-            last_s = s;
-            s = std::min(next_s(s), maxs);
-            if (s <= prev) s = next_s(prev);  // never stall (the reference's "potential infinite loop" TODO, band.rs:110)
-            if (head < fl.size() && fl[head].p.f_max != s) give_up();  // assumption (a)
+            if (head < fl.size() && fl[head].p.f_max != bs.s) give_up();  // assumption (a)
         }
     }
 
@@ -377,23 +364,11 @@ class SweepAligner {
         using namespace engine;
         AlignResult out;
         const Cost h_0 = h0();
-        Cost start_f = 0, start_inc = 1;  // band.rs:13-23
-        if (params.start == DoublingStart::Gap) {
-            start_f = start_inc = unit_gap_cost(0, 0, n, m);
-        } else if (params.start == DoublingStart::H0) {
-            start_f = h_0;
-            start_inc = 1;
-        }
-        std::pair<Cost, std::optional<Cigar>> r;
-        if (params.doubling == DoublingKind::LinearSearch) {
-            const Cost delta = (Cost)params.delta;
-            r = search(start_f, [delta](Cost s) { return s + delta; });
-        } else {
-            start_inc = std::max(start_inc, params.block_width);  // lib.rs:142
-            const float factor = params.factor;
-            const Cost offset = start_f;
-            r = search(offset + start_inc, [factor, offset](Cost s) { return std::max((Cost)std::ceil(factor * (float)(s - offset)), 1) + offset; });
-        }
+        const band::Schedule sc = schedule_of(params);
+        band::Search bs;
+        bs.begin(sc, h_0, unit_gap_cost(0, 0, n, m), params.block_width);
+        std::pair<Cost, std::optional<Cigar>> r = search(sc, bs);
+        stats.sanity_violations += bs.sanity;
         PA_ASSERT(h_0 <= r.first, "Heuristic at start > final cost");
         out.cost = r.first;
         out.has_cigar = r.second.has_value();

@@ -9,11 +9,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define PA_HD __host__ __device__ __forceinline__
-#else
-#define PA_HD inline
-#endif
+#include "band_search.hpp"  // PA_HD
 
 namespace pa {
 namespace sweep {

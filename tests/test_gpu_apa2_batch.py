@@ -333,3 +333,38 @@ def test_sh_with_local_pruning_batch_and_single(pa, oracle):
             want = oracle.cpu_align(a, b, oc)
             got = al.align_with_stats(a, b)
             assert (got[0], got[1]) == want[:2] and {k_: got[2][k_] for k_ in KEYS} == {k_: want[2][k_] for k_ in KEYS}
+
+
+SEARCH_SCHEDULES = {
+    "band_h0_f2": dict(doubling="band", start="h0", factor=2.0),
+    "band_gap_f2": dict(doubling="band", start="gap", factor=2.0),
+    "band_zero_f15": dict(doubling="band", start="zero", factor=1.5),
+    "linear_h0_d3": dict(doubling="linear", start="h0", delta=3.0),  # (dozens of passes on the 700 bp pairs)
+    "linear_gap_d300": dict(doubling="linear", start="gap", delta=300.0),
+}
+SEARCH_ROUTES = {
+    "simple": dict(heuristic="gap", incremental_doubling=False, prune=False),
+    "full": dict(heuristic="gcsh", k=10, p=20, incremental_doubling=True, prune=True),
+}
+
+
+def search_schedule_pairs():
+    """One, two and three 256-column blocks and their edges, identical to unrelated; two pairs whose lengths differ by about 300, so
+    that a search started at the gap cost differs from one started at h(0, 0)."""
+    pairs = [gen_pair(n, e, seed=1000 + 10 * n + int(10 * e)) for n in (1, 2, 255, 256, 257, 513, 700) for e in (0.0, 0.2, 1.0)]
+    return pairs + [(rand_seq(700, seed=41), rand_seq(400, seed=42)), (rand_seq(215, seed=43), rand_seq(513, seed=44))]
+
+
+@pytest.mark.parametrize("route", list(SEARCH_ROUTES))
+@pytest.mark.parametrize("schedule", list(SEARCH_SCHEDULES))
+def test_search_schedules_on_both_routes(pa, oracle, schedule, route):
+    """The band search as the two batch kernels run it (csrc/band_search.hpp in apa2_kernel, apa2_full_logic.hpp's own loop in
+    apa2_full_kernel), at the smallest shapes where the loop can go wrong: every start kind, band doubling and linear search.  Cost, CIGAR string and all twelve
+    statistics against the engine over the CPU kernels; no pair goes to the host engine unless the CPU emulation of the same
+    program hands it back too."""
+    oc = oracle.make_params(**{**dict(domain="astar", block_width=256, sparse=True, dt_trace=True, max_g=40, fr_drop=10, sparse_h=True),
+                               **SEARCH_ROUTES[route], **SEARCH_SCHEDULES[schedule]})
+    pairs = search_schedule_pairs()
+    emu = oracle.apa2_emu_align if route == "simple" else oracle.apa2_full_emu_align
+    handed_back = sum(1 for a, b in pairs if emu(a, b, oc)[0] != 0)
+    check(pa, oracle, pairs, oc, fallbacks=handed_back)
