@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "pa_search_batch_destroy",
     "pa_affine_batch_create", "pa_affine_batch_run", "pa_affine_batch_align", "pa_affine_batch_info", "pa_affine_batch_destroy",
     "pa_affine_batch_align_tiled", "pa_affine_batch_tiled_info", "pa_affine_batch_set_chain", "pa_affine_batch_chain_info",
+    "pa_affine_batch_set_free_ends", "pa_affine_batch_ends", "pa_affine_batch_last_row",
 ]
 
 _lib = None
@@ -107,6 +108,10 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine_batch_set_chain.argtypes = [vp, C.c_int]
         L.pa_affine_batch_chain_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
         L.pa_affine_batch_chain_info.restype = None
+    if hasattr(L, "pa_affine_batch_set_free_ends"):
+        L.pa_affine_batch_set_free_ends.argtypes = [vp, C.c_int, C.c_int]
+        L.pa_affine_batch_ends.argtypes = [vp, vp, vp]
+        L.pa_affine_batch_last_row.argtypes = [vp, vp, vp]
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -535,12 +540,21 @@ class AffineCost:
         return f"AffineCost(sub={self.sub}, ins={self.ins}, del_={self.del_}, layers={self.layers})"
 
 
+def _switch(v, name: str) -> int:
+    """A free_start / free_end value: a bool, or the integer 0 or 1."""
+    if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
+        return int(v)
+    raise ValueError(f"{name} must be a bool (or 0 / 1), got {v!r}")
+
+
 class AffineBatch:
     """Gap-affine global alignment of many pairs on the GPU (pa_affine_batch_*): NW::new(cm, false, false).align(a, b) of pa-base-algos
     for every pair, a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align().  chain=True runs every
-    pair with |b| > 1024 on a wavefront per strip of 1024 rows in run() and align_tiled() (set_chain); the results are the same."""
+    pair with |b| > 1024 on a wavefront per strip of 1024 rows in run() and align_tiled() (set_chain); the results are the same.
+    free_start / free_end (set_free_ends) make the ends of a, the text, free: the pattern b is placed in a[start:end]."""
 
-    def __init__(self, pairs, cm: AffineCost, trace: bool = False, chain: bool = False):
+    def __init__(self, pairs, cm: AffineCost, trace: bool = False, chain: bool = False, free_start: bool = False, free_end: bool = False):
+        free_start, free_end = _switch(free_start, "free_start"), _switch(free_end, "free_end")
         pairs = list(pairs)
         if any(not isinstance(x, bytes) or not isinstance(y, bytes) for x, y in pairs):
             raise ValueError("pairs must be (bytes, bytes)")
@@ -573,6 +587,39 @@ class AffineBatch:
         self.last_trace_ms = 0.0
         if chain:
             self.set_chain(True)
+        if free_start or free_end:
+            self.set_free_ends(free_start, free_end)
+
+    def set_free_ends(self, free_start: bool, free_end: bool) -> None:
+        """Ends-free (semi-global) mode for every later run(), align() and align_tiled(): with free_start a prefix of a costs nothing
+        (row 0 is zero), with free_end the cost is the lowest value of the last row and `end` the lowest column that holds it.  The
+        CIGARs then describe a[start:end] against b (ends()).  Both off (the default): global alignment."""
+        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+        self._check(load().pa_affine_batch_set_free_ends(self._h, fs, fe), "pa_affine_batch_set_free_ends")
+
+    def ends(self) -> np.ndarray:
+        """int64[npairs, 2]: (start, end) of every pair in the last run(), align() or align_tiled() under the current setting; after a
+        cost-only run() start is -1 under free_start and 0 otherwise.  ValueError before any such call or after set_free_ends."""
+        n = max(self.npairs, 1)
+        st, en = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self._check(load().pa_affine_batch_ends(self._h, _p(st), _p(en)), "pa_affine_batch_ends")
+        return np.stack([st, en], axis=1)[: self.npairs]
+
+    def last_row(self, pairs=None) -> list:
+        """M(i, |b|) for i = 0 .. |a| of every pair in `pairs` (indices; None: all), a list of int32 arrays, under the current setting: in
+        global mode the cost of b against every prefix of a.  Runs a cost-only pass of its own, in chunks within
+        PA_AFFINE_TRACE_BUDGET_MB; ValueError for a pair whose row alone exceeds it."""
+        ids = list(range(self.npairs)) if pairs is None else [int(p) for p in pairs]
+        if any(not 0 <= p < self.npairs for p in ids) or len(set(ids)) != len(ids):
+            raise ValueError("pairs must be distinct indices of the batch")
+        offs = np.full(max(self.npairs, 1), np.iinfo(np.uint64).max, np.uint64)
+        total = 0
+        for p in ids:
+            offs[p] = total
+            total += len(self._keep[p][0]) + 1
+        out = np.zeros(max(total, 1), np.int32)
+        self._check(load().pa_affine_batch_last_row(self._h, _p(out), _p(offs)), "pa_affine_batch_last_row")
+        return [out[int(offs[p]): int(offs[p]) + len(self._keep[p][0]) + 1].copy() for p in ids]
 
     def set_chain(self, on: bool) -> None:
         """Chained strips for pairs with |b| > 1024 in run() and align_tiled() (align() ignores it).  Off by default."""
@@ -669,6 +716,21 @@ def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False
     b = AffineBatch(pairs, cm, trace=True, chain=chain)
     try:
         return b.align_tiled() if tiled else b.align()
+    finally:
+        b.close()
+
+
+def map_affine(pairs, cm: AffineCost, free_start: bool = True, free_end: bool = True, tiled: bool = False, chain: bool = False) -> list[tuple[int, str, int, int]]:
+    """[(cost, CIGAR, start, end)] of every pair (a the text, b the pattern) under the gap-affine cost model `cm` with the text's ends
+    free (AffineBatch.set_free_ends): b is placed in a[start:end], which the CIGAR describes.  tiled and chain as in align_affine."""
+    free_start, free_end = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+    if chain and not tiled:
+        raise ValueError("chain=True needs tiled=True: the untiled traced route has no chained form")
+    b = AffineBatch(pairs, cm, trace=True, chain=chain, free_start=free_start, free_end=free_end)
+    try:
+        res = b.align_tiled() if tiled else b.align()
+        se = b.ends()
+        return [(c, g, int(se[p, 0]), int(se[p, 1])) for p, (c, g) in enumerate(res)]
     finally:
         b.close()
 

@@ -33,6 +33,11 @@
 //   bit  4    delete layer: 0 open (from M(i-1,j)), 1 extend
 // Codes of rows 1 .. H of column i at codes[i H + j - 1], row 0 at codes[(n + 1) H + i].  affine_walk_kernel walks them backwards from
 // (n, m, main) to (0, 0, main) (AffineNwFronts::trace / parent, nw/affine.rs:164-188, 283-305).
+//
+// Ends-free mode (no counterpart in the reference; include/pa_affine_hip.h has the definition): the same recurrence with another row 0
+// (zero in every column under kFreeStart), another answer (the lowest value of row |b| and its lowest column under kFreeEnd) and other
+// endpoints of the walk.  Every fill kernel has a second set of instantiations for it (ENDS, FS), which read the switches from
+// Costs::ends; the global-mode ones compile to the instructions they had before the mode existed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,8 +55,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // Edge costs, kInf where the model has no such edge.
 struct Costs {
     uint32_t sub, ins, del, io, ie, dopen, de;
-    uint32_t pad_;
+    uint32_t ends;  // kFreeStart | kFreeEnd: read by the ENDS instantiations only
 };
+constexpr uint32_t kFreeStart = 1, kFreeEnd = 2;
 
 // One pair.  Device pointers.
 struct Pair {
@@ -73,6 +79,40 @@ struct Wave {
     uint64_t* bnd;       // strips > 1: nmax + 1 boundary values (M | I << 32) of the strip above; CKPT: of every strip but the last
 };
 static_assert(sizeof(Wave) == 32, "Wave layout");
+
+// Ends-free mode (the ENDS instantiations; the others never look at it).  With kFreeStart row 0 is zero in every column; with kFreeEnd a
+// pair's cost is the lowest value of row |b|, and its end the lowest column that holds it.  The lane that owns row |b| keeps both while
+// its columns go by and stores them at column n.
+struct Ends {
+    int32_t* end_out;         // by Pair::out, next to cost_out
+    int32_t* rows;            // last_row(): M(i, |b|) of column i at rows[row_off[Pair::out] + i]; nullptr: not asked for
+    const uint64_t* row_off;  // ~0 skips the pair
+};
+struct LastRow {
+    uint32_t best = 0xFFFFFFFFu;
+    int32_t end = 0;
+    PA_GLOBAL int32_t* row = nullptr;
+};
+__device__ __forceinline__ LastRow last_row_init(const Ends& E, uint32_t out, bool present) {
+    LastRow L;
+    if (E.rows && present) {
+        const uint64_t off = ((gcu64)E.row_off)[out];
+        if (off != ~uint64_t(0)) L.row = (gi32)E.rows + off;
+    }
+    return L;
+}
+// Column i (0 .. n, in order) of row |b| holds v.
+__device__ __forceinline__ void last_row_step(LastRow& L, const Costs& C, const Ends& E, uint32_t out, uint32_t v, int i, int n, gi32 cost_out) {
+    if (L.row) L.row[i] = (int32_t)v;
+    if ((C.ends & kFreeEnd) ? v < L.best : i == n) {  // strict: the lowest column wins
+        L.best = v;
+        L.end = i;
+    }
+    if (i == n) {
+        cost_out[out] = (int32_t)L.best;
+        ((gi32)E.end_out)[out] = L.end;
+    }
+}
 
 __device__ __forceinline__ uint32_t umin(uint32_t x, uint32_t y) { return x < y ? x : y; }
 __device__ __forceinline__ uint32_t umin3(uint32_t x, uint32_t y, uint32_t z) { return umin(umin(x, y), z); }
@@ -144,9 +184,9 @@ __device__ __forceinline__ void store_col_ckpt(gu64 col, gu64 row0, const uint32
 //   * the row checkpoints: the boundary row of every strip but the last, strip s at bnd + s (nmax + 1);
 //   * the column checkpoints, in Pair::codes as 8-byte values: (M | D << 32) of rows 1 .. H after columns C, 2C, .. < n (C = tile_cols),
 //     checkpoint k = 0 .. K - 1 (column (k + 1) C, K = (n - 1) / C) at [k H + j - 1], then (M | D << 32) of row 0 at [K H + k].
-template <bool FILL, bool CKPT = false>
+template <bool FILL, bool CKPT = false, bool ENDS = false>
 __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __restrict__ waves, int nwaves, const Pair* __restrict__ pairs,
-                                                                  Costs C, int32_t* __restrict__ cost_out) {
+                                                                  Costs C, int32_t* __restrict__ cost_out, Ends E) {
     const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
     if (wave >= nwaves) return;
     const int lane = (int)(threadIdx.x & 63);
@@ -174,6 +214,9 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
     const gu8 codes = (gu8)P.codes;
     const gi32 out = (gi32)cost_out;
     const int T = (int)W.nmax + g;  // steps per strip: the last lane reaches column nmax at step nmax + g - 1
+    LastRow LR;
+    if constexpr (ENDS) LR = last_row_init(E, P.out, present);
+    const bool fs = ENDS && (C.ends & kFreeStart);
     for (int s = 0; s < (int)W.strips; ++s) {
         const uint32_t j0 = (uint32_t)(64 * s + r) * kRows;
         uint32_t bk[kRows], Mp[kRows], Dp[kRows];
@@ -206,13 +249,13 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
                     Row0 R;
                     if (FILL) {  // row0_step, written out: see the note above rows_step
                         R.D = umin3(r0M + C.dopen, r0D + C.de, kInf);
-                        R.M = t == 0 ? 0u : umin3(r0M + C.del, R.D + C.de, kInf);
+                        R.M = t == 0 || fs ? 0u : umin3(r0M + C.del, R.D + C.de, kInf);
                         if (active) {
                             const uint32_t code = (R.M == r0M + C.del ? 2u : 4u) | (R.D == r0M + C.dopen ? 0u : 16u);
                             codes[(size_t)(n + 1) * P.H + (size_t)i] = (uint8_t)code;
                         }
                     } else {
-                        R = row0_step(C, r0M, r0D, t == 0);
+                        R = row0_step(C, r0M, r0D, t == 0 || fs);
                     }
                     r0M = R.M;
                     r0D = R.D;
@@ -225,7 +268,11 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
                 // prefetch the next column's byte and boundary value
                 nextC = present && t + 1 <= n ? (uint32_t)ga[t] : 0x100u;
                 if (from_bnd && present && t + 1 <= n) nextB = bnd[t + 1];
-                if (top && active && i == n && m == 0) out[P.out] = (int32_t)inM;
+                if constexpr (ENDS) {
+                    if (top && active && m == 0) last_row_step(LR, C, E, P.out, inM, i, n, out);  // row |b| is row 0
+                } else {
+                    if (top && active && i == n && m == 0) out[P.out] = (int32_t)inM;
+                }
             }
             uint32_t Mdiag = topPrev;
             topPrev = inM;
@@ -268,7 +315,14 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
                     next_ck += (int)W.tile_cols;
                     ++kck;
                 }
-                if (i == n && m > j0 && m <= j0 + kRows) {
+                if constexpr (ENDS) {
+                    if (m > j0 && m <= j0 + kRows) {  // every column of the lane that owns row |b|
+                        uint32_t v = 0;
+#pragma unroll
+                        for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
+                        last_row_step(LR, C, E, P.out, v, i, n, out);
+                    }
+                } else if (i == n && m > j0 && m <= j0 + kRows) {
                     uint32_t v = 0;
 #pragma unroll
                     for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
@@ -284,19 +338,25 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_kernel(const Wave* __
 }
 
 // One traceback (AffineNwFronts::trace): from (n, m, main) back to (0, 0, main), the first matching parent of every state as the FILL
-// codes recorded it.  ops[] receives the steps from the end backwards: '=', 'X', 'I', 'D'.
+// codes recorded it.  ops[] receives the steps from the end backwards: '=', 'X', 'I', 'D'.  Ends-free: from (end, m, main), the end the
+// forward pass left at ends[out], and with free_start only to the first state (i, 0, main), whose i is the start.
 struct Walk {
     const uint8_t* a;
     const uint8_t* b;
     const uint8_t* codes;
     uint8_t* ops;
     uint32_t n, m, H, cap;
+    uint32_t out, free_start;
 };
-static_assert(sizeof(Walk) == 48, "Walk layout");
+static_assert(sizeof(Walk) == 56, "Walk layout");
 struct WalkOut {
     int32_t status;  // 0 ok, 1 bad code, 2 ops over capacity
     int32_t nops;
+    int32_t start;  // the column the walk stopped in
 };
+
+// The walk is over: (0, 0, main), or with a free start any (i, 0, main).
+__device__ __forceinline__ bool walk_done(int64_t i, int64_t j, int layer, bool free_start) { return j == 0 && layer == 0 && (free_start || i == 0); }
 
 // One step of the walk from (i, j, layer) (0 main, 1 insert, 2 delete) over that state's code c; o.status = 1 on a code that cannot be.
 __device__ __forceinline__ void walk_step(uint32_t c, const uint8_t* a, const uint8_t* b, uint8_t* ops, uint32_t cap, int64_t& i, int64_t& j,
@@ -353,21 +413,24 @@ __device__ __forceinline__ void walk_step(uint32_t c, const uint8_t* a, const ui
     }
 }
 
-__global__ __launch_bounds__(64) void affine_walk_kernel(const Walk* __restrict__ walks, int nw, WalkOut* __restrict__ outs) {
+__global__ __launch_bounds__(64) void affine_walk_kernel(const Walk* __restrict__ walks, int nw, WalkOut* __restrict__ outs,
+                                                         const int32_t* __restrict__ ends) {
     const int t = (int)(blockIdx.x * 64 + threadIdx.x);
     if (t >= nw) return;
     const Walk Q = walks[t];
-    int64_t i = Q.n, j = Q.m;
+    int64_t i = ends ? ends[Q.out] : Q.n, j = Q.m;
+    if (i < 0 || i > (int64_t)Q.n) i = Q.n;  // (never: the forward pass stores a column of the pair)
     int layer = 0;  // 0 main, 1 insert, 2 delete
     const size_t row0 = (size_t)(Q.n + 1) * Q.H;
     WalkOut o;
     o.status = 0;
     o.nops = 0;
-    while (o.status == 0 && (i > 0 || j > 0 || layer != 0)) {
+    while (o.status == 0 && !walk_done(i, j, layer, Q.free_start != 0)) {
         const uint32_t c = j > 0 ? Q.codes[(size_t)i * Q.H + (size_t)(j - 1)] : Q.codes[row0 + (size_t)i];
         walk_step(c, Q.a, Q.b, Q.ops, Q.cap, i, j, layer, o);
     }
     if (o.status == 0 && (uint32_t)o.nops > Q.cap) o.status = 2;
+    o.start = (int32_t)i;
     outs[t] = o;
 }
 
@@ -407,6 +470,8 @@ struct TileWave {
     uint32_t first, np, lg, steps;
 };
 
+// FS: row 0 is zero in every column (kFreeStart), as the checkpoint pass had it.
+template <bool FS>
 __global__ __launch_bounds__(64 * kBlockWaves) void affine_tile_kernel(const TileWave* __restrict__ waves, int nwaves, const TileJob* __restrict__ jobs,
                                                                        Costs C) {
     const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
@@ -465,7 +530,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_tile_kernel(const Til
         if (first) {
             inC = nextC;
             if (top) {
-                const Row0 R = row0_step(C, r0M, r0D, i == 0);
+                const Row0 R = row0_step(C, r0M, r0D, i == 0 || FS);
                 if (active) codes[(size_t)J.row0 + (size_t)(i - cs)] = (uint8_t)R.code;
                 r0M = R.M;
                 r0D = R.D;
@@ -494,8 +559,8 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_tile_kernel(const Til
 }
 
 // The walk inside a tile: affine_walk_kernel's loop from the pair's stored state, until the state leaves the tile (upwards, leftwards or
-// diagonally) or reaches (0, 0, main).  The layer travels with the state, so a gap that is open at a tile edge goes on in its layer.
-__global__ __launch_bounds__(64) void affine_tile_walk_kernel(const TileJob* __restrict__ jobs, int nj) {
+// diagonally) or reaches (0, 0, main) -- with a free start, row 0 in the main layer.  The layer travels with the state, so a gap that is open at a tile edge goes on in its layer.
+__global__ __launch_bounds__(64) void affine_tile_walk_kernel(const TileJob* __restrict__ jobs, int nj, int free_start) {
     const int t = (int)(blockIdx.x * 64 + threadIdx.x);
     if (t >= nj) return;
     const TileJob J = jobs[t];
@@ -507,11 +572,11 @@ __global__ __launch_bounds__(64) void affine_tile_walk_kernel(const TileJob* __r
     o.nops = S.nops;
     const int64_t cs = J.c0 ? (int64_t)J.c0 + 1 : 0;
     const int64_t jt = (int64_t)J.rt * (64 * kRows), jmin = J.rt ? jt + 1 : 0;  // rows jmin .. of the pair are the tile's
-    while (o.status == 0 && (i > 0 || j > 0 || layer != 0) && i >= cs && j >= jmin) {
+    while (o.status == 0 && !walk_done(i, j, layer, free_start != 0) && i >= cs && j >= jmin) {
         const uint32_t c = j > 0 ? J.codes[(size_t)(i - cs) * J.Ht + (size_t)(j - 1 - jt)] : J.codes[(size_t)J.row0 + (size_t)(i - cs)];
         walk_step(c, J.a, J.b, J.ops, J.cap, i, j, layer, o);
     }
-    if (o.status == 0 && i == 0 && j == 0 && layer == 0 && (uint32_t)o.nops > J.cap) o.status = 2;
+    if (o.status == 0 && walk_done(i, j, layer, free_start != 0) && (uint32_t)o.nops > J.cap) o.status = 2;
     WalkState R;
     R.i = (int32_t)i;
     R.j = (int32_t)j;
@@ -579,10 +644,10 @@ __device__ __attribute__((noinline)) uint64_t chain_wait(const uint64_t* row, ui
 }
 
 // ticket_err[0]: the job ticket, ticket_err[1]: the error word; both zero at launch.
-template <bool CKPT>
+template <bool CKPT, bool ENDS = false>
 __global__ __launch_bounds__(64 * kBlockWaves) void affine_chain_kernel(const ChainJob* __restrict__ jobs, int njobs, const Pair* __restrict__ pairs,
                                                                         Costs C, uint32_t tile_cols, uint32_t* ticket_err,
-                                                                        int32_t* __restrict__ cost_out) {
+                                                                        int32_t* __restrict__ cost_out, Ends E) {
     const int lane = (int)(threadIdx.x & 63);
     uint32_t tk = 0;
     if (lane == 0) tk = __hip_atomic_fetch_add(ticket_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -612,6 +677,9 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_chain_kernel(const Ch
         Dp[k] = kInf;
     }
     const int T = n + 64;  // the last lane reaches column n at step n + 63
+    LastRow LR;
+    if constexpr (ENDS) LR = last_row_init(E, P.out, true);
+    const bool fs = ENDS && (C.ends & kFreeStart);
     int next_ck = (int)tile_cols;
     uint32_t kck = 0;
     uint32_t r0M = kInf, r0D = kInf;
@@ -649,7 +717,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_chain_kernel(const Ch
                 fM = (uint32_t)__builtin_amdgcn_readlane((int)curM, u);
                 fI = (uint32_t)__builtin_amdgcn_readlane((int)curI, u);
             } else {  // row 0 of column t, the same in every lane
-                const Row0 R = row0_step(C, r0M, r0D, t == 0);
+                const Row0 R = row0_step(C, r0M, r0D, t == 0 || fs);
                 r0M = R.M;
                 r0D = R.D;
                 fM = R.M;
@@ -670,7 +738,14 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine_chain_kernel(const Ch
                     next_ck += (int)tile_cols;
                     ++kck;
                 }
-                if (i == n && m > j0 && m <= j0 + kRows) {
+                if constexpr (ENDS) {
+                    if (m > j0 && m <= j0 + kRows) {
+                        uint32_t v = 0;
+#pragma unroll
+                        for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
+                        last_row_step(LR, C, E, P.out, v, i, n, out);
+                    }
+                } else if (i == n && m > j0 && m <= j0 + kRows) {
                     uint32_t v = 0;
 #pragma unroll
                     for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;

@@ -8,7 +8,9 @@
 // CIGARs in bounded memory: a cost-only pass that keeps checkpoints (affine_ckpt_kernel), then rounds that re-fill the one tile of codes
 // each unfinished pair's walk stands in (affine_tile_kernel) and walk it (affine_tile_walk_kernel).  set_chain(1) sends the pairs with
 // |b| > 1024 through affine_chain_kernel in run() and in align_tiled()'s checkpoint pass: a wavefront per strip, the strips of a pair
-// chained through their boundary rows (planned by affine_chain_plan.hpp).
+// chained through their boundary rows (planned by affine_chain_plan.hpp).  set_free_ends() makes the ends of a free in all of these
+// routes: the launches then pick the kernels' ENDS instantiations, which leave every pair's end in d_end; the walks start there, and
+// pa_affine_batch_ends reports where they started and stopped.  last_row() is a cost-only pass of its own that also stores row |b|.
 #include "pa_hip_internal.hpp"
 #include "engine.hpp"
 #include "affine_kernel.hpp"
@@ -71,6 +73,12 @@ struct pa_affine_batch {
         DeviceBuf d_jobs, d_bnd, d_ticket_err;
         double pairs = 0, jobs = 0, chunks = 0, bnd_bytes_max = 0;  // the last chained pass
     } chain;
+    // Ends-free mode (set_free_ends): the switches are C.ends, the kernels leave every pair's end in d_end.
+    DeviceBuf d_end;
+    struct {
+        bool valid = false;               // a run, align or align_tiled has succeeded under the current setting
+        std::vector<int64_t> start, end;  // of that call
+    } ends;
 };
 
 namespace {
@@ -177,11 +185,21 @@ int make_plan(const pa_affine_batch& ab, const std::vector<uint32_t>& ids, Plan&
 }
 
 // affine_kernel over nwaves device waves; a whole plan's, or (the checkpoint pass with chaining on) the one-strip waves of a plan.
+// Global mode runs the instantiations without the ends-free state; a free end, or `rows` (last_row(): where the last rows go), the ones with.
+Ends ends_of(const pa_affine_batch& ab, const Ends* rows = nullptr) {
+    Ends E{ab.d_end.as<int32_t>(), nullptr, nullptr};
+    return rows ? *rows : E;
+}
 template <bool FILL, bool CKPT = false>
-bool launch(const pa_affine_batch& ab, const Wave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s) {
+bool launch(const pa_affine_batch& ab, const Wave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s, const Ends* rows = nullptr) {
     if (nwaves == 0) return true;
     const int grid = (int)((nwaves + kBlockWaves - 1) / kBlockWaves);
-    hipLaunchKernelGGL((affine_kernel<FILL, CKPT>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_waves, (int)nwaves, d_pairs, ab.C, ab.d_cost.as<int32_t>());
+    if (ab.C.ends || rows)
+        hipLaunchKernelGGL((affine_kernel<FILL, CKPT, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_waves, (int)nwaves, d_pairs, ab.C,
+                           ab.d_cost.as<int32_t>(), ends_of(ab, rows));
+    else
+        hipLaunchKernelGGL((affine_kernel<FILL, CKPT, false>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_waves, (int)nwaves, d_pairs, ab.C,
+                           ab.d_cost.as<int32_t>(), Ends{});
     return hip_ok(hipGetLastError(), FILL ? "affine_kernel<FILL> launch" : CKPT ? "affine_kernel<CKPT> launch" : "affine_kernel launch");
 }
 template <bool FILL>
@@ -234,8 +252,12 @@ bool launch_chain(pa_affine_batch& ab, const affine_chain::Plan& cp, const Chain
         if (!hip_ok(hipMemsetAsync(te, 0, 8, s), "hipMemsetAsync") || (c.words && !hip_ok(hipMemsetAsync(rows, 0xFF, c.words * 8, s), "hipMemsetAsync")))
             return false;
         const int grid = (int)((c.njobs + kBlockWaves - 1) / kBlockWaves);
-        hipLaunchKernelGGL(affine_chain_kernel<CKPT>, dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs + c.first_job, (int)c.njobs, d_pairs, ab.C, tile_cols,
-                           te, ab.d_cost.as<int32_t>());
+        if (ab.C.ends)
+            hipLaunchKernelGGL((affine_chain_kernel<CKPT, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs + c.first_job, (int)c.njobs, d_pairs, ab.C,
+                               tile_cols, te, ab.d_cost.as<int32_t>(), ends_of(ab));
+        else
+            hipLaunchKernelGGL((affine_chain_kernel<CKPT, false>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs + c.first_job, (int)c.njobs, d_pairs, ab.C,
+                               tile_cols, te, ab.d_cost.as<int32_t>(), Ends{});
         if (!hip_ok(hipGetLastError(), CKPT ? "affine_chain_kernel<CKPT> launch" : "affine_chain_kernel launch") ||
             !hip_ok(hipMemcpyAsync(&errs[k], te + 1, 4, hipMemcpyDeviceToHost, s), "D2H"))
             return false;
@@ -294,13 +316,28 @@ int run_chained(pa_affine_batch& ab, Events& ev, hipStream_t s) {
     return chain_check("pa_affine_batch_run", errs);
 }
 
-// The costs of every pair, to the caller; the end of run(), align() and align_tiled().
-int costs_out(const pa_affine_batch& ab, int32_t* cost_out, hipStream_t s) {
-    if (ab.np == 0) return 0;
-    std::vector<int32_t> c(ab.np);
-    if (!hip_ok(hipMemcpyAsync(c.data(), ab.d_cost.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
+// Every pair's end after an ends-free pass (global mode: |a|, without a copy).
+int fetch_ends(const pa_affine_batch& ab, std::vector<int32_t>& end, hipStream_t s) {
+    end.assign(ab.n.begin(), ab.n.end());
+    if (ab.np == 0 || !ab.C.ends) return 0;
+    if (!hip_ok(hipMemcpyAsync(end.data(), ab.d_end.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
         return PA_E_HIP;
-    if (cost_out) std::memcpy(cost_out, c.data(), ab.np * 4);
+    return 0;
+}
+
+// The costs of every pair, to the caller; the end of run(), align() and align_tiled().  Keeps what pa_affine_batch_ends reports: the ends,
+// and the starts a traced call found (start; a cost-only run has none: -1 under a free start, else 0).
+int costs_out(pa_affine_batch& ab, int32_t* cost_out, hipStream_t s, const std::vector<int64_t>* start = nullptr) {
+    ab.ends.valid = false;
+    std::vector<int32_t> c(ab.np), e;
+    if (ab.np && (!hip_ok(hipMemcpyAsync(c.data(), ab.d_cost.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync")))
+        return PA_E_HIP;
+    if (const int rc = fetch_ends(ab, e, s)) return rc;
+    if (cost_out && ab.np) std::memcpy(cost_out, c.data(), ab.np * 4);
+    ab.ends.end.assign(e.begin(), e.end());
+    if (start) ab.ends.start = *start;
+    else ab.ends.start.assign(ab.np, (ab.C.ends & kFreeStart) ? -1 : 0);
+    ab.ends.valid = true;
     return 0;
 }
 
@@ -407,8 +444,8 @@ extern "C" pa_affine_batch* pa_affine_batch_create(const uint8_t* const* a, cons
 extern "C" int pa_affine_batch_run(pa_affine_batch* ab, int32_t* cost_out, float* kernel_ms) {
     if (!ab) return fail(PA_E_ARG, "pa_affine_batch_run: NULL batch");
     if (kernel_ms) *kernel_ms = 0;
-    if (ab->np == 0) return 0;
     hipStream_t s = 0;
+    if (ab->np == 0) return costs_out(*ab, cost_out, s);  // (nothing to copy: the call counts for pa_affine_batch_ends)
     Events ev;
     if (!ev.make()) return PA_E_HIP;
     if (ab->chain.on) ab->chain.pairs = ab->chain.jobs = ab->chain.chunks = ab->chain.bnd_bytes_max = 0;
@@ -435,6 +472,7 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
                         code_bytes_of(ab->n[p], ab->m[p]), budget);
     hipStream_t s = 0;
     std::vector<std::string> cigars(ab->np);
+    std::vector<int64_t> starts(ab->np, 0);
     ab->trace_chunks = 0;
     float fwd_total = 0, trace_total = 0;
     DeviceBuf d_codes, d_ops, d_walk, d_wout;
@@ -463,13 +501,16 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
             w.m = Q.m;
             w.H = Q.H;
             w.cap = Q.n + Q.m;
+            w.out = Q.out;
+            w.free_start = ab->C.ends & kFreeStart;
         }
         const int nw = (int)walks.size();
         Events ev;
         if (!ev.make() || !upload(d_walk, walks.data(), walks.size() * sizeof(Walk), s) || !d_wout.reserve(std::max<size_t>(nw * sizeof(WalkOut), 16)) ||
             !hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<true>(*ab, P, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event"))
             return PA_E_HIP;
-        hipLaunchKernelGGL(affine_walk_kernel, dim3((nw + 63) / 64), dim3(64), 0, s, d_walk.as<Walk>(), nw, d_wout.as<WalkOut>());
+        hipLaunchKernelGGL(affine_walk_kernel, dim3((nw + 63) / 64), dim3(64), 0, s, d_walk.as<Walk>(), nw, d_wout.as<WalkOut>(),
+                           (ab->C.ends & kFreeEnd) ? ab->d_end.as<int32_t>() : nullptr);
         std::vector<WalkOut> wout(nw);
         std::vector<uint8_t> ops(ops_bytes);
         if (!hip_ok(hipGetLastError(), "affine_walk_kernel launch") || !hip_ok(hipEventRecord(ev.e[2], s), "event") ||
@@ -487,10 +528,11 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
             if (o.status != 0)
                 return fail(PA_E_INTERNAL, "pa_affine_batch_align: pair %u: %s", P.pairs[k].out, o.status == 1 ? "bad traceback code" : "path longer than its buffer");
             cigars[P.pairs[k].out] = cigar_of(ops.data() + ops_off[k], o.nops);
+            starts[P.pairs[k].out] = o.start;
         }
         c0 += ids.size();
     }
-    if (const int rc = costs_out(*ab, cost_out, s)) return rc;
+    if (const int rc = costs_out(*ab, cost_out, s, &starts)) return rc;
     if (forward_ms) *forward_ms = fwd_total;
     if (trace_ms) *trace_ms = trace_total;
     return cigar_out ? give_cstrings(cigars, cigar_out) : 0;
@@ -511,7 +553,7 @@ struct TiledChunk {
     DeviceBuf d_pwaves, d_cjobs;  // chained: the plan's one-strip waves, and the chain jobs of the others
 };
 
-// The chunk's buffers, the checkpoint pass, and every walk at (n, m, main).
+// The chunk's buffers, the checkpoint pass, and every walk at (n, m, main) -- with a free end at (end, m, main).
 int tiled_forward(pa_affine_batch& ab, const std::vector<uint32_t>& ids, uint32_t C, TiledChunk& ch, hipStream_t s, float* ms) {
     Plan& P = ch.plan;
     size_t ck_words = 0;
@@ -572,7 +614,14 @@ int tiled_forward(pa_affine_batch& ab, const std::vector<uint32_t>& ids, uint32_
         !hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync") ||
         !hip_ok(hipEventElapsedTime(ms, ev.e[0], ev.e[1]), "hipEventElapsedTime"))
         return PA_E_HIP;
-    return chain_check("pa_affine_batch_align_tiled", errs);
+    if (const int rc = chain_check("pa_affine_batch_align_tiled", errs)) return rc;
+    if (ab.C.ends & kFreeEnd) {  // every walk starts at (end, m, main), the end the checkpoint pass found
+        std::vector<int32_t> end;
+        if (const int rc = fetch_ends(ab, end, s)) return rc;
+        for (size_t k = 0; k < np; ++k) ch.st[k].i = end[P.pairs[k].out];
+        if (!upload(ch.d_state, ch.st.data(), np * sizeof(WalkState), s) || !hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
+    }
+    return 0;
 }
 
 // The tile job of every unfinished pair, grouped into waves like the planner's (consecutive packed pairs of one width share a wave).
@@ -584,7 +633,7 @@ int tiled_jobs(pa_affine_batch& ab, uint32_t C, TiledChunk& ch, std::vector<Tile
         const WalkState& S = ch.st[k];
         if (S.status != 0)
             return fail(PA_E_INTERNAL, "pa_affine_batch_align_tiled: pair %u: %s", Q.out, S.status == 1 ? "bad traceback code" : "path longer than its buffer");
-        if (S.i == 0 && S.j == 0 && S.layer == 0) continue;
+        if (S.j == 0 && S.layer == 0 && (S.i == 0 || (ab.C.ends & kFreeStart))) continue;  // walk_done
         if (S.i < 0 || S.j < 0 || (uint32_t)S.i > Q.n || (uint32_t)S.j > Q.m || ++ch.visits[k] > tile_visits_max(Q.n, Q.m, C) + 1)
             return fail(PA_E_INTERNAL, "pa_affine_batch_align_tiled: pair %u: the walk left its %u tiles at (%d, %d)", Q.out,
                         tile_visits_max(Q.n, Q.m, C), S.i, S.j);
@@ -630,10 +679,11 @@ int tiled_round(pa_affine_batch& ab, TiledChunk& ch, const std::vector<TileJob>&
         !hip_ok(hipMemcpyAsync(ch.d_twaves.ptr, waves.data(), waves.size() * sizeof(TileWave), hipMemcpyHostToDevice, s), "H2D") ||
         !hip_ok(hipEventRecord(ev.e[0], s), "event"))
         return PA_E_HIP;
-    hipLaunchKernelGGL(affine_tile_kernel, dim3((nw + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, ch.d_twaves.as<TileWave>(), nw,
-                       ch.d_jobs.as<TileJob>(), ab.C);
+    const bool fs = ab.C.ends & kFreeStart;
+    hipLaunchKernelGGL(fs ? affine_tile_kernel<true> : affine_tile_kernel<false>, dim3((nw + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s,
+                       ch.d_twaves.as<TileWave>(), nw, ch.d_jobs.as<TileJob>(), ab.C);
     if (!hip_ok(hipGetLastError(), "affine_tile_kernel launch") || !hip_ok(hipEventRecord(ev.e[1], s), "event")) return PA_E_HIP;
-    hipLaunchKernelGGL(affine_tile_walk_kernel, dim3((nj + 63) / 64), dim3(64), 0, s, ch.d_jobs.as<TileJob>(), nj);
+    hipLaunchKernelGGL(affine_tile_walk_kernel, dim3((nj + 63) / 64), dim3(64), 0, s, ch.d_jobs.as<TileJob>(), nj, fs ? 1 : 0);
     float f = 0, w = 0;
     if (!hip_ok(hipGetLastError(), "affine_tile_walk_kernel launch") || !hip_ok(hipEventRecord(ev.e[2], s), "event") ||
         !hip_ok(hipMemcpyAsync(ch.st.data(), ch.d_state.ptr, ch.st.size() * sizeof(WalkState), hipMemcpyDeviceToHost, s), "D2H") ||
@@ -667,6 +717,7 @@ extern "C" int pa_affine_batch_align_tiled(pa_affine_batch* ab, uint32_t tile_co
                         tiled_bytes_of(ab->n[p], ab->m[p], C), budget);
     hipStream_t s = 0;
     std::vector<std::string> cigars(ab->np);
+    std::vector<int64_t> starts(ab->np, 0);
     ab->tiled = {};
     if (ab->chain.on) ab->chain.pairs = ab->chain.jobs = ab->chain.chunks = ab->chain.bnd_bytes_max = 0;
     float fwd_total = 0, refill_total = 0, walk_total = 0;
@@ -692,10 +743,13 @@ extern "C" int pa_affine_batch_align_tiled(pa_affine_batch* ab, uint32_t tile_co
         if (ch.ops_bytes && (!hip_ok(hipMemcpyAsync(ops.data(), ch.d_ops.ptr, ch.ops_bytes, hipMemcpyDeviceToHost, s), "D2H") ||
                              !hip_ok(hipStreamSynchronize(s), "sync")))
             return PA_E_HIP;
-        for (size_t k = 0; k < ch.plan.pairs.size(); ++k) cigars[ch.plan.pairs[k].out] = cigar_of(ops.data() + ch.ops_off[k], ch.st[k].nops);
+        for (size_t k = 0; k < ch.plan.pairs.size(); ++k) {
+            cigars[ch.plan.pairs[k].out] = cigar_of(ops.data() + ch.ops_off[k], ch.st[k].nops);
+            starts[ch.plan.pairs[k].out] = ch.st[k].i;
+        }
         c0 += ids.size();
     }
-    if (const int rc = costs_out(*ab, cost_out, s)) return rc;
+    if (const int rc = costs_out(*ab, cost_out, s, &starts)) return rc;
     if (forward_ms) *forward_ms = fwd_total;
     if (refill_ms) *refill_ms = refill_total;
     if (walk_ms) *walk_ms = walk_total;
@@ -717,6 +771,67 @@ extern "C" int pa_affine_batch_set_chain(pa_affine_batch* ab, int on) {
     if (on)
         if (const int rc = chain_build(*ab, 0)) return rc;
     ab->chain.on = on != 0;
+    return 0;
+}
+
+extern "C" int pa_affine_batch_set_free_ends(pa_affine_batch* ab, int free_start, int free_end) {
+    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_set_free_ends: NULL batch");
+    if ((free_start != 0 && free_start != 1) || (free_end != 0 && free_end != 1))
+        return fail(PA_E_ARG, "pa_affine_batch_set_free_ends: free_start = %d, free_end = %d: each is 0 or 1", free_start, free_end);
+    if ((free_start || free_end) && !ab->d_end.reserve(std::max<size_t>(ab->np, 1) * 4)) return PA_E_HIP;
+    ab->C.ends = (free_start ? kFreeStart : 0) | (free_end ? kFreeEnd : 0);
+    ab->ends.valid = false;
+    return 0;
+}
+
+extern "C" int pa_affine_batch_ends(const pa_affine_batch* ab, int64_t* start_out, int64_t* end_out) {
+    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_ends: NULL batch");
+    if (!ab->ends.valid) return fail(PA_E_ARG, "pa_affine_batch_ends: no run, align or align_tiled has succeeded under the current setting");
+    if (start_out && ab->np) std::memcpy(start_out, ab->ends.start.data(), ab->np * 8);
+    if (end_out && ab->np) std::memcpy(end_out, ab->ends.end.data(), ab->np * 8);
+    return 0;
+}
+
+// A cost-only pass of its own over the pairs that are asked for, in chunks whose rows fit the budget.  (It leaves costs and ends of its
+// chunks in d_cost and d_end, which every other call reads only right after its own pass.)
+extern "C" int pa_affine_batch_last_row(pa_affine_batch* ab, int32_t* out, const uint64_t* offsets) {
+    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_last_row: NULL batch");
+    if (ab->np == 0) return 0;
+    if (!out || !offsets) return fail(PA_E_ARG, "pa_affine_batch_last_row: NULL array");
+    const size_t budget = trace_budget("PA_AFFINE_TRACE_BUDGET_MB");
+    std::vector<uint32_t> want;
+    for (const uint32_t p : ab->order)
+        if (offsets[p] != UINT64_MAX) {
+            if (((size_t)ab->n[p] + 1) * 4 > budget)
+                return fail(PA_E_ARG, "pa_affine_batch_last_row: pair %u: %zu bytes of last row exceed the budget of %zu bytes", p, ((size_t)ab->n[p] + 1) * 4,
+                            budget);
+            want.push_back(p);
+        }
+    hipStream_t s = 0;
+    DeviceBuf d_rows, d_off;
+    if (!ab->d_end.reserve(ab->np * 4)) return PA_E_HIP;
+    std::vector<uint64_t> off(ab->np);
+    std::vector<int32_t> rows;
+    for (size_t c0 = 0; c0 < want.size();) {
+        std::fill(off.begin(), off.end(), UINT64_MAX);
+        size_t c1 = c0, words = 0;
+        while (c1 < want.size() && (c1 == c0 || (words + ab->n[want[c1]] + 1) * 4 <= budget)) {
+            off[want[c1]] = words;
+            words += (size_t)ab->n[want[c1]] + 1;
+            ++c1;
+        }
+        const std::vector<uint32_t> ids(want.begin() + c0, want.begin() + c1);
+        Plan P;
+        if (const int rc = make_plan(*ab, ids, P, nullptr, s)) return rc;
+        rows.resize(words);
+        if (!d_rows.reserve(words * 4) || !upload(d_off, off.data(), off.size() * 8, s)) return PA_E_HIP;
+        const Ends E{ab->d_end.as<int32_t>(), d_rows.as<int32_t>(), d_off.as<uint64_t>()};
+        if (!launch<false>(*ab, P.d_waves.as<Wave>(), P.waves.size(), P.d_pairs.as<Pair>(), s, &E) ||
+            !hip_ok(hipMemcpyAsync(rows.data(), d_rows.ptr, words * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
+            return PA_E_HIP;
+        for (const uint32_t p : ids) std::memcpy(out + offsets[p], rows.data() + off[p], ((size_t)ab->n[p] + 1) * 4);
+        c0 = c1;
+    }
     return 0;
 }
 

@@ -73,6 +73,26 @@ int pa_affine_batch_set_chain(pa_affine_batch* ab, int on);
  * ran chained, its chunks, and the largest chunk's boundary-row bytes.  Every pointer may be NULL. */
 void pa_affine_batch_chain_info(const pa_affine_batch* ab, double* on, double* chain_pairs, double* chain_jobs, double* chunks,
                                 double* bnd_bytes_max);
+/* Ends-free (semi-global) mode: a is the text, b the pattern, and b is always consumed whole.  Both switches are 0 by default, and with
+ * both 0 nothing changes.  There is no counterpart in the reference (its only semi-global code is pa_bitpacking::search, unit costs).
+ *   free_start = 1: M(i, 0) = 0 for every column i (I(i, 0) stays absent): a prefix of a costs nothing.
+ *   free_end = 1:   the cost is the minimum of M(i, |b|) over i = 0 .. |a|, and `end` the lowest i that reaches it (the tie rule of
+ *                   pa_search_batch_run); without it end = |a|.
+ * So the cost is the least global cost of (a[s:e], b) over the allowed s <= e (s = 0 unless free_start, e = |a| unless free_end).  The
+ * CIGAR is the same first-parent walk over the ends-free matrix, from (end, |b|, main); with free_start it stops at the first state
+ * (i, 0, main) it reaches and start = i, else it runs to (0, 0, main) and start = 0.  It describes a[start:end] against b: the free
+ * flanks are not printed.  The setting holds for every later run, align and align_tiled (all routes, chained or not) and invalidates what
+ * pa_affine_batch_ends would report.  A NULL batch, or a value other than 0 and 1, is PA_E_ARG. */
+int pa_affine_batch_set_free_ends(pa_affine_batch* ab, int free_start, int free_end);
+/* start and end of every pair in the last successful run, align or align_tiled under the current setting (either pointer may be NULL).
+ * After a cost-only run start_out[p] is -1 when free_start is on and 0 otherwise.  Before any such call, or after a change of the
+ * setting, PA_E_ARG. */
+int pa_affine_batch_ends(const pa_affine_batch* ab, int64_t* start_out, int64_t* end_out);
+/* The last row under the current setting: M(i, |b|) for i = 0 .. |a| of pair p to out + offsets[p]; offsets[p] == UINT64_MAX skips the
+ * pair.  In global mode these are the costs of b against every prefix of a, the last one the pair's cost.  Runs a cost-only pass of its
+ * own over the pairs asked for, in chunks whose rows (4 bytes per column, device memory taken only here) stay within
+ * PA_AFFINE_TRACE_BUDGET_MB or a quarter of the free device memory; a pair whose row alone exceeds it is PA_E_ARG naming the pair. */
+int pa_affine_batch_last_row(pa_affine_batch* ab, int32_t* out, const uint64_t* offsets);
 /* Plan shape of run() with chaining off (the setting does not change it): wavefronts launched, pairs packed into segments (|b| <= 1024), pairs on strips of their own, lanes carrying rows
  * of b (sum of ceil(max(|b|, 1) / 16)) over lanes launched (64 per wavefront and strip), and the chunks of the last align(). */
 void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,

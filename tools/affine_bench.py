@@ -1,7 +1,8 @@
 """Batched gap-affine alignment (pa_affine_batch_*): kernel time, GCUPS and pairs/s, costs only and traced, for three shapes under
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
-    python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--models affine,unit]
+    python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends]
+                                 [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
 tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
@@ -10,7 +11,12 @@ the line shows the fastest repeat and lists them all.  The tiled route also trac
 
 --chain measures the chained route (AffineBatch.set_chain) instead: for each shape the cost-only pass and the tiled traced pass with
 chaining off and on, on one batch in one process, alternating, each warmed once and then R times; it prints both routes' fastest
-repeats, their ratio and chain_info().  The shape 100k1 is one 100 kbp pair."""
+repeats, their ratio and chain_info().  The shape 100k1 is one 100 kbp pair.
+
+--ends measures the ends-free mode (AffineBatch.set_free_ends, both ends of the text free) on two mapping shapes of its own, whatever
+--shapes says: 100 000 patterns of 150 bp in 400 bp windows, and 4096 reads of 10 kbp in 12 kbp windows (traced: --trace-pairs of them).
+Each runs cost-only, traced and tiled, global and ends-free alternating on one batch, each warmed once and then R times: the cells are
+the same, so the ratio of the fastest repeats is what the mode costs."""
 from __future__ import annotations
 
 import argparse
@@ -163,6 +169,52 @@ def chain_legs(title, pairs, cm, mname, tile_cols, reps):
     print(f"{'':44s} {mname:14s} chain_info: {ci}", flush=True)
 
 
+def ends_shape(name, rng):
+    """(text, pattern) pairs: a mutated piece of the window, somewhere inside it."""
+    count, plen, wlen = (100_000, 150, 400) if name == "map150" else (4096, 10_000, 12_000)
+    pairs = []
+    for _ in range(count):
+        w = rand_seq(rng, wlen)
+        off = int(rng.integers(0, wlen - plen + 1))
+        pairs.append((w, mutate(rng, w[off:off + plen], 0.05)))
+    return f"{count} x {plen} bp in {wlen} bp windows", pairs
+
+
+def ends_legs(title, pairs, tp, cm, mname, tile_cols, reps):
+    """Global and ends-free, alternating: run() on a batch of `pairs`, align() and align_tiled() on a traced batch of `tp`."""
+    cells, tcells = float(sum(len(x) * len(y) for x, y in pairs)), float(sum(len(x) * len(y) for x, y in tp))
+    b, tb = AffineBatch(pairs, cm), AffineBatch(tp, cm, trace=True)
+    ms = {(leg, on): [] for leg in ("cost", "traced", "tiled") for on in (False, True)}
+    inside = 0
+    for rep_ in range(reps + 1):  # the first round warms every route
+        for on in (False, True):
+            b.set_free_ends(on, on)
+            tb.set_free_ends(on, on)
+            b.run()
+            k = b.last_kernel_ms
+            tb.align()
+            u = tb.last_forward_ms + tb.last_trace_ms
+            tb.align_tiled(tile_cols)
+            t = tb.last_forward_ms + tb.last_refill_ms + tb.last_trace_ms
+            if on:
+                se = tb.ends()
+                inside = int(((se[:, 0] > 0) & (se[:, 1] < np.array([len(x) for x, _ in tp]))).sum())
+            if rep_:
+                ms[("cost", on)].append(k)
+                ms[("traced", on)].append(u)
+                ms[("tiled", on)].append(t)
+    ti = tb.tiled_info()
+    b.close()
+    tb.close()
+    for leg, c, npairs in (("cost", cells, len(pairs)), ("traced", tcells, len(tp)), ("tiled", tcells, len(tp))):
+        g, e = min(ms[(leg, False)]), min(ms[(leg, True)])
+        print(f"{title:44s} {mname:14s} {leg + ':':10s} global {g:10.2f} ms {c / g / 1e6:8.1f} GCUPS | ends-free {e:10.2f} ms {c / e / 1e6:8.1f} GCUPS"
+              f" | ends-free / global {e / g:6.3f}  ({npairs} pairs; repeats {' '.join(f'{x:.2f}' for x in ms[(leg, False)])} |"
+              f" {' '.join(f'{x:.2f}' for x in ms[(leg, True)])})", flush=True)
+    print(f"{'':44s} {mname:14s} ends-free: {inside} of {len(tp)} traced pairs start after column 0 and end before |a|; tiled: {ti['tile_jobs']} tile jobs,"
+          f" {ti['refill_cells'] / tcells:.3f} of the cells filled", flush=True)
+
+
 def traced(tp, cm, mname, untiled, tile_cols, reps, warm=True, note=""):
     """The traced lines of one batch: the untiled route (if asked for) and the tiled one, alternating."""
     tcells = float(sum(len(x) * len(y) for x, y in tp))
@@ -200,6 +252,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3, help="timed repeats of each traced route")
     ap.add_argument("--trace-pairs", type=int, default=512, help="traced runs of the 10 kbp shape use this many of its pairs")
     ap.add_argument("--chain", action="store_true", help="measure the chained route against the unchained one instead (see above)")
+    ap.add_argument("--ends", action="store_true", help="measure the ends-free mode against the global one instead (see above)")
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -208,6 +261,12 @@ def main():
     rng = np.random.default_rng(1)
     models = {"affine(4,6,2)": AffineCost.affine(4, 6, 2), "unit()": AffineCost.unit()}
     models = {k: v for k, v in models.items() if k.split("(")[0] in args.models.split(",")}
+    if args.ends:
+        for sname in ("map150", "map10k"):
+            title, pairs = ends_shape(sname, rng)
+            for mname, cm in models.items():
+                ends_legs(title, pairs, pairs if sname == "map150" else pairs[: args.trace_pairs], cm, mname, args.tile_cols, args.reps)
+        return
     for sname in args.shapes.split(","):
         title, pairs = shape(sname, rng)
         cells = float(sum(len(x) * len(y) for x, y in pairs))
