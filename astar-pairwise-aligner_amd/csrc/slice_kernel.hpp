@@ -28,8 +28,10 @@
 // MI355X_MICROARCH.md R2: a boundary row is preset to hp = hm = ~0, which no real delta pair can be, and the consumer puts that value back).  Jobs (group, strip) are claimed by an
 // atomic ticket in producer-before-consumer order, so a consumer's producer has always started; every poll is bounded.
 //
-// The step: 7 R + 11 VALU instructions in ONE basic block that every lane runs in every step -- eight DPP instructions (PA_SLICE_FEED), the
-// rows, one store, two running counters and the capture test.  No lane is predicated: a lane in front of column 0 is kept in the left
+// The step: 7 R + 6 VALU instructions in ONE basic block that every lane runs in every step -- two DPP instructions (PA_SLICE_FEED), the
+// rows, one store, two running counters, the capture test and the mask that makes the column counter an LDS address -- beside one
+// ds_read_b128 and its lgkmcnt wait: the column's code planes and the boundary row come from a per-wavefront ring in LDS ("The column
+// ring" below; until round 16 they travelled down the lanes and the chunk registers rotated: eight DPP, 7 R + 11).  No lane is predicated: a lane in front of column 0 is kept in the left
 // column's state by the NEUTRAL border (hp, hm) = (0, ~0) that the pipeline registers start with, a lane behind the last column computes
 // what nothing reads; the store's offset and the capture's column are per-lane counters, the step counter is scalar (see the kernel).
 //
@@ -150,27 +152,40 @@ __device__ __forceinline__ void st_boundary(uint2* p, uint32_t hp, uint32_t hm) 
             : [a0_] "v"(a0), [a1_] "v"(a1), [nb0A_] "v"(nb0A), [nb1A_] "v"(nb1A), [hpp_] "v"(hpp), [hmp_] "v"(hmp));                    \
     } while (0)
 
-// The top of a step: every lane takes what the lane above it had a step ago -- the column's two code planes (a0, a1, in place) and the
-// bottom row's (hp, hm) of the column (from ohp / ohm into hpp / hmp) --, lane 0 the chunk registers' value of its own lane, and the four
-// chunk registers rotate one lane.  v_cndmask_b32_dpp does the first in ONE instruction a register: vcc = 1 selects the second source in
-// lane 0 and the DPP source (wave_shr:1; bound_ctrl, so lane 0 -- which has no source lane -- is written all the same) in every other lane;
-// v_mov_b32_dpp keeps `old` in lane 0 instead, which costs a copy of the chunk register in front and, for a0 / a1, one behind.  The
-// registers a DPP operand reads must not have been written by the two instructions before (the assembler adds no s_nop inside asm): the
-// rotations come first and read only what the step before rotated, ohp / ohm -- written by the last rows of the step before -- come last.
-#define PA_SLICE_FEED(a0, a1, hpp, hmp, ohp, ohm, cAx, cAy, cHx, cHy)                                                                    \
+// The column ring (round 16).  What a lane needs of its column besides the row above -- the column's two code planes (a0, a1) and, in lane
+// 0, the boundary row's (hp, hm) -- does not change on its way down the lanes, so it does not travel: it sits in LDS, one 16-byte entry
+// (a0, a1, hp_in, hm_in) per column at index column mod kRingEntries, and every lane reads the entry of ITS OWN column.  A workgroup is one
+// wavefront, so the ring is the wavefront's own, LDS operations of one wavefront are carried out in order, and no barrier is involved.
+//   written  once per chunk of 64 columns: lane j writes column 64 q + j at the chunk top (one ds_write_b128), after the poll, where the
+//            chunk's boundary values are final;
+//   read     once per step (one ds_read_b128): behind its rows every lane reads the entry of the column it works on in the NEXT step.  At
+//            the chunk top every lane reads the entry of the chunk's first step again, behind the write: lane 0's column 64 q was not in
+//            the ring when the step before asked for it.
+// Size.  The entries alive at a chunk top are those of the columns the chunk's steps 64 q .. 64 q + 63 work on: 64 q - 63 (lane 63 in
+// the first step) .. 64 q + 63 (lane 0 in the last), 127 columns; the write of columns 64 q .. 64 q + 63 must not land on the entry of a
+// column from 64 q - 63 on that a later read of this chunk still wants, i.e. kRingEntries >= 127 + 1 (the one extra: the read for the next
+// step in the chunk's last step, column 64 q + 64 in lane 0, which nothing uses).  A power of two, so that the index is one v_and of the
+// column counter: 128 is the minimum for this order of write and reads (tests/test_slice_lds_ring.py steps a model of it); 256 is taken,
+// 4 KB a wavefront and 32 KB of a CU's 160 KB at 8 wavefronts, so that a write a whole chunk ahead of its reads (192 entries) would fit too.
+// Lanes in front of column 0 read the 63 entries in front of entry 0; they are zeroed once per job, so a0 = a1 = 0 there as the
+// pipeline registers had it (the neutral border makes z = ~0 whatever eq is: the value cannot matter, but it is the same in every run).
+constexpr int kRingEntries = 256;
+constexpr uint32_t kRingMask = (uint32_t)(kRingEntries - 1) * 16u;  // on the column counter in units of 16 bytes
+
+// The top of a step: every lane takes the bottom row's (hp, hm) that the lane above it had a step ago (from ohp / ohm into hpp / hmp), lane 0
+// the boundary half (hin, min) of its own column's ring entry.  v_cndmask_b32_dpp does that in ONE instruction a register: vcc = 1 selects
+// the second source in lane 0 and the DPP source (wave_shr:1; bound_ctrl, so lane 0 -- which has no source lane -- is written all the same)
+// in every other lane.  The registers a DPP operand reads must not have been written by the two instructions before (the assembler adds no
+// s_nop inside asm): ohp / ohm are written by the last rows of the step before, and both row macros end with two instructions (vp', vm')
+// BEHIND the ones that write hpo / hmo; the s_mov and the loop's branch come on top.  The column's code planes are not fed at all: the rows
+// read a0 / a1 straight from the registers the ring entry was read into.
+#define PA_SLICE_FEED(hpp, hmp, ohp, ohm, hin, min_)                                                                                     \
     asm volatile(                                                                                                                       \
         "s_mov_b64 vcc, 1\n\t"                                                                                                          \
-        "v_cndmask_b32_dpp %[a0_], %[a0_], %[cAx_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                         \
-        "v_cndmask_b32_dpp %[a1_], %[a1_], %[cAy_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                         \
-        "v_cndmask_b32_dpp %[hpp_], %[ohp_], %[cHx_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                       \
-        "v_cndmask_b32_dpp %[hmp_], %[ohm_], %[cHy_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                       \
-        "v_mov_b32_dpp %[cAx_], %[cAx_] wave_rol:1 row_mask:0xf bank_mask:0xf\n\t"                                                      \
-        "v_mov_b32_dpp %[cAy_], %[cAy_] wave_rol:1 row_mask:0xf bank_mask:0xf\n\t"                                                      \
-        "v_mov_b32_dpp %[cHx_], %[cHx_] wave_rol:1 row_mask:0xf bank_mask:0xf\n\t"                                                      \
-        "v_mov_b32_dpp %[cHy_], %[cHy_] wave_rol:1 row_mask:0xf bank_mask:0xf"                                                          \
-        : [a0_] "+v"(a0), [a1_] "+v"(a1), [hpp_] "=&v"(hpp), [hmp_] "=&v"(hmp), [cAx_] "+v"(cAx), [cAy_] "+v"(cAy), [cHx_] "+v"(cHx),   \
-          [cHy_] "+v"(cHy)                                                                                                              \
-        : [ohp_] "v"(ohp), [ohm_] "v"(ohm)                                                                                              \
+        "v_cndmask_b32_dpp %[hpp_], %[ohp_], %[hin_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"                       \
+        "v_cndmask_b32_dpp %[hmp_], %[ohm_], %[hmin_], vcc wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"                          \
+        : [hpp_] "=&v"(hpp), [hmp_] "=&v"(hmp)                                                                                          \
+        : [ohp_] "v"(ohp), [ohm_] "v"(ohm), [hin_] "v"(hin), [hmin_] "v"(min_)                                                          \
         : "vcc")
 
 // ticket_err[0] = ticket, [1] = error code (first one wins)
@@ -178,6 +193,7 @@ template <int R>
 __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict__ jobs, int njobs, const SliceGroup* __restrict__ groups,
                                                       const SliceEvent* __restrict__ events, const uint2* __restrict__ A, const uint2* __restrict__ B,
                                                       uint2* H, uint2* V, uint32_t* ticket_err, unsigned long long* dbg) {
+    __shared__ uint4 ring[kRingEntries];  // the column ring of this wavefront (a workgroup is one wavefront)
     const int lane = (int)threadIdx.x;
     const uint32_t wave_slot = (uint32_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 4) & 15u;  // HW_REG_HW_ID[3:0]: this wavefront's slot on its SIMD
     for (;;) {
@@ -209,9 +225,9 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
             vm[i] = 0u;
         }
         // Columns come in CHUNKS of 64: lane j loads column 64 q + j of the group's planes and of the boundary row above (one coalesced load
-        // each per chunk, issued a whole chunk ahead); the chunk registers ROTATE one lane per step (DPP wave_rol:1), so that at step j lane 0 finds column 64 q + j in its own lane,
-        // and everything -- the column's two code planes AND the row's (hp, hm) -- then moves down the lanes one lane per step through DPP
-        // wave_shr:1.  No vector memory load sits in the step loop, so no wait does either.
+        // each per chunk, issued a whole chunk ahead) and writes both into the column ring in LDS at the chunk top ("The column ring" above);
+        // in every step every lane reads its own column's entry from there, and only the row's (hp, hm) moves down the lanes, one lane per
+        // step through DPP wave_shr:1.  No vector memory load sits in the step loop, so no vmcnt wait does either.
         //
         // The wait for the prefetched chunk (round 6).  Loads and stores of a wavefront retire in order through ONE counter (vmcnt), and the
         // compiler's wait for the next chunk's registers -- placed at their first use, the top of the next chunk -- was vmcnt(0): behind the
@@ -227,7 +243,10 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
         //    the asm statement on; one place issues them and one place consumes them, on every path (no prefetch in a strip's last chunk:
         //    every other chunk has all 64 steps), so there is no join that would need a copy;
         //  * no compiler-visible wait may sit in the step loop (the row loads of the job are waited for before the loops);
-        //  * more operations in between (the capture's atomics) only make the wait stronger.
+        //  * more operations in between (the capture's atomics) only make the wait stronger;
+        //  * the ring's ds_write / ds_read are LDS operations: they count on lgkmcnt, not on vmcnt, so they neither add to nor take from
+        //    the stores this argument counts.  The compiler keeps their score itself (plain C++ accesses of a __shared__ array): its wait
+        //    for a step's entry is an lgkmcnt wait at the top of the step.
         constexpr int kWaitStep = 8;
         // The pipeline registers: what this lane worked on in the step before and the lane below takes in this one.  (hp, hm) starts as
         // (0, ~0), the NEUTRAL border: a row with vp = ~0, vm = 0 that takes it in has z = ~0 whatever its eq, so hm = vp = ~0, hp = 0,
@@ -235,21 +254,26 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
         // predicate: it runs the rows like every other lane and changes nothing (tests/test_slice_neutral_border.py).  A lane behind the last
         // column computes garbage that nothing reads: its columns were captured at c + 1 == ev_col <= n, its bottom row only goes to lanes
         // that are behind the end too, and its boundary store is out of the descriptor's range.
+        // (a0, a1: the code planes of the lane's column, taken from its ring entry in every step; 0 in front of column 0 -- the zeroed entries.)
         uint32_t a0 = 0, a1 = 0, o_hp = 0, o_hm = ~0u;
         // Per-lane running counters instead of index arithmetic in the step: `off`, the boundary store's byte offset (+ 8 a step), is
         // 8 c in lane 63 of a strip that has a strip below -- out of the descriptor's n * 8 bytes while c < 0 ((uint32)c * 8 >= 2^32 - 8 * 63)
         // and from c = n on -- and in every other lane starts at 0x7FFFFFF0 and stays out of range for the whole job (n + 63 steps, n < 2^27:
-        // no wrap); `cnt` = c + 1, the columns this lane has finished after the step, is real in every lane (every lane captures).
+        // no wrap); `cnt` = c + 1, the columns this lane has finished after the step, is real in every lane (every lane captures).  The
+        // step keeps it in units of 16 bytes (cnt16): masked, it is the address of the ring entry of the lane's NEXT column, and the capture
+        // test compares it with the event's column in the same units (n + 63 < 2^27, choose_rows_per_lane: 16 (n + 63) does not wrap).
         uint32_t off = (lane == 63 && has_out) ? (uint32_t)(-lane) * 8u : 0x7FFFFFF0u;
         int cnt = 1 - lane;
-        constexpr int kNoEvent = INT32_MIN;  // no lane's cnt (1 - 63 .. n + 63) is ever this
+        int cnt16 = cnt * 16;
+        constexpr int kNoEvent = INT32_MIN;  // no lane's cnt16 (16 (1 - 63) .. 16 (n + 63)) is ever this
         uint32_t ev_i = 0;
-        int ev_col = ev[0].col;
+        int ev_col16 = ev[0].col * 16;
         const int nchunks = (n + 63 + 63) / 64;  // steps 0 .. n + 62
         const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc((void*)Hout, 0, (int)((uint32_t)n * 8u), 0x00020000);
         unsigned long long nA = 0, nH = ~0ull;
         uint2 kA = Ag[lane], kH = make_uint2(~0u, 0u);  // chunk 0: ordinary loads
         if (has_in) kH = ld_boundary(Hin + lane);
+        ring[kRingEntries - 64 + lane] = make_uint4(0u, 0u, 0u, ~0u);  // the entries in front of column 0: what the lanes in front of it read
         __builtin_amdgcn_s_waitcnt(0);  // nothing in flight when the loops start (a wait the compiler derives from these loads would sit inside them)
         for (int q = 0; q < nchunks; ++q) {
             // Fair shares of the SIMD.  With equal priority the OLDER of a SIMD's two wavefronts wins every arbitration (MI355X_MICROARCH.md:
@@ -268,7 +292,7 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
             else __builtin_amdgcn_s_setprio(0);
 #endif
             uint2 cA = kA, cH = kH;
-            const int col = q * 64 + lane;  // the column this lane holds for lane 0
+            const int col = q * 64 + lane;  // the column this lane loaded and writes into the ring
             if (has_in) {
                 // The strip above has to be past this chunk.  It normally is (it started first and runs at the same pace); when this strip has
                 // caught up, waiting here until all 64 columns are there lets it run them at full speed.  (Letting the strip above get three
@@ -305,6 +329,10 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
                 // memory like the producer's; it is older than the prefetch loads below, so the wait for them covers it as well.
                 if (col < n) st_boundary(const_cast<uint2*>(Hin) + col, ~0u, ~0u);
             }
+            // This chunk's columns go into the ring -- a strip without a strip above writes the matrix's top border (kH) --, and every lane
+            // reads the entry of the column of the chunk's first step, 64 q - lane = cnt - 1, behind that write.
+            ring[col & (kRingEntries - 1)] = make_uint4(cA.x, cA.y, cH.x, cH.y);
+            uint4 r = *(const uint4*)((const char*)ring + ((uint32_t)(cnt16 - 16) & kRingMask));
             // the next chunk's values, a whole chunk ahead of their use (issued after the test above: a wait for THIS chunk's values must not
             // cover loads that have only just been issued)
             const int pcol = min(col + 64, n + kPad - 1);  // (behind the last column: the pad, never used)
@@ -322,10 +350,12 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
                     kA = make_uint2((uint32_t)nA, (uint32_t)(nA >> 32));
                     if (has_in) kH = make_uint2((uint32_t)nH, (uint32_t)(nH >> 32));
                 }
-                // lane 0 takes the chunk registers' value of ITS lane -- they rotate one lane per step, so that is column 64 q + j --, every other
-                // lane the value the lane above it had a step ago
+                // the column's code planes: this lane's ring entry; the row above: lane 0 takes the boundary half of that entry, every other
+                // lane what the lane above it put out a step ago
                 uint32_t hpp, hmp;
-                PA_SLICE_FEED(a0, a1, hpp, hmp, o_hp, o_hm, cA.x, cA.y, cH.x, cH.y);
+                a0 = r.x;
+                a1 = r.y;
+                PA_SLICE_FEED(hpp, hmp, o_hp, o_hm, r.z, r.w);
 #pragma unroll
                 for (int i = 0; i + 1 < R; i += 2) {
                     uint32_t hpo, hmo;
@@ -341,12 +371,16 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
                 }
                 o_hp = hpp;
                 o_hm = hmp;
+                // the entry of the next step's column, c + 1 = cnt: issued here, where the registers of this step's entry are free again
+                // (read at the top of the step, into registers of its own, it costs two copies a step or a loop of two steps: 1.5 % slower
+                //  with the copies, DESIGN §8 -- the SIMD's other wavefront covers the latency here)
+                r = *(const uint4*)((const char*)ring + ((uint32_t)cnt16 & kRingMask));
                 {  // lane 63's (hp, hm) of column c: 8 bytes, write-through; every other offset is out of range (see the rules above)
                     const pa_slice_u32x2 d = {hpp, hmp};
                     __builtin_amdgcn_raw_buffer_store_b64(d, hrs, off, 0, 16);  // aux 16 = sc1
                 }
                 off += 8u;
-                if (cnt == ev_col) {  // some pairs' a ends here: keep their bits of this lane's rows (the last event is the last column)
+                if (cnt16 == ev_col16) {  // some pairs' a ends here: keep their bits of this lane's rows (the last event is the last column)
                     const uint32_t mask = ev[ev_i].mask;
                     // V is zeroed before every pass; a pair is captured once, so OR-ing its bit in is exact.  One row at a time (the
                     // compiler would otherwise hold 2 R masked values at once: this path is rare, registers are not)
@@ -357,10 +391,10 @@ __global__ __launch_bounds__(64, 2) void slice_kernel(const SliceJob* __restrict
                         asm volatile("" ::: "memory");
                     }
                     ++ev_i;
-                    ev_col = ev_i < grp.ev_count ? ev[ev_i].col : kNoEvent;
+                    ev_col16 = ev_i < grp.ev_count ? ev[ev_i].col * 16 : kNoEvent;
                     __builtin_amdgcn_s_waitcnt(0);  // (otherwise the compiler waits for this load at the test above, in EVERY step -- behind the store)
                 }
-                ++cnt;
+                cnt16 += 16;
             }
         }
         if (dbg && lane == 0) {

@@ -45,7 +45,7 @@ struct Info {
     double boundary_bytes;        // of those, the boundary rows (reset in every pass, by the strips that consume them)
 };
 Info info(const Plan* p);
-constexpr int kStepOverheadInstr = 11;  // VALU instructions of a strip step outside the rows (ISA count, tests/test_slice_step_isa.py: 8 DPP, the store offset, the column counter and its compare)
+constexpr int kStepOverheadInstr = 6;  // VALU instructions of a strip step outside the rows (ISA count, tests/test_slice_step_isa.py, test_slice_lds_isa.py: 2 DPP, the store offset, the column counter, its compare and its ring mask)
 
 }  // namespace slice
 }  // namespace pa

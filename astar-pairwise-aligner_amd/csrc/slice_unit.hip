@@ -30,12 +30,17 @@ struct Plan {
 
 static int strips_for(size_t m, int R) { return (int)((m + (size_t)64 * R - 1) / ((size_t)64 * R)); }
 
-// ns per row step (7 instructions) per wavefront at two wavefronts per SIMD, and per step outside the rows (11 instructions).  The row step:
+// ns per row step (7 instructions) per wavefront at two wavefronts per SIMD, and per step outside the rows (6 instructions).  The row step:
 // the bench batch's 8192 jobs of 100 063 steps took their wave slots 4 x 86.5 ms with the predicated step of round 7 (346 ms a launch:
 // profiles/r07_runs/row_ab.log), 864 ns a step = 50 x 16.2 + 53.7 (24 instructions outside the rows, priced at 3.31 row steps).  The step
 // outside the rows now: the same batch, alternated three times with that build on one box (profiles/r08_runs/step_ab.log), 353.8-354.2
 // against 342.2-342.6 ms a launch = 884.3 against 855.5 ns a step; on that box a row step is 884.3 / 53.31 = 16.59 ns, so the 28.8 ns
-// that went leave 55.0 - 28.8 = 26.2 ns = 1.58 row steps = 25.6 ns at 16.2 ns a row step.
+// that went leave 55.0 - 28.8 = 26.2 ns = 1.58 row steps = 25.6 ns at 16.2 ns a row step.  Round 16 (the column ring in LDS: 6 instructions
+// outside the rows, 2 of them DPP, where there were 11 with 8 DPP): the bench batch at R = 49, alternated three times with the parent's
+// build on one box (profiles/r16_runs/lds_ab.log), 309.60-309.84 against 304.16-304.51 ms a launch = 773.9 against 760.7 ns a step; on that
+// box a row step is 773.9 / 50.58 = 15.30 ns, so the 13.2 ns that went are 0.86 of the 1.58 row steps: 0.72 are left = 11.6 ns at 16.2 ns
+// a row step.  (Priced by instruction class -- tools/bank_probe: 1.72 ns a DPP, 1.02 a VOP2 -- 25.6 x 7.52 / 16.82 = 11.4 ns.  A first
+// look on another box, two alternations, found 23.8 ns gone: lds_ab_first_box.log.)
 // kChainPenalty: what a strip loses per strip of its group's chain (asleep behind the strip above, filling and draining the chain) -- 36 strips
 // of 44 rows against 32 of 50 for 16 384 x 100 kbp: 789 against 760 ms where the plain count of instructions calls it a tie.  A chain is
 // the strips of a group that are in flight together (chain_in_flight below), 8 and not 32 for the bench batch since the job list is
@@ -43,7 +48,7 @@ static int strips_for(size_t m, int R) { return (int)((m + (size_t)64 * R - 1) /
 // chains of 32 (chain_gate.log) give 0.0016, the time asleep 4.42 % / 31 = 0.0014 and 0.46 % / 7 = 0.0007: the constant stays.  It is the
 // same factor for every R of a batch now unless a group has fewer strips than fit in flight, so it ranks the sliced kernel against the
 // other batch shapes more than it chooses R.
-static constexpr double kNsPerRowStep = 16.2, kNsStepOverhead = 25.6, kChainPenalty = 0.0015;
+static constexpr double kNsPerRowStep = 16.2, kNsStepOverhead = 11.6, kChainPenalty = 0.0015;
 
 // The ticket order (slice_job_order.hpp): PA_SLICE_CHAIN=<C> asks for bands of C strips of every group, 0 = one band, group after group.
 // Unset: bands of ONE strip -- all groups' strip 0, then all groups' strip 1, .. -- which for any C is also "the bands of C, strip-major
@@ -69,8 +74,8 @@ int choose_rows_per_lane(const size_t* a_len, const size_t* b_len, size_t pairs,
     for (size_t i = 0; i < pairs; ++i) {
         live += a_len[i] > 0 && b_len[i] > 0;
         // (the boundary rows are addressed through a buffer descriptor of n * 8 bytes, the columns through 32-bit counters: pairs beyond
-        //  2^27 columns stay with the strip kernels)
-        if (a_len[i] >= (size_t(1) << 27) || b_len[i] >= (size_t(1) << 27)) return 0;
+        //  2^27 columns stay with the strip kernels; the column counter runs in units of 16 up to 16 (n + 63), below 2^31)
+        if (a_len[i] >= (size_t(1) << 27) - 64 || b_len[i] >= (size_t(1) << 27)) return 0;
     }
     const bool forced = getenv("PA_SLICE") && atoi(getenv("PA_SLICE")) > 0;
     if ((live + 31) / 32 > 65535) return 0;  // (the groups are gridDim.y of the transposes)
