@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine_batch_create", "pa_affine_batch_run", "pa_affine_batch_align", "pa_affine_batch_info", "pa_affine_batch_destroy",
     "pa_affine_batch_align_tiled", "pa_affine_batch_tiled_info", "pa_affine_batch_set_chain", "pa_affine_batch_chain_info",
     "pa_affine_batch_set_free_ends", "pa_affine_batch_ends", "pa_affine_batch_last_row",
+    "pa_affine_batch_run_dt", "pa_affine_batch_align_dt", "pa_affine_batch_dt_info",
 ]
 
 _lib = None
@@ -112,6 +113,11 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine_batch_set_free_ends.argtypes = [vp, C.c_int, C.c_int]
         L.pa_affine_batch_ends.argtypes = [vp, vp, vp]
         L.pa_affine_batch_last_row.argtypes = [vp, vp, vp]
+    if hasattr(L, "pa_affine_batch_run_dt"):
+        L.pa_affine_batch_run_dt.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_float)]
+        L.pa_affine_batch_align_dt.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.pa_affine_batch_dt_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 6
+        L.pa_affine_batch_dt_info.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -689,6 +695,48 @@ class AffineBatch:
         load().pa_affine_batch_tiled_info(self._h, *[C.byref(v) for v in vals])
         return {k: int(v.value) for k, v in zip(("chunks", "rounds", "tile_jobs", "refill_cells", "chunk_bytes_max"), vals)}
 
+    @staticmethod
+    def _s_max(s_max) -> int:
+        if not isinstance(s_max, (int, np.integer)) or isinstance(s_max, bool) or not 0 <= s_max < 1 << 30:
+            raise ValueError(f"s_max must be an integer in [0, 2^30), got {s_max!r}")
+        return int(s_max)
+
+    def run_dt(self, s_max: int) -> np.ndarray:
+        """Costs only, by diagonal transition (WFA) bounded by s_max: int32[npairs], the cost of run() in global mode where it is
+        <= s_max and -1 ("not found") where it is not.  No retry inside: the caller decides what to do with a -1.  The time is kept in
+        `last_kernel_ms`, the counters in dt_info().  ValueError in ends-free mode."""
+        costs = np.zeros(max(self.npairs, 1), np.int32)
+        ms = C.c_float(0)
+        self._check(load().pa_affine_batch_run_dt(self._h, self._s_max(s_max), _p(costs), C.byref(ms)), "pa_affine_batch_run_dt")
+        self.last_kernel_ms = float(ms.value)
+        return costs[: self.npairs]
+
+    def align_dt(self, s_max: int) -> list[tuple[int, str]]:
+        """[(cost, CIGAR)] of every pair by diagonal transition bounded by s_max (trace batches only); (-1, "") where the cost exceeds
+        s_max.  Same cost as align(); where several optimal paths exist the CIGAR may be another one of them (DEVIATIONS.md).  The
+        times are kept in `last_forward_ms` and `last_trace_ms`."""
+        s_max = self._s_max(s_max)
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        cig = (C.c_void_p * max(n, 1))()
+        f, t = C.c_float(0), C.c_float(0)
+        rc = L.pa_affine_batch_align_dt(self._h, s_max, _p(costs), cig, C.byref(f), C.byref(t))
+        try:
+            self._check(rc, "pa_affine_batch_align_dt")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
+        return [(int(costs[p]), cigars[p] if costs[p] >= 0 else "") for p in range(n)]
+
+    def dt_info(self) -> dict:
+        """The last run_dt() / align_dt(): pairs found and not found, chunks, front cells computed (layers x live diagonals x cost
+        steps), bytes compared while extending, device bytes of the largest chunk."""
+        vals = [C.c_double(0) for _ in range(6)]
+        load().pa_affine_batch_dt_info(self._h, *[C.byref(v) for v in vals])
+        return {k: int(v.value) for k, v in zip(("found", "not_found", "chunks", "front_cells", "extend_chars", "bytes_max"), vals)}
+
     def info(self) -> dict:
         vals = [C.c_double(0) for _ in range(5)]
         load().pa_affine_batch_info(self._h, *[C.byref(v) for v in vals])
@@ -707,14 +755,19 @@ class AffineBatch:
             pass
 
 
-def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False) -> list[tuple[int, str]]:
+def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False, s_max: int | None = None) -> list[tuple[int, str]]:
     """[(cost, CIGAR)] of every pair under the gap-affine cost model `cm` (one traced AffineBatch); tiled=True takes the
     bounded-memory route (AffineBatch.align_tiled), for pairs whose whole code matrix would not fit.  chain=True (with tiled=True only:
-    the untiled route has no chained form) chains the strips of the pairs with |b| > 1024 in the checkpoint pass."""
+    the untiled route has no chained form) chains the strips of the pairs with |b| > 1024 in the checkpoint pass.  s_max=K takes the
+    diagonal-transition route instead (AffineBatch.align_dt(K), without tiled or chain): (-1, "") for a pair whose cost exceeds K."""
+    if s_max is not None and (tiled or chain):
+        raise ValueError("s_max selects the diagonal-transition route, which has no tiled or chained form")
     if chain and not tiled:
         raise ValueError("chain=True needs tiled=True: the untiled traced route has no chained form")
     b = AffineBatch(pairs, cm, trace=True, chain=chain)
     try:
+        if s_max is not None:
+            return b.align_dt(s_max)
         return b.align_tiled() if tiled else b.align()
     finally:
         b.close()

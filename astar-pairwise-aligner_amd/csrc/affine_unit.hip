@@ -11,10 +11,12 @@
 // chained through their boundary rows (planned by affine_chain_plan.hpp).  set_free_ends() makes the ends of a free in all of these
 // routes: the launches then pick the kernels' ENDS instantiations, which leave every pair's end in d_end; the walks start there, and
 // pa_affine_batch_ends reports where they started and stopped.  last_row() is a cost-only pass of its own that also stores row |b|.
+// The diagonal-transition route (run_dt, align_dt) is a unit of its own, affine_dt_unit.hip, which sees a batch through dt_view().
 #include "pa_hip_internal.hpp"
 #include "engine.hpp"
 #include "affine_kernel.hpp"
 #include "affine_chain_plan.hpp"
+#include "affine_dt_view.hpp"
 #include "../../include/pa_affine_hip.h"
 
 #include <algorithm>
@@ -79,7 +81,17 @@ struct pa_affine_batch {
         bool valid = false;               // a run, align or align_tiled has succeeded under the current setting
         std::vector<int64_t> start, end;  // of that call
     } ends;
+    DtState* dt = nullptr;  // the diagonal-transition route's own state (affine_dt_unit.hip)
 };
+
+// What the diagonal-transition route (run_dt, align_dt: affine_dt_unit.hip) reads of a batch.
+DtView pa::affine::dt_view(pa_affine_batch* ab) {
+    static_assert(kDtAbsent == kInf, "an absent edge");
+    const Costs& C = ab->C;
+    const size_t seq_bytes = ab->np ? ab->boff[ab->np - 1] + ab->m[ab->np - 1] : 0;  // (b of the last pair ends d_seq)
+    return DtView{ab->np, ab->trace, DtCosts{C.sub, C.ins, C.del, C.io, C.ie, C.dopen, C.de, C.ends}, ab->n.data(), ab->m.data(),
+                  ab->aoff.data(), ab->boff.data(), ab->d_seq.as<uint8_t>(), seq_bytes, &ab->dt};
+}
 
 namespace {
 
@@ -856,5 +868,6 @@ extern "C" void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, d
 extern "C" void pa_affine_batch_destroy(pa_affine_batch* ab) {
     if (!ab) return;
     (void)hipDeviceSynchronize();
+    dt_release(ab->dt);
     delete ab;
 }

@@ -93,6 +93,31 @@ int pa_affine_batch_ends(const pa_affine_batch* ab, int64_t* start_out, int64_t*
  * own over the pairs asked for, in chunks whose rows (4 bytes per column, device memory taken only here) stay within
  * PA_AFFINE_TRACE_BUDGET_MB or a quarter of the free device memory; a pair whose row alone exceeds it is PA_E_ARG naming the pair. */
 int pa_affine_batch_last_row(pa_affine_batch* ab, int32_t* out, const uint64_t* offsets);
+/* The diagonal-transition (WFA) route: the same global-mode cost as pa_affine_batch_run, found by keeping for every cost s = 0, 1, ..
+ * the furthest-reaching point of every diagonal and layer (pa-base-algos dt.rs, cost_for_bounded_dist), so the work is about (cost) x
+ * (diagonals reached) plus the bytes matched, not |a| |b|.  s_max in [0, 2^30) bounds the search: a pair whose cost exceeds it is "not
+ * found", cost_out[p] = -1 (the reference's None).  There is no doubling, retry or fallback inside the call.  Every model
+ * pa_affine_batch_create accepts is accepted (the largest single edge, at most 1000, sets the ring of fronts: largest edge + 1).
+ * Ends-free mode has no DT route: with either switch on, PA_E_ARG.  The chain setting is ignored.  A pair takes a wavefront and, per
+ * layer (3, or 1 for a model without affine layers), (largest edge + 2) * (D + 2) * 4 bytes of device memory, where s' = min(s_max, the
+ * cost of deleting a and inserting b) and D the diagonals cost s' reaches, clipped to [-|b|, |a|]; the pairs run in chunks within
+ * PA_AFFINE_TRACE_BUDGET_MB (or a quarter of the free device memory), and a pair that alone exceeds it is PA_E_ARG naming the pair.
+ * kernel_ms (optional): HIP-event time of clearing the fronts and the kernel, summed over the chunks.  A NULL batch or a negative
+ * s_max is PA_E_ARG.  Leaves every other route's results and settings as they were. */
+int pa_affine_batch_run_dt(pa_affine_batch* ab, int32_t s_max, int32_t* cost_out, float* kernel_ms);
+/* Costs and CIGARs by diagonal transition (trace batches only, else PA_E_ARG).  Keeps every front of a pair, (s' + 2) * (D + 2) * 4
+ * bytes per layer plus |a| + |b| ops, chunked under the same budget, and walks back from (cost, main, |a|, |b|) to (0, main, 0, 0) over
+ * the stored furthest-reaching values.  Main layer: the point before extension is the maximum over the parents in the order
+ * substitution, linear insert, linear delete, close of the insert layer, close of the delete layer, each read from the front
+ * `s - edge cost`; the matches down to it are emitted, and the walk moves to the first parent in that order that reaches the maximum.
+ * Affine layers: open before extend.  At s = 0 the rest is matches.  The CIGAR has the cost of pa_affine_batch_align's and is a valid
+ * path, but where several optimal paths exist it may be another one (DEVIATIONS.md).  A pair above s_max gets cost -1 and "".
+ * cigar_out[p] is malloc'ed (pa_free_cigars); on error every cigar_out[p] is NULL. */
+int pa_affine_batch_align_dt(pa_affine_batch* ab, int32_t s_max, int32_t* cost_out, char** cigar_out, float* forward_ms, float* trace_ms);
+/* The last DT call: pairs found and not found, chunks, front cells computed (layers x live diagonals, summed over the cost steps of
+ * every pair), bytes compared while extending, and the largest chunk's device bytes.  Every pointer may be NULL. */
+void pa_affine_batch_dt_info(const pa_affine_batch* ab, double* found, double* not_found, double* chunks, double* front_cells,
+                             double* extend_chars, double* bytes_max);
 /* Plan shape of run() with chaining off (the setting does not change it): wavefronts launched, pairs packed into segments (|b| <= 1024), pairs on strips of their own, lanes carrying rows
  * of b (sum of ceil(max(|b|, 1) / 16)) over lanes launched (64 per wavefront and strip), and the chunks of the last align(). */
 void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,

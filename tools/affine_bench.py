@@ -1,7 +1,7 @@
 """Batched gap-affine alignment (pa_affine_batch_*): kernel time, GCUPS and pairs/s, costs only and traced, for three shapes under
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
-    python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends]
+    python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt]
                                  [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
@@ -16,7 +16,12 @@ repeats, their ratio and chain_info().  The shape 100k1 is one 100 kbp pair.
 --ends measures the ends-free mode (AffineBatch.set_free_ends, both ends of the text free) on two mapping shapes of its own, whatever
 --shapes says: 100 000 patterns of 150 bp in 400 bp windows, and 4096 reads of 10 kbp in 12 kbp windows (traced: --trace-pairs of them).
 Each runs cost-only, traced and tiled, global and ends-free alternating on one batch, each warmed once and then R times: the cells are
-the same, so the ratio of the fastest repeats is what the mode costs."""
+the same, so the ratio of the fastest repeats is what the mode costs.
+
+--dt measures the diagonal-transition route (AffineBatch.run_dt) against run() instead: for each shape one batch in one process, run() and
+run_dt() alternating, each warmed once and then three times; s_max is the largest cost run() returned for the batch, so every pair is
+found.  run() is chained for the 100 kbp shapes (its best route there).  It prints both routes' fastest repeats, their ratio (above 1:
+DT is faster) and dt_info().  A shape takes a divergence in per cent after an @: 10k@1, 10k@15, reads@15 (default 5)."""
 from __future__ import annotations
 
 import argparse
@@ -116,24 +121,27 @@ def mutate(rng, s: bytes, rate: float) -> bytes:
 
 
 def shape(name, rng):
+    name, _, pct = name.partition("@")
+    rate = float(pct) / 100 if pct else 0.05
+    pct = pct or "5"
     if name == "reads":
         pairs = []
         for _ in range(100_000):
             w = int(rng.integers(150, 201))
             y = rand_seq(rng, w)
-            pairs.append((mutate(rng, y[:150], 0.05), y))
-        return "100000 x 150 bp reads vs 150-200 bp windows", pairs
+            pairs.append((mutate(rng, y[:150], rate), y))
+        return "100000 x 150 bp reads vs 150-200 bp windows" + ("" if pct == "5" else f" at {pct} %"), pairs
     if name == "10k":
         pairs = []
         for _ in range(4096):
             y = rand_seq(rng, 10_000)
-            pairs.append((mutate(rng, y, 0.05), y))
-        return "4096 x 10 kbp at 5 %", pairs
+            pairs.append((mutate(rng, y, rate), y))
+        return f"4096 x 10 kbp at {pct} %", pairs
     pairs = []
     for _ in range(1 if name == "100k1" else 16):
         y = rand_seq(rng, 100_000)
-        pairs.append((mutate(rng, y, 0.05), y))
-    return f"{len(pairs)} x 100 kbp at 5 %", pairs
+        pairs.append((mutate(rng, y, rate), y))
+    return f"{len(pairs)} x 100 kbp at {pct} %", pairs
 
 
 def chain_legs(title, pairs, cm, mname, tile_cols, reps):
@@ -167,6 +175,33 @@ def chain_legs(title, pairs, cm, mname, tile_cols, reps):
           f"  (fills {r1:.2f} ms, walks {w1:.2f} ms; repeats {' '.join(f'{sum(x):.2f}' for x in tiled[False])} |"
           f" {' '.join(f'{sum(x):.2f}' for x in tiled[True])})", flush=True)
     print(f"{'':44s} {mname:14s} chain_info: {ci}", flush=True)
+
+
+def dt_legs(title, pairs, cm, mname, chain):
+    """run() and run_dt(largest cost), alternating on one batch."""
+    cells = float(sum(len(x) * len(y) for x, y in pairs))
+    b = AffineBatch(pairs, cm, chain=chain)
+    want = b.run()
+    s_max = int(want.max())
+    nw, dt = [], []
+    for rep in range(4):  # the first round warms both routes
+        c = b.run()
+        k = b.last_kernel_ms
+        d = b.run_dt(s_max)
+        if c.tolist() != want.tolist() or d.tolist() != want.tolist():
+            raise SystemExit(f"{title} {mname}: run() and run_dt() disagree")
+        if rep:
+            nw.append(k)
+            dt.append(b.last_kernel_ms)
+    di = b.dt_info()
+    b.close()
+    k0, k1 = min(nw), min(dt)
+    print(f"{title:44s} {mname:14s} run(){' chained' if chain else ''}: {k0:10.2f} ms {cells / k0 / 1e6:8.1f} GCUPS | run_dt(s_max={s_max}): {k1:10.2f} ms"
+          f" {len(pairs) / k1 * 1e3:12.0f} pairs/s | run / run_dt {k0 / k1:7.3f}  (repeats {' '.join(f'{x:.2f}' for x in nw)} |"
+          f" {' '.join(f'{x:.2f}' for x in dt)})", flush=True)
+    print(f"{'':44s} {mname:14s} dt_info: front_cells {di['front_cells']:.4g} ({di['front_cells'] / cells:.4f} of |a||b|), extend_chars"
+          f" {di['extend_chars']:.4g}, chunks {di['chunks']}, {di['bytes_max'] / 2**20:.1f} MiB, found {di['found']}, mean cost {float(want.mean()):.1f}",
+          flush=True)
 
 
 def ends_shape(name, rng):
@@ -253,6 +288,7 @@ def main():
     ap.add_argument("--trace-pairs", type=int, default=512, help="traced runs of the 10 kbp shape use this many of its pairs")
     ap.add_argument("--chain", action="store_true", help="measure the chained route against the unchained one instead (see above)")
     ap.add_argument("--ends", action="store_true", help="measure the ends-free mode against the global one instead (see above)")
+    ap.add_argument("--dt", action="store_true", help="measure the diagonal-transition route against run() instead (see above)")
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -271,6 +307,9 @@ def main():
         title, pairs = shape(sname, rng)
         cells = float(sum(len(x) * len(y) for x, y in pairs))
         for mname, cm in models.items():
+            if args.dt:
+                dt_legs(title, pairs, cm, mname, sname.startswith("100k"))
+                continue
             if args.chain:
                 chain_legs(title, pairs, cm, mname, args.tile_cols, args.reps)
                 continue
