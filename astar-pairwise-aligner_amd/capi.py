@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine_batch_align_tiled", "pa_affine_batch_tiled_info", "pa_affine_batch_set_chain", "pa_affine_batch_chain_info",
     "pa_affine_batch_set_free_ends", "pa_affine_batch_ends", "pa_affine_batch_last_row",
     "pa_affine_batch_run_dt", "pa_affine_batch_align_dt", "pa_affine_batch_dt_info",
+    "pa_affine_batch_run_dt_ends", "pa_affine_batch_align_dt_ends",
 ]
 
 _lib = None
@@ -118,6 +119,9 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine_batch_align_dt.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.pa_affine_batch_dt_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 6
         L.pa_affine_batch_dt_info.restype = None
+    if hasattr(L, "pa_affine_batch_run_dt_ends"):
+        L.pa_affine_batch_run_dt_ends.argtypes = [vp, C.c_int, C.c_int, C.c_int32, vp, vp, C.POINTER(C.c_float)]
+        L.pa_affine_batch_align_dt_ends.argtypes = [vp, C.c_int, C.c_int, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -553,6 +557,13 @@ def _switch(v, name: str) -> int:
     raise ValueError(f"{name} must be a bool (or 0 / 1), got {v!r}")
 
 
+def _s_max_arg(s_max) -> int:
+    """The bound of a diagonal-transition call: an integer in [0, 2^30)."""
+    if not isinstance(s_max, (int, np.integer)) or isinstance(s_max, bool) or not 0 <= s_max < 1 << 30:
+        raise ValueError(f"s_max must be an integer in [0, 2^30), got {s_max!r}")
+    return int(s_max)
+
+
 class AffineBatch:
     """Gap-affine global alignment of many pairs on the GPU (pa_affine_batch_*): NW::new(cm, false, false).align(a, b) of pa-base-algos
     for every pair, a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align().  chain=True runs every
@@ -697,9 +708,7 @@ class AffineBatch:
 
     @staticmethod
     def _s_max(s_max) -> int:
-        if not isinstance(s_max, (int, np.integer)) or isinstance(s_max, bool) or not 0 <= s_max < 1 << 30:
-            raise ValueError(f"s_max must be an integer in [0, 2^30), got {s_max!r}")
-        return int(s_max)
+        return _s_max_arg(s_max)
 
     def run_dt(self, s_max: int) -> np.ndarray:
         """Costs only, by diagonal transition (WFA) bounded by s_max: int32[npairs], the cost of run() in global mode where it is
@@ -730,8 +739,43 @@ class AffineBatch:
         self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
         return [(int(costs[p]), cigars[p] if costs[p] >= 0 else "") for p in range(n)]
 
+    def run_dt_ends(self, s_max: int, free_start: bool = True, free_end: bool = True) -> tuple[np.ndarray, np.ndarray]:
+        """Costs and ends by ends-free diagonal transition bounded by s_max: (int32[npairs], int64[npairs]), the cost of run() and the
+        end of ends() under set_free_ends(free_start, free_end) where the cost is <= s_max, and -1, -1 where it is not.  The switches
+        belong to this call: the batch's own setting, ends() and every other route are left alone.  With both off: run_dt(), and
+        end = |a|.  The time is kept in `last_kernel_ms`, the counters in dt_info()."""
+        s_max = self._s_max(s_max)
+        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+        costs, ends = np.zeros(max(self.npairs, 1), np.int32), np.zeros(max(self.npairs, 1), np.int64)
+        ms = C.c_float(0)
+        self._check(load().pa_affine_batch_run_dt_ends(self._h, fs, fe, s_max, _p(costs), _p(ends), C.byref(ms)), "pa_affine_batch_run_dt_ends")
+        self.last_kernel_ms = float(ms.value)
+        return costs[: self.npairs], ends[: self.npairs]
+
+    def align_dt_ends(self, s_max: int, free_start: bool = True, free_end: bool = True) -> list[tuple[int, str, int, int]]:
+        """[(cost, CIGAR, start, end)] of every pair by ends-free diagonal transition bounded by s_max (trace batches only): b is placed
+        in a[start:end], which the CIGAR describes; (-1, "", -1, -1) where the cost exceeds s_max.  Cost and end are those of align()
+        under set_free_ends(free_start, free_end); start and the CIGAR may be another optimal placement (DEVIATIONS.md).  The times are
+        kept in `last_forward_ms` and `last_trace_ms`."""
+        s_max = self._s_max(s_max)
+        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        st, en = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        cig = (C.c_void_p * max(n, 1))()
+        f, t = C.c_float(0), C.c_float(0)
+        rc = L.pa_affine_batch_align_dt_ends(self._h, fs, fe, s_max, _p(costs), _p(st), _p(en), cig, C.byref(f), C.byref(t))
+        try:
+            self._check(rc, "pa_affine_batch_align_dt_ends")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
+        return [(int(costs[p]), cigars[p] if costs[p] >= 0 else "", int(st[p]), int(en[p])) for p in range(n)]
+
     def dt_info(self) -> dict:
-        """The last run_dt() / align_dt(): pairs found and not found, chunks, front cells computed (layers x live diagonals x cost
+        """The last run_dt() / align_dt() or run_dt_ends() / align_dt_ends(): pairs found and not found, chunks, front cells computed (layers x live diagonals x cost
         steps), bytes compared while extending, device bytes of the largest chunk."""
         vals = [C.c_double(0) for _ in range(6)]
         load().pa_affine_batch_dt_info(self._h, *[C.byref(v) for v in vals])
@@ -773,12 +817,24 @@ def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False
         b.close()
 
 
-def map_affine(pairs, cm: AffineCost, free_start: bool = True, free_end: bool = True, tiled: bool = False, chain: bool = False) -> list[tuple[int, str, int, int]]:
+def map_affine(pairs, cm: AffineCost, free_start: bool = True, free_end: bool = True, tiled: bool = False, chain: bool = False,
+               s_max: int | None = None) -> list[tuple[int, str, int, int]]:
     """[(cost, CIGAR, start, end)] of every pair (a the text, b the pattern) under the gap-affine cost model `cm` with the text's ends
-    free (AffineBatch.set_free_ends): b is placed in a[start:end], which the CIGAR describes.  tiled and chain as in align_affine."""
+    free (AffineBatch.set_free_ends): b is placed in a[start:end], which the CIGAR describes.  tiled and chain as in align_affine.
+    s_max=K takes the diagonal-transition route instead (AffineBatch.align_dt_ends(K, free_start, free_end), without tiled or chain):
+    (-1, "", -1, -1) for a pair whose cost exceeds K."""
     free_start, free_end = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+    if s_max is not None and (tiled or chain):
+        raise ValueError("s_max selects the diagonal-transition route, which has no tiled or chained form")
     if chain and not tiled:
         raise ValueError("chain=True needs tiled=True: the untiled traced route has no chained form")
+    if s_max is not None:
+        s_max = _s_max_arg(s_max)
+        b = AffineBatch(pairs, cm, trace=True)
+        try:
+            return b.align_dt_ends(s_max, free_start, free_end)
+        finally:
+            b.close()
     b = AffineBatch(pairs, cm, trace=True, chain=chain, free_start=free_start, free_end=free_end)
     try:
         res = b.align_tiled() if tiled else b.align()

@@ -15,6 +15,13 @@
 // launch, a column of padding stands on either side, and a front is written over its whole live range, which contains the live range
 // of the front that last used the slot.  One __syncthreads separates the steps.
 //
+// Ends-free (a the text, b the pattern, consumed whole; tests/affine_dt_ends_plain.py): the template switches FS and FE.  Under FS front
+// 0 starts every diagonal k = 0 .. |a| at (k, 0), and the live range of every cost reaches up to the job's kmax: |a|, less the diagonals
+// from which no path within s_max comes back to an end diagonal (the host's shape_of; the results are those of |a|).  Under FE the pair
+// is found at the first s at which any diagonal holds M_s[k] - k = |b|, and `end` is the lowest such diagonal's M_s[k].  With either
+// switch the kernel stores {cost, end} per pair, else the cost alone; with both off the code is the global kernel's, instruction for
+// instruction.
+//
 // Fronts: slot-major int32, [slot][layer][W], W = diagonals + 2.  The cost-only kernel keeps a ring of `max edge + 1` slots, the traced
 // one every front 0 .. s_max; slot `nslots` is the kNeg row.  Models without affine layers (AFF = false) keep the main layer only.
 #pragma once
@@ -32,6 +39,7 @@ constexpr int32_t kNeg = (int32_t)0xC0C0C0C0;  // the fronts are cleared with me
 constexpr int kNegByte = 0xC0;
 constexpr int kWideBlock = 256;  // threads of a block where the fronts are wide: four wavefronts share a pair
 constexpr double kWideMean = 256;  // mean diagonals (at s_max) of a chunk's pairs above which its blocks are wide
+constexpr int kNoHit = 0x7FFFFFFF;  // free end: no diagonal has reached row |b| in this step
 constexpr size_t kSeqPad = 16;  // bytes after the last sequence, so that an 8-byte load at any sequence byte stays inside
 
 // One pair.  Device pointers; a and b point into the padded copy of the sequences.
@@ -91,7 +99,7 @@ __device__ __forceinline__ int match_run(const uint8_t* a, const uint8_t* b, int
     return min(len, lim);
 }
 
-template <bool AFF>
+template <bool AFF, bool FS = false, bool FE = false>
 __global__ __launch_bounds__(kWideBlock) void affine_dt_kernel(const Job* __restrict__ jobs, DtCosts C, int32_t* __restrict__ cost_out, Stat* __restrict__ stat) {
     const Job J = jobs[blockIdx.x];
     const int tid = (int)threadIdx.x, T = (int)blockDim.x;  // 64, or kWideBlock where the fronts are wide
@@ -112,9 +120,10 @@ __global__ __launch_bounds__(kWideBlock) void affine_dt_kernel(const Job* __rest
     unsigned long long cells = 0, cmp = 0;
     int found = -1, slot = 0;
     // set by the owner of the end diagonal in the step that reaches the end; two flags in turn, so that a wavefront that runs ahead
-    // into step s + 1 cannot touch the flag another one has yet to read for step s
+    // into step s + 1 cannot touch the flag another one has yet to read for step s.  Under FE every diagonal may reach row |b|: the word
+    // holds the lowest diagonal that did, kNoHit until then (a found pair leaves the loop, so the words need no reset).
     __shared__ int reached[2];
-    if (tid < 2) reached[tid] = 0;
+    if (tid < 2) reached[tid] = FE ? kNoHit : 0;
     __syncthreads();
     for (int s = 0; s <= J.s_max; ++s) {
         if (s) {
@@ -124,7 +133,7 @@ __global__ __launch_bounds__(kWideBlock) void affine_dt_kernel(const Job* __rest
         ri_aff.step(s, C.ie, C.io);
         rd_aff.step(s, C.de, C.dopen);
         const int klo = max(-(int)min(m, (uint32_t)max(ri_lin.q, ri_aff.q)), J.kmin);
-        const int khi = min((int)min(n, (uint32_t)max(rd_lin.q, rd_aff.q)), J.kmax);
+        const int khi = FS ? J.kmax : min((int)min(n, (uint32_t)max(rd_lin.q, rd_aff.q)), J.kmax);  // (FS: every diagonal up to kmax, from cost 0 on)
         const int32_t* Msub = front(s, slot, C.sub, 0);
         const int32_t* Mins = front(s, slot, C.ins, 0);
         const int32_t* Mdel = front(s, slot, C.del, 0);
@@ -143,15 +152,18 @@ __global__ __launch_bounds__(kWideBlock) void affine_dt_kernel(const Job* __rest
                 out[2 * W + k] = inside(max(Mdo[k - 1], Dde[k - 1]) + 1, k, n, m);
                 pre = max(pre, max(Iie[k], Dde[k]));
             }
-            pre = s == 0 ? 0 : pre;  // (the live range of cost 0 is diagonal 0)
+            pre = s == 0 ? (FS ? k : 0) : pre;  // (the live range of cost 0 is diagonal 0; under FS [0, kmax], diagonal k from (k, 0))
             const int lim = pre < 0 ? 0 : (int)min(n - (uint32_t)pre, m - (uint32_t)(pre - k));
             const int i = pre + match_run(J.a + pre, J.b + (pre - k), lim, cmp);
             out[k] = i;
-            if (k == kend && (uint32_t)i == n) reached[s & 1] = 1;
+            if (FE) {
+                if ((uint32_t)(i - k) == m) atomicMin(&reached[s & 1], k);  // (an absent i is far below k)
+            } else if (k == kend && (uint32_t)i == n)
+                reached[s & 1] = 1;
         }
         cells += (unsigned long long)(L * (khi - klo + 1));
         __syncthreads();  // the front is in memory before the next step reads it, and `reached` is what the owner of the end diagonal left
-        if (reached[s & 1]) {
+        if (FE ? reached[s & 1] != kNoHit : reached[s & 1]) {
             found = s;
             break;
         }
@@ -160,7 +172,11 @@ __global__ __launch_bounds__(kWideBlock) void affine_dt_kernel(const Job* __rest
     for (int off = 32; off; off >>= 1) cmp += __shfl_xor(cmp, off);
     if ((tid & 63) == 0) atomicAdd(&stat[J.out].extend_chars, cmp);  // (cleared by the host; one add per wavefront)
     if (tid == 0) {
-        cost_out[J.out] = found;
+        if (FS || FE) {  // {cost, end}: the lowest hit diagonal's i under FE, else |a|
+            cost_out[2 * (size_t)J.out] = found;
+            cost_out[2 * (size_t)J.out + 1] = found < 0 ? -1 : FE ? reached[found & 1] + (int32_t)m : (int32_t)n;
+        } else
+            cost_out[J.out] = found;
         stat[J.out].front_cells = cells;
     }
 }
@@ -168,8 +184,9 @@ __global__ __launch_bounds__(kWideBlock) void affine_dt_kernel(const Job* __rest
 // One thread per pair: from (cost, main, |a|, |b|) back to (0, main, 0, 0) over the stored fronts.  On the main layer the point before
 // extension is the maximum over the parents in the order substitution, linear insert, linear delete, close insert, close delete; the
 // matches down to it are emitted and the walk moves to the first parent that reaches it.  On an affine layer open comes before extend.
-// The ops are recorded from the end backwards.
-template <bool AFF>
+// The ops are recorded from the end backwards.  Ends-free: from (cost, main, end, |b|), and at s = 0 the rest is the i - k matches down
+// to (k, 0); the host reads start = k off the ops (end minus the bytes of a they consume).
+template <bool AFF, bool FS = false, bool FE = false>
 __global__ void affine_dt_walk_kernel(const Job* __restrict__ jobs, int njobs, DtCosts C, const int32_t* __restrict__ cost, WalkOut* __restrict__ wout) {
     const int x = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (x >= njobs) return;
@@ -188,7 +205,9 @@ __global__ void affine_dt_walk_kernel(const Job* __restrict__ jobs, int njobs, D
             nops += nops < cap;
         }
     };
-    int s = cost[J.out], layer = 0, k = (int)n - (int)m, i = (int)n;
+    constexpr bool ENDS = FS || FE;  // cost holds {cost, end} per pair
+    const int32_t cost0 = ENDS ? cost[2 * (size_t)J.out] : cost[J.out];
+    int s = cost0, layer = 0, i = ENDS ? cost[2 * (size_t)J.out + 1] : (int)n, k = i - (int)m;
     while (s >= 0 && status == 0) {
         if (k < J.kmin || k > J.kmax || i < 0) {
             status = 1;
@@ -196,7 +215,11 @@ __global__ void affine_dt_walk_kernel(const Job* __restrict__ jobs, int njobs, D
         }
         if (layer == 0) {
             if (s == 0) {
-                emit('=', (uint32_t)i);
+                if (ENDS) {  // front 0 of diagonal k starts at (k, 0): start = k, which is 0 without FS
+                    if ((FS ? k < 0 : k != 0) || i < k) status = 1;
+                    else emit('=', (uint32_t)(i - k));
+                } else
+                    emit('=', (uint32_t)i);
                 break;
             }
             const int32_t c0 = inside(at(s, C.sub, 0, k) + 1, k, n, m), c1 = inside(at(s, C.ins, 0, k + 1), k, n, m),
@@ -234,7 +257,7 @@ __global__ void affine_dt_walk_kernel(const Job* __restrict__ jobs, int njobs, D
             k -= 1, i -= 1;
         }
     }
-    if (cost[J.out] >= 0 && s < 0 && status == 0) status = 1;
+    if (cost0 >= 0 && s < 0 && status == 0) status = 1;
     wout[x].nops = (int32_t)nops;
     wout[x].status = status;
 }

@@ -98,7 +98,7 @@ int pa_affine_batch_last_row(pa_affine_batch* ab, int32_t* out, const uint64_t* 
  * (diagonals reached) plus the bytes matched, not |a| |b|.  s_max in [0, 2^30) bounds the search: a pair whose cost exceeds it is "not
  * found", cost_out[p] = -1 (the reference's None).  There is no doubling, retry or fallback inside the call.  Every model
  * pa_affine_batch_create accepts is accepted (the largest single edge, at most 1000, sets the ring of fronts: largest edge + 1).
- * Ends-free mode has no DT route: with either switch on, PA_E_ARG.  The chain setting is ignored.  A pair takes a wavefront and, per
+ * A batch whose ends-free setting is on is refused, PA_E_ARG (ends-free DT is pa_affine_batch_run_dt_ends).  The chain setting is ignored.  A pair takes a wavefront and, per
  * layer (3, or 1 for a model without affine layers), (largest edge + 2) * (D + 2) * 4 bytes of device memory, where s' = min(s_max, the
  * cost of deleting a and inserting b) and D the diagonals cost s' reaches, clipped to [-|b|, |a|]; the pairs run in chunks within
  * PA_AFFINE_TRACE_BUDGET_MB (or a quarter of the free device memory), and a pair that alone exceeds it is PA_E_ARG naming the pair.
@@ -114,7 +114,35 @@ int pa_affine_batch_run_dt(pa_affine_batch* ab, int32_t s_max, int32_t* cost_out
  * path, but where several optimal paths exist it may be another one (DEVIATIONS.md).  A pair above s_max gets cost -1 and "".
  * cigar_out[p] is malloc'ed (pa_free_cigars); on error every cigar_out[p] is NULL. */
 int pa_affine_batch_align_dt(pa_affine_batch* ab, int32_t s_max, int32_t* cost_out, char** cigar_out, float* forward_ms, float* trace_ms);
-/* The last DT call: pairs found and not found, chunks, front cells computed (layers x live diagonals, summed over the cost steps of
+/* Ends-free (semi-global) diagonal transition: the cost and `end` of pa_affine_batch_run under pa_affine_batch_set_free_ends(free_start,
+ * free_end), a the text and b the pattern, found in work proportional to cost x diagonals.  The switches are arguments of the call: the
+ * batch's own ends-free setting, what pa_affine_batch_ends reports, the chain setting and every other route's results are neither read
+ * nor changed.  The recurrence, layers, extension and ring are those of pa_affine_batch_run_dt, and three things differ:
+ *   free_start = 1: front 0 starts every diagonal k = 0 .. |a| at (k, 0), and the live diagonals of cost s are
+ *                   [-min(|b|, reach_ins(s)), |a|] (no further trimming).
+ *   free_end = 1:   the pair is found at the first s at which any diagonal holds M_s[k] - k = |b|; end_out[p] is the lowest such
+ *                   i = M_s[k] (the lowest column on ties, as in pa_affine_batch_set_free_ends).  Without it end = |a|.
+ *   bound:          with either switch on s' = min(s_max, the gap cost of inserting b), which end = 0 or start = |a| always reaches.
+ * Device memory per pair and layer: (largest edge + 2) * (D + 2) * 4 bytes, D the diagonals of [kmin, kmax] at s'.  Under free_start
+ * the diagonals above |a| - |b| + reach_ins(s') are left out (no path within s' that passes there comes back to an end diagonal, so
+ * nothing changes but the work), and kmax = min(|a|, |a| - |b| + reach_ins(s')) whatever the cost: D = kmax + min(|b|, reach_ins(s'))
+ * + 1, at most |a| + reach + 1, i.e. about 4 (|a| - |b| + 2 reach) (largest edge + 2) bytes per layer: 35 KB in all for a 150-byte
+ * pattern in a 400-byte text at s' = 120 under affine(4, 6, 2) (8 rows, 3 layers, 367 columns), against 12 KB with free_end alone, where D
+ * is as in global mode.
+ * A pair above s_max gets cost -1 and end -1.  With both switches 0 the call returns what pa_affine_batch_run_dt returns, and end = |a|.
+ * A NULL batch, a switch other than 0 and 1, or an s_max outside [0, 2^30) is PA_E_ARG.  Chunking, the order of the pairs, the wide
+ * blocks and the refusal of a pair that alone exceeds the budget are those of pa_affine_batch_run_dt. */
+int pa_affine_batch_run_dt_ends(pa_affine_batch* ab, int free_start, int free_end, int32_t s_max,
+                                int32_t* cost_out, int64_t* end_out, float* kernel_ms);
+/* Costs, placements and CIGARs by ends-free diagonal transition (trace batches only, else PA_E_ARG).  Keeps every front of a pair,
+ * (s' + 2) * (D + 2) * 4 bytes per layer plus |a| + |b| ops, and walks back from (cost, main, i = end, k = end - |b|) with the parent
+ * order and tie rule of pa_affine_batch_align_dt down to s = 0, where the rest is i - k matches and start = k (0 without free_start).
+ * The CIGAR describes a[start:end] against b.  Cost and end are those of pa_affine_batch_align in the same ends-free setting; start
+ * and the CIGAR are this walk's own and may be another optimal placement (DEVIATIONS.md).  A pair above s_max gets cost -1, start -1,
+ * end -1 and "".  cigar_out[p] is malloc'ed (pa_free_cigars); on error every cigar_out[p] is NULL. */
+int pa_affine_batch_align_dt_ends(pa_affine_batch* ab, int free_start, int free_end, int32_t s_max, int32_t* cost_out,
+                                  int64_t* start_out, int64_t* end_out, char** cigar_out, float* forward_ms, float* trace_ms);
+/* The last DT call of either kind: pairs found and not found, chunks, front cells computed (layers x live diagonals, summed over the cost steps of
  * every pair), bytes compared while extending, and the largest chunk's device bytes.  Every pointer may be NULL. */
 void pa_affine_batch_dt_info(const pa_affine_batch* ab, double* found, double* not_found, double* chunks, double* front_cells,
                              double* extend_chars, double* bytes_max);

@@ -1,7 +1,7 @@
 """Batched gap-affine alignment (pa_affine_batch_*): kernel time, GCUPS and pairs/s, costs only and traced, for three shapes under
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
-    python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt]
+    python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
                                  [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
@@ -21,7 +21,13 @@ the same, so the ratio of the fastest repeats is what the mode costs.
 --dt measures the diagonal-transition route (AffineBatch.run_dt) against run() instead: for each shape one batch in one process, run() and
 run_dt() alternating, each warmed once and then three times; s_max is the largest cost run() returned for the batch, so every pair is
 found.  run() is chained for the 100 kbp shapes (its best route there).  It prints both routes' fastest repeats, their ratio (above 1:
-DT is faster) and dt_info().  A shape takes a divergence in per cent after an @: 10k@1, 10k@15, reads@15 (default 5)."""
+DT is faster) and dt_info().  A shape takes a divergence in per cent after an @: 10k@1, 10k@15, reads@15 (default 5).
+
+--dt-ends measures the ends-free diagonal-transition route (AffineBatch.run_dt_ends) against the ends-free run() on the mapping shapes of
+--ends: map150 (100 000 x 150 bp in 400 bp windows) and map10k@1, map10k@3, map10k@5 (4096 x 10 kbp in 12 kbp windows), or those of
+them that --shapes names.  Each runs twice: both ends free on the windows, and free_end only on the windows cut to begin where the
+pattern does (extension from a seed: front 0 is one diagonal).  One batch, run() and run_dt_ends(largest cost) alternating, each
+warmed once and then three times; the costs and ends of the two routes must agree."""
 from __future__ import annotations
 
 import argparse
@@ -204,15 +210,46 @@ def dt_legs(title, pairs, cm, mname, chain):
           flush=True)
 
 
-def ends_shape(name, rng):
-    """(text, pattern) pairs: a mutated piece of the window, somewhere inside it."""
+def ends_shape(name, rng, rate=0.05, offsets=None):
+    """(text, pattern) pairs: a mutated piece of the window, somewhere inside it (`offsets`, a list, receives where)."""
     count, plen, wlen = (100_000, 150, 400) if name == "map150" else (4096, 10_000, 12_000)
     pairs = []
     for _ in range(count):
         w = rand_seq(rng, wlen)
         off = int(rng.integers(0, wlen - plen + 1))
-        pairs.append((w, mutate(rng, w[off:off + plen], 0.05)))
+        pairs.append((w, mutate(rng, w[off:off + plen], rate)))
+        if offsets is not None:
+            offsets.append(off)
     return f"{count} x {plen} bp in {wlen} bp windows", pairs
+
+
+def dt_ends_legs(title, pairs, cm, mname, fs, fe):
+    """Ends-free run() and run_dt_ends(largest cost), alternating on one batch; the cost and end of every pair must agree."""
+    cells = float(sum(len(x) * len(y) for x, y in pairs))
+    b = AffineBatch(pairs, cm, free_start=fs, free_end=fe)
+    want = b.run()
+    want_end = b.ends()[:, 1]
+    s_max = int(want.max())
+    nw, dt = [], []
+    for rep in range(4):  # the first round warms both routes
+        c = b.run()
+        k = b.last_kernel_ms
+        d, e = b.run_dt_ends(s_max, fs, fe)
+        if c.tolist() != want.tolist() or d.tolist() != want.tolist() or e.tolist() != want_end.tolist():
+            raise SystemExit(f"{title} {mname}: run() and run_dt_ends() disagree")
+        if rep:
+            nw.append(k)
+            dt.append(b.last_kernel_ms)
+    di = b.dt_info()
+    b.close()
+    k0, k1 = min(nw), min(dt)
+    mode = "both ends free" if fs else "free_end only"
+    print(f"{title:44s} {mname:14s} {mode:15s} run(): {k0:10.2f} ms {cells / k0 / 1e6:8.1f} GCUPS | run_dt_ends(s_max={s_max}): {k1:10.2f} ms"
+          f" {len(pairs) / k1 * 1e3:12.0f} pairs/s | run / run_dt_ends {k0 / k1:7.3f}  (repeats {' '.join(f'{x:.2f}' for x in nw)} |"
+          f" {' '.join(f'{x:.2f}' for x in dt)})", flush=True)
+    print(f"{'':44s} {mname:14s} {'':15s} dt_info: front_cells {di['front_cells']:.4g} ({di['front_cells'] / cells:.4f} of |a||b|), extend_chars"
+          f" {di['extend_chars']:.4g}, chunks {di['chunks']}, {di['bytes_max'] / 2**20:.1f} MiB, found {di['found']}, mean cost {float(want.mean()):.1f}",
+          flush=True)
 
 
 def ends_legs(title, pairs, tp, cm, mname, tile_cols, reps):
@@ -289,6 +326,7 @@ def main():
     ap.add_argument("--chain", action="store_true", help="measure the chained route against the unchained one instead (see above)")
     ap.add_argument("--ends", action="store_true", help="measure the ends-free mode against the global one instead (see above)")
     ap.add_argument("--dt", action="store_true", help="measure the diagonal-transition route against run() instead (see above)")
+    ap.add_argument("--dt-ends", action="store_true", help="measure the ends-free diagonal-transition route against the ends-free run() instead (see above)")
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -302,6 +340,17 @@ def main():
             title, pairs = ends_shape(sname, rng)
             for mname, cm in models.items():
                 ends_legs(title, pairs, pairs if sname == "map150" else pairs[: args.trace_pairs], cm, mname, args.tile_cols, args.reps)
+        return
+    if args.dt_ends:
+        own = [s for s in args.shapes.split(",") if s.startswith("map")] or ["map150", "map10k@1", "map10k@3", "map10k@5"]
+        for sname in own:
+            name, _, pct = sname.partition("@")
+            offs = []
+            title, pairs = ends_shape(name, rng, float(pct or 5) / 100, offs)
+            seeded = [(w[o:], y) for (w, y), o in zip(pairs, offs)]  # extension: the text begins where the pattern does
+            for mname, cm in models.items():
+                dt_ends_legs(f"{title} at {pct or 5} %", pairs, cm, mname, True, True)
+                dt_ends_legs(f"{title} at {pct or 5} %, from the seed", seeded, cm, mname, False, True)
         return
     for sname in args.shapes.split(","):
         title, pairs = shape(sname, rng)
