@@ -146,6 +146,37 @@ int pa_affine_batch_align_dt_ends(pa_affine_batch* ab, int free_start, int free_
  * every pair), bytes compared while extending, and the largest chunk's device bytes.  Every pointer may be NULL. */
 void pa_affine_batch_dt_info(const pa_affine_batch* ab, double* found, double* not_found, double* chunks, double* front_cells,
                              double* extend_chars, double* bytes_max);
+/* pa_affine_batch_align_dt_ends in device memory that grows with the square root of the cost, not with the cost (trace batches only,
+ * else PA_E_ARG): cost, start, end and CIGAR are those of pa_affine_batch_align_dt_ends(free_start, free_end, s_max), byte for byte.
+ * With E the largest edge, front s depends on fronts s - E .. s - 1 only and a step of the walk lowers s by at most E.  The costs are
+ * cut into segments of S >= E costs, segment c = [cS, cS + S - 1].  A checkpoint pass (pa_affine_batch_run_dt_ends' pass over the ring,
+ * costs and ends as there) also stores the E fronts below every segment start cS, c >= 1.  Then rounds follow, from every pair's top
+ * segment down, one fill launch and one walk launch per round over all unfinished pairs of the chunk: the fill puts the segment's E
+ * checkpoint rows at the head of the pair's segment buffer and recomputes the fronts of the segment up to the pair's cost; the walk is
+ * pa_affine_batch_align_dt_ends' walk with its state kept between rounds, until it leaves the segment or ends at s = 0.
+ *   seg:  0 selects S = max(E, ceil(sqrt((s' + 1) E))) for every pair from its own s' (pa_affine_batch_run_dt_ends' bound: min(s_max,
+ *         the gap cost that always reaches)); any other value is S for every pair and must lie in [E, 2^30), else PA_E_ARG.  Where S
+ *         exceeds max(E, s' + 1) that is used instead: one segment.
+ * Device bytes of a pair, with L = 3 layers (1 for a model without affine layers), W = D + 2 as in pa_affine_batch_run_dt_ends and
+ * nseg = s' / S + 1, all taken from the bound s' before anything runs, none shared and none resized after the checkpoint pass:
+ *   (E + 2) L W 4  the ring,  (nseg - 1) E L W 4  the checkpoint rows,  (E + S + 1) L W 4  the segment buffer,
+ *   (|a| + |b|) rounded up to 16  the ops,  and 40  the walk state and the fills' counters.
+ * The pairs run most expensive first in chunks whose sum of these stays within PA_AFFINE_TRACE_BUDGET_MB (or a quarter of the free
+ * device memory); a pair that alone exceeds it is PA_E_ARG naming the pair.  The wide-block rule of pa_affine_batch_run_dt applies
+ * per launch, to the jobs of that launch.  A pair above s_max gets cost -1, start -1, end -1 and "" and takes no part in the rounds.
+ * The batch's ends-free setting, pa_affine_batch_ends, the chain setting and every other route's results are neither read nor changed.
+ * A NULL batch, a switch other than 0 and 1, or an s_max outside [0, 2^30) is PA_E_ARG.  forward_ms, refill_ms, walk_ms (optional):
+ * HIP-event times of the checkpoint passes, the fills and the walks, summed over chunks and rounds.  Every output pointer may be NULL.
+ * cigar_out[p] is malloc'ed (pa_free_cigars); on error every cigar_out[p] is NULL.  pa_affine_batch_dt_info then reports the
+ * checkpoint pass. */
+int pa_affine_batch_align_dt_seg(pa_affine_batch* ab, int free_start, int free_end, int32_t s_max, uint32_t seg, int32_t* cost_out,
+                                 int64_t* start_out, int64_t* end_out, char** cigar_out, float* forward_ms, float* refill_ms,
+                                 float* walk_ms);
+/* The last pa_affine_batch_align_dt_seg: chunks, rounds (one fill launch and one walk launch each, summed over the chunks: per chunk
+ * the largest cost / S + 1 among its found pairs), segment jobs (the sum of cost / S + 1 over the found pairs), front cells the fills
+ * computed, and the largest chunk's device bytes by the formula above.  Every pointer may be NULL. */
+void pa_affine_batch_dt_seg_info(const pa_affine_batch* ab, double* chunks, double* rounds, double* seg_jobs, double* refill_cells,
+                                 double* bytes_max);
 /* Plan shape of run() with chaining off (the setting does not change it): wavefronts launched, pairs packed into segments (|b| <= 1024), pairs on strips of their own, lanes carrying rows
  * of b (sum of ceil(max(|b|, 1) / 16)) over lanes launched (64 per wavefront and strip), and the chunks of the last align(). */
 void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,

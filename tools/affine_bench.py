@@ -2,7 +2,7 @@
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
     python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
-                                 [--models affine,unit]
+                                 [--dt-seg] [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
 tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
@@ -27,7 +27,13 @@ DT is faster) and dt_info().  A shape takes a divergence in per cent after an @:
 --ends: map150 (100 000 x 150 bp in 400 bp windows) and map10k@1, map10k@3, map10k@5 (4096 x 10 kbp in 12 kbp windows), or those of
 them that --shapes names.  Each runs twice: both ends free on the windows, and free_end only on the windows cut to begin where the
 pattern does (extension from a seed: front 0 is one diagonal).  One batch, run() and run_dt_ends(largest cost) alternating, each
-warmed once and then three times; the costs and ends of the two routes must agree."""
+warmed once and then three times; the costs and ends of the two routes must agree.
+
+--dt-seg measures the segmented traceback of the diagonal-transition route (AffineBatch.align_dt_seg, default seg) against
+AffineBatch.align_dt_ends, globally, on the shapes of --shapes (a divergence after an @ as for --dt): one traced batch in one process,
+s_max the largest cost run_dt() finds, the two calls in turn, each warmed once and then three times, the results compared in every round.
+It prints both calls' fastest repeat with its parts, the ratio of the totals next to the ratio of the two bytes_max, rounds and chunks.
+Where align_dt_ends refuses the batch (a pair's fronts exceed the budget) its error is printed and align_dt_seg runs alone."""
 from __future__ import annotations
 
 import argparse
@@ -210,6 +216,46 @@ def dt_legs(title, pairs, cm, mname, chain):
           flush=True)
 
 
+def dt_seg_legs(title, pairs, cm, mname):
+    """align_dt_ends(largest cost) and align_dt_seg(largest cost), both switches off, in turn on one traced batch."""
+    b = AffineBatch(pairs, cm, trace=True)
+    s_max = int(b.run_dt((1 << 30) - 1).max())
+    every, seg, err = [], [], None
+    for rep in range(4):  # the first round warms both routes
+        want = None
+        if err is None:
+            try:
+                want = b.align_dt_ends(s_max, False, False)
+                if rep:
+                    every.append((b.last_forward_ms, b.last_trace_ms, b.dt_info()))
+            except ValueError as e:
+                err = str(e)
+        got = b.align_dt_seg(s_max, 0, False, False)
+        if want is not None and got != want:
+            raise SystemExit(f"{title} {mname}: align_dt_ends() and align_dt_seg() disagree")
+        if any(g[0] < 0 for g in got):
+            raise SystemExit(f"{title} {mname}: align_dt_seg() did not find a pair within the largest cost")
+        if rep:
+            seg.append((b.last_forward_ms, b.last_refill_ms, b.last_trace_ms, b.dt_seg_info()))
+    b.close()
+    f1, r1, w1, si = min(seg, key=lambda x: sum(x[:3]))
+    t1 = f1 + r1 + w1
+    line = (f"align_dt_seg: forward {f1:.2f} + refill {r1:.2f} + walk {w1:.2f} = {t1:.2f} ms, rounds {si['rounds']}, chunks {si['chunks']},"
+            f" {si['bytes_max'] / 2**20:.1f} MiB, seg jobs {si['seg_jobs']}, refill cells {si['refill_cells']:.4g}"
+            f"  (repeats {' '.join(f'{sum(x[:3]):.2f}' for x in seg)})")
+    if every:
+        f0, w0, di = min(every, key=lambda x: x[0] + x[1])
+        t0 = f0 + w0
+        print(f"{title:44s} {mname:14s} s_max {s_max}: align_dt_ends: forward {f0:.2f} + walk {w0:.2f} = {t0:.2f} ms, chunks {di['chunks']},"
+              f" {di['bytes_max'] / 2**20:.1f} MiB  (repeats {' '.join(f'{x[0] + x[1]:.2f}' for x in every)})", flush=True)
+        print(f"{'':44s} {mname:14s} {line}", flush=True)
+        print(f"{'':44s} {mname:14s} time seg / ends {t1 / t0:.3f} (forward {f1 / f0:.3f}), bytes_max ends / seg {di['bytes_max'] / si['bytes_max']:.1f}",
+              flush=True)
+    else:
+        print(f"{title:44s} {mname:14s} s_max {s_max}: align_dt_ends: {err}", flush=True)
+        print(f"{'':44s} {mname:14s} {line}", flush=True)
+
+
 def ends_shape(name, rng, rate=0.05, offsets=None):
     """(text, pattern) pairs: a mutated piece of the window, somewhere inside it (`offsets`, a list, receives where)."""
     count, plen, wlen = (100_000, 150, 400) if name == "map150" else (4096, 10_000, 12_000)
@@ -327,6 +373,7 @@ def main():
     ap.add_argument("--ends", action="store_true", help="measure the ends-free mode against the global one instead (see above)")
     ap.add_argument("--dt", action="store_true", help="measure the diagonal-transition route against run() instead (see above)")
     ap.add_argument("--dt-ends", action="store_true", help="measure the ends-free diagonal-transition route against the ends-free run() instead (see above)")
+    ap.add_argument("--dt-seg", action="store_true", help="measure the segmented DT traceback against align_dt_ends instead (see above)")
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -358,6 +405,9 @@ def main():
         for mname, cm in models.items():
             if args.dt:
                 dt_legs(title, pairs, cm, mname, sname.startswith("100k"))
+                continue
+            if args.dt_seg:
+                dt_seg_legs(title, pairs, cm, mname)
                 continue
             if args.chain:
                 chain_legs(title, pairs, cm, mname, args.tile_cols, args.reps)
