@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine_batch_run_dt", "pa_affine_batch_align_dt", "pa_affine_batch_dt_info",
     "pa_affine_batch_run_dt_ends", "pa_affine_batch_align_dt_ends",
     "pa_affine_batch_align_dt_seg", "pa_affine_batch_dt_seg_info",
+    "pa_affine4_batch_create", "pa_affine4_batch_run", "pa_affine4_batch_align", "pa_affine4_batch_info", "pa_affine4_batch_destroy",
 ]
 
 _lib = None
@@ -127,6 +128,15 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine_batch_align_dt_seg.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp, vp, vp] + [C.POINTER(C.c_float)] * 3
         L.pa_affine_batch_dt_seg_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
         L.pa_affine_batch_dt_seg_info.restype = None
+    if hasattr(L, "pa_affine4_batch_create"):
+        L.pa_affine4_batch_create.argtypes = [vp, vp, vp, vp, sz, vp, C.c_int]
+        L.pa_affine4_batch_create.restype = vp
+        L.pa_affine4_batch_run.argtypes = [vp, vp, C.POINTER(C.c_float)]
+        L.pa_affine4_batch_align.argtypes = [vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.pa_affine4_batch_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
+        L.pa_affine4_batch_info.restype = None
+        L.pa_affine4_batch_destroy.argtypes = [vp]
+        L.pa_affine4_batch_destroy.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -480,8 +490,14 @@ class _AffineCostC(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ("sub", "ins", "del_", "ins_open", "ins_extend", "del_open", "del_extend")]
 
 
+class _Affine4CostC(C.Structure):
+    _fields_ = [("sub", C.c_int32), ("ins", C.c_int32), ("del_", C.c_int32), ("open", C.c_int32 * 4), ("extend", C.c_int32 * 4)]
+
+
 AFFINE_MAX_COST = 1000
 AFFINE_ROWS_PER_LANE = 16  # rows of b per lane of the kernel (csrc/affine_kernel.hpp kRows)
+AFFINE4_ROWS_PER_LANE = 16  # ... of the double-affine kernel (csrc/affine4_kernel.hpp kRows)
+AFFINE4_LAYER_KINDS = ["ins", "del", "ins", "del"]
 
 
 class AffineCost:
@@ -523,7 +539,8 @@ class AffineCost:
 
     @classmethod
     def double_affine(cls, sub, open, extend, open2, extend2):
-        """AffineCost<4>: expressible here for completeness, refused by AffineBatch (not supported on the GPU)."""
+        """AffineCost<4>, the two-piece gap cost: a gap of length L costs min(open + L extend, open2 + L extend2).  Affine4Batch and
+        align_affine4 run it (to_c4); AffineBatch, whose kernels have two layers, refuses it."""
         return cls(sub, None, None, [("ins", open, extend), ("del", open, extend), ("ins", open2, extend2), ("del", open2, extend2)])
 
     def ins_layer(self):
@@ -535,7 +552,8 @@ class AffineCost:
     def to_c(self) -> _AffineCostC:
         """The pa_affine_cost of this model; ValueError for what the GPU kernel does not take."""
         if len(self.layers) > 2 or [k for k, _, _ in self.layers] not in ([], ["ins", "del"]):
-            raise ValueError(f"only AffineCost<0> and AffineCost<2> with layers [ins, del] are supported, got {self.layers}")
+            raise ValueError(f"only AffineCost<0> and AffineCost<2> with layers [ins, del] are supported, got {self.layers}"
+                             " (Affine4Batch takes the four layers [ins, del, ins, del])")
         vals = [self.sub, self.ins, self.del_] + [x for _, o, e in self.layers for x in (o, e)]
         for v in vals:
             if v is not None and (not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= AFFINE_MAX_COST):
@@ -547,6 +565,21 @@ class AffineCost:
             raise ValueError("the cost model has no deletion edge")
         z = lambda v: 0 if v is None else int(v)  # noqa: E731
         return _AffineCostC(z(self.sub), z(self.ins), z(self.del_), z(il and il[0]), z(il and il[1]), z(dl and dl[0]), z(dl and dl[1]))
+
+    def to_c4(self) -> _Affine4CostC:
+        """The pa_affine4_cost of this model: exactly the four layers [ins, del, ins, del]; ValueError for anything else, and for a
+        cost that is not an integer in [1, 1000]."""
+        if [k for k, _, _ in self.layers] != AFFINE4_LAYER_KINDS:
+            raise ValueError(f"only AffineCost<4> with layers [ins, del, ins, del] is supported, got {self.layers}")
+        vals = [self.sub, self.ins, self.del_] + [x for _, o, e in self.layers for x in (o, e)]
+        for v in vals:
+            if v is not None and (not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= AFFINE_MAX_COST):
+                raise ValueError(f"every cost must be an integer in [1, {AFFINE_MAX_COST}], got {v!r}")
+        if any(o is None or e is None for _, o, e in self.layers):
+            raise ValueError("every layer needs both open and extend")
+        z = lambda v: 0 if v is None else int(v)  # noqa: E731
+        return _Affine4CostC(z(self.sub), z(self.ins), z(self.del_), (C.c_int32 * 4)(*[int(o) for _, o, _ in self.layers]),
+                             (C.c_int32 * 4)(*[int(e) for _, _, e in self.layers]))
 
     def max_edge(self) -> int:
         return max([v for v in (self.sub, self.ins, self.del_) if v is not None] + [o + e for _, o, e in self.layers])
@@ -851,6 +884,102 @@ def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False
         if s_max is not None:
             return b.align_dt(s_max)
         return b.align_tiled() if tiled else b.align()
+    finally:
+        b.close()
+
+
+class Affine4Batch:
+    """Double-affine (two-piece gap cost) global alignment of many pairs on the GPU (pa_affine4_batch_*): NW::new(cm, false,
+    false).align(a, b) of pa-base-algos under an AffineCost<4> with layers [ins, del, ins, del] (AffineCost.double_affine, or four
+    layers with costs of their own), a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align().
+    Global mode only: ends-free mode, chained strips, the tiled traceback and diagonal transition are AffineBatch's, for two layers."""
+
+    def __init__(self, pairs, cm: AffineCost, trace: bool = False):
+        pairs = list(pairs)
+        if any(not isinstance(x, bytes) or not isinstance(y, bytes) for x, y in pairs):
+            raise ValueError("pairs must be (bytes, bytes)")
+        if not isinstance(cm, AffineCost):
+            raise ValueError("cm must be an AffineCost")
+        c = cm.to_c4()
+        big = cm.max_edge()
+        for p, (x, y) in enumerate(pairs):
+            if (len(x) + len(y) + 1) * big >= 1 << 30:
+                raise ValueError(f"pair {p}: (|a| + |b| + 1) * max edge cost is not below 2^30")
+        L = load()
+        self._keep = pairs
+        self.npairs = len(pairs)
+        self.trace = bool(trace)
+        n = max(len(pairs), 1)
+        ap = (C.c_char_p * n)(*[x for x, _ in pairs])
+        bp = (C.c_char_p * n)(*[y for _, y in pairs])
+        al = np.array([len(x) for x, _ in pairs] or [0], np.uint64)
+        bl = np.array([len(y) for _, y in pairs] or [0], np.uint64)
+        self._c = c
+        self._h = L.pa_affine4_batch_create(ap, _p(al), bp, _p(bl), len(pairs), C.byref(c), int(self.trace))
+        if not self._h:
+            msg = last_error()
+            if msg.startswith("pa_affine4_batch_create:"):
+                raise ValueError(msg)
+            raise PaError(msg)
+        self.last_kernel_ms = 0.0
+        self.last_forward_ms = 0.0
+        self.last_trace_ms = 0.0
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc == -4:
+            raise ValueError(last_error())
+        if rc != 0:
+            raise PaError(f"{what} rc={rc}: {last_error()}")
+
+    def run(self) -> np.ndarray:
+        """Costs only: int32[npairs]; the kernel time is kept in `last_kernel_ms`.  May be called again."""
+        costs = np.zeros(max(self.npairs, 1), np.int32)
+        ms = C.c_float(0)
+        self._check(load().pa_affine4_batch_run(self._h, _p(costs), C.byref(ms)), "pa_affine4_batch_run")
+        self.last_kernel_ms = float(ms.value)
+        return costs[: self.npairs]
+
+    def align(self) -> list[tuple[int, str]]:
+        """[(cost, CIGAR)] of every pair (trace batches only), in chunks whose traceback codes stay within PA_AFFINE_TRACE_BUDGET_MB;
+        ValueError naming a pair whose codes alone exceed it."""
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        cig = (C.c_void_p * max(n, 1))()
+        f, t = C.c_float(0), C.c_float(0)
+        rc = L.pa_affine4_batch_align(self._h, _p(costs), cig, C.byref(f), C.byref(t))
+        try:
+            self._check(rc, "pa_affine4_batch_align")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
+        return [(int(costs[p]), cigars[p]) for p in range(n)]
+
+    def info(self) -> dict:
+        """The plan of run(), as AffineBatch.info() reports it, and the chunks of the last align()."""
+        vals = [C.c_double(0) for _ in range(5)]
+        load().pa_affine4_batch_info(self._h, *[C.byref(v) for v in vals])
+        return {"waves": int(vals[0].value), "packed_pairs": int(vals[1].value), "strip_pairs": int(vals[2].value), "lane_use": vals[3].value,
+                "trace_chunks": int(vals[4].value)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().pa_affine4_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def align_affine4(pairs, cm: AffineCost, trace: bool = True):
+    """Every pair under the four-layer cost model `cm` (one Affine4Batch): [(cost, CIGAR)] with trace=True, else the int32 costs."""
+    b = Affine4Batch(pairs, cm, trace=trace)
+    try:
+        return b.align() if trace else b.run()
     finally:
         b.close()
 

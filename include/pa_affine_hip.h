@@ -26,7 +26,7 @@ extern "C" {
 /* One cost model; 0 means absent (the reference's None).  The insert layer exists when ins_open and ins_extend are both non-zero, the
  * delete layer likewise; a gap of length L in a layer costs open + L * extend.  Every cost is in [1, 1000] or 0; a layer with only one
  * of its two costs, or a model with no way to insert or no way to delete, is PA_E_ARG.  (AffineCost<4>, double_affine, has no
- * representation here.) */
+ * representation here: pa_affine4_hip.h has its own batch type, pa_affine4_batch_*, global mode with cost and CIGAR.) */
 typedef struct pa_affine_cost {
     int32_t sub, ins, del, ins_open, ins_extend, del_open, del_extend;
 } pa_affine_cost;

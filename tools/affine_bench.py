@@ -2,7 +2,7 @@
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
     python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
-                                 [--dt-seg] [--models affine,unit]
+                                 [--dt-seg] [--double] [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
 tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
@@ -33,7 +33,13 @@ warmed once and then three times; the costs and ends of the two routes must agre
 AffineBatch.align_dt_ends, globally, on the shapes of --shapes (a divergence after an @ as for --dt): one traced batch in one process,
 s_max the largest cost run_dt() finds, the two calls in turn, each warmed once and then three times, the results compared in every round.
 It prints both calls' fastest repeat with its parts, the ratio of the totals next to the ratio of the two bytes_max, rounds and chunks.
-Where align_dt_ends refuses the batch (a pair's fronts exceed the budget) its error is printed and align_dt_seg runs alone."""
+Where align_dt_ends refuses the batch (a pair's fronts exceed the budget) its error is printed and align_dt_seg runs alone.
+
+--double measures the double-affine batch (Affine4Batch under double_affine(4, 6, 2, 24, 1)) against AffineBatch under affine(4, 6, 2),
+whatever --shapes says: 100 000 x 150 bp and 4096 x 10 kbp at 5 %, a quarter of the pairs with one more indel of 20 to 200 bytes so that
+layers 2 and 3 are used.  Both batches hold the same pairs; run() alternates between them, each warmed once and then three times, and
+the line shows the fastest repeats, their ratio (double over affine) and how many pairs differ in cost between the two models.  align()
+does the same on --trace-pairs of the 10 kbp pairs."""
 from __future__ import annotations
 
 import argparse
@@ -49,7 +55,7 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import astar_pairwise_aligner_amd as pa  # noqa: E402
-from astar_pairwise_aligner_amd import AffineBatch, AffineCost  # noqa: E402
+from astar_pairwise_aligner_amd import Affine4Batch, AffineBatch, AffineCost  # noqa: E402
 
 GOTOH_C = r"""
 #include <stdint.h>
@@ -154,6 +160,68 @@ def shape(name, rng):
         y = rand_seq(rng, 100_000)
         pairs.append((mutate(rng, y, rate), y))
     return f"{len(pairs)} x 100 kbp at {pct} %", pairs
+
+
+def long_indels(rng, pairs, share=0.25):
+    """An indel of 20 to 200 bytes in a share of the pairs: bytes put into a, or taken out of it, at a random place."""
+    out = []
+    for x, y in pairs:
+        if rng.random() < share:
+            L = int(rng.integers(20, 201))
+            if rng.random() < 0.5 or len(x) < L + 20:
+                at = int(rng.integers(0, len(x) + 1))
+                x = x[:at] + rand_seq(rng, L) + x[at:]
+            else:
+                at = int(rng.integers(0, len(x) - L + 1))
+                x = x[:at] + x[at + L:]
+        out.append((x, y))
+    return out
+
+
+def double_legs(title, pairs, tp):
+    """Affine4Batch under double_affine(4, 6, 2, 24, 1) against AffineBatch under affine(4, 6, 2) on the same pairs, alternating, each
+    warmed once and then three times: run() on all pairs, align() on the pairs tp."""
+    cm2, cm4 = AffineCost.affine(4, 6, 2), AffineCost.double_affine(4, 6, 2, 24, 1)
+    cells = float(sum(len(x) * len(y) for x, y in pairs))
+    b2, b4 = AffineBatch(pairs, cm2), Affine4Batch(pairs, cm4)
+    t2, t4 = [], []
+    for rep in range(4):  # the first round warms both
+        c2 = b2.run()
+        k2 = b2.last_kernel_ms
+        c4 = b4.run()
+        if rep:
+            t2.append(k2)
+            t4.append(b4.last_kernel_ms)
+    info = b4.info()
+    b2.close()
+    b4.close()
+    if (c4 > c2).any():
+        raise SystemExit(f"{title}: a double-affine cost above the two-layer cost")
+    k2, k4 = min(t2), min(t4)
+    print(f"{title:52s} run():   affine(4,6,2) {k2:10.2f} ms {cells / k2 / 1e6:8.1f} GCUPS | double_affine(4,6,2,24,1) {k4:10.2f} ms"
+          f" {cells / k4 / 1e6:8.1f} GCUPS | ratio {k4 / k2:6.3f}  (repeats {' '.join(f'{x:.2f}' for x in t2)} | {' '.join(f'{x:.2f}' for x in t4)})", flush=True)
+    print(f"{'':52s} {int((c4 != c2).sum())} of {len(pairs)} pairs differ in cost between the two models (mean cost {float(c2.mean()):.1f} and"
+          f" {float(c4.mean()):.1f}); plan {info}", flush=True)
+    if tp is None:
+        return
+    cells = float(sum(len(x) * len(y) for x, y in tp))
+    b2, b4 = AffineBatch(tp, cm2, trace=True), Affine4Batch(tp, cm4, trace=True)
+    t2, t4 = [], []
+    for rep in range(4):
+        r2 = b2.align()
+        f2 = (b2.last_forward_ms, b2.last_trace_ms)
+        r4 = b4.align()
+        if rep:
+            t2.append(f2)
+            t4.append((b4.last_forward_ms, b4.last_trace_ms))
+    chunks = (b2.info()["trace_chunks"], b4.info()["trace_chunks"])
+    b2.close()
+    b4.close()
+    (f2, w2), (f4, w4) = min(t2, key=sum), min(t4, key=sum)
+    differ = sum(x[0] != y[0] for x, y in zip(r2, r4))
+    print(f"{'':52s} align() of {len(tp)} pairs: affine forward {f2:9.2f} ms + walks {w2:7.2f} ms | double_affine forward {f4:9.2f} ms + walks"
+          f" {w4:7.2f} ms | ratio forward {f4 / f2:6.3f}, all {(f4 + w4) / (f2 + w2):6.3f}  ({cells / (f4 + w4) / 1e6:.1f} GCUPS traced; chunks {chunks};"
+          f" {differ} pairs differ in cost; repeats {' '.join(f'{sum(x):.2f}' for x in t2)} | {' '.join(f'{sum(x):.2f}' for x in t4)})", flush=True)
 
 
 def chain_legs(title, pairs, cm, mname, tile_cols, reps):
@@ -374,6 +442,7 @@ def main():
     ap.add_argument("--dt", action="store_true", help="measure the diagonal-transition route against run() instead (see above)")
     ap.add_argument("--dt-ends", action="store_true", help="measure the ends-free diagonal-transition route against the ends-free run() instead (see above)")
     ap.add_argument("--dt-seg", action="store_true", help="measure the segmented DT traceback against align_dt_ends instead (see above)")
+    ap.add_argument("--double", action="store_true", help="measure Affine4Batch under double_affine against AffineBatch under affine instead (see above)")
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -382,6 +451,12 @@ def main():
     rng = np.random.default_rng(1)
     models = {"affine(4,6,2)": AffineCost.affine(4, 6, 2), "unit()": AffineCost.unit()}
     models = {k: v for k, v in models.items() if k.split("(")[0] in args.models.split(",")}
+    if args.double:
+        for sname in ("reads", "10k"):
+            title, pairs = shape(sname, rng)
+            pairs = long_indels(rng, pairs)
+            double_legs(title + ", indels of 20-200 bp in a quarter", pairs, None if sname == "reads" else pairs[: args.trace_pairs])
+        return
     if args.ends:
         for sname in ("map150", "map10k"):
             title, pairs = ends_shape(sname, rng)
