@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine_batch_run_dt_ends", "pa_affine_batch_align_dt_ends",
     "pa_affine_batch_align_dt_seg", "pa_affine_batch_dt_seg_info",
     "pa_affine4_batch_create", "pa_affine4_batch_run", "pa_affine4_batch_align", "pa_affine4_batch_info", "pa_affine4_batch_destroy",
+    "pa_affine4_batch_align_tiled", "pa_affine4_batch_tiled_info",
 ]
 
 _lib = None
@@ -137,6 +138,10 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine4_batch_info.restype = None
         L.pa_affine4_batch_destroy.argtypes = [vp]
         L.pa_affine4_batch_destroy.restype = None
+    if hasattr(L, "pa_affine4_batch_align_tiled"):
+        L.pa_affine4_batch_align_tiled.argtypes = [vp, C.c_uint32, vp, vp] + [C.POINTER(C.c_float)] * 3
+        L.pa_affine4_batch_tiled_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
+        L.pa_affine4_batch_tiled_info.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -891,8 +896,9 @@ def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False
 class Affine4Batch:
     """Double-affine (two-piece gap cost) global alignment of many pairs on the GPU (pa_affine4_batch_*): NW::new(cm, false,
     false).align(a, b) of pa-base-algos under an AffineCost<4> with layers [ins, del, ins, del] (AffineCost.double_affine, or four
-    layers with costs of their own), a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align().
-    Global mode only: ends-free mode, chained strips, the tiled traceback and diagonal transition are AffineBatch's, for two layers."""
+    layers with costs of their own), a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align() and
+    align_tiled(), the same CIGARs in bounded device memory (include/pa_affine4_tiled_hip.h).  Global mode only: ends-free mode,
+    chained strips and diagonal transition are AffineBatch's, for two layers."""
 
     def __init__(self, pairs, cm: AffineCost, trace: bool = False):
         pairs = list(pairs)
@@ -924,6 +930,8 @@ class Affine4Batch:
         self.last_kernel_ms = 0.0
         self.last_forward_ms = 0.0
         self.last_trace_ms = 0.0
+        self.last_refill_ms = 0.0
+        self.last_walk_ms = 0.0
 
     def _check(self, rc: int, what: str) -> None:
         if rc == -4:
@@ -956,6 +964,32 @@ class Affine4Batch:
         self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
         return [(int(costs[p]), cigars[p]) for p in range(n)]
 
+    def align_tiled(self, tile_cols: int = 0) -> list[tuple[int, str]]:
+        """align(), byte for byte, in bounded device memory: checkpoints from a cost-only pass, then only the tiles the path crosses
+        are filled with codes and walked.  tile_cols: columns of a tile, 0 for the default of 1024, else in [64, 2^20].  The times are
+        kept in `last_forward_ms` (checkpoint pass), `last_refill_ms` (tile fills) and `last_walk_ms` (walks)."""
+        if not isinstance(tile_cols, (int, np.integer)) or isinstance(tile_cols, bool) or not 0 <= tile_cols < 1 << 32:
+            raise ValueError(f"tile_cols must be 0 or in [64, 2^20], got {tile_cols!r}")
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        cig = (C.c_void_p * max(n, 1))()
+        f, r, t = C.c_float(0), C.c_float(0), C.c_float(0)
+        rc = L.pa_affine4_batch_align_tiled(self._h, int(tile_cols), _p(costs), cig, C.byref(f), C.byref(r), C.byref(t))
+        try:
+            self._check(rc, "pa_affine4_batch_align_tiled")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_refill_ms, self.last_walk_ms = float(f.value), float(r.value), float(t.value)
+        return [(int(costs[p]), cigars[p]) for p in range(n)]
+
+    def tiled_info(self) -> dict:
+        """Shape of the last align_tiled(): chunks, rounds, tile jobs, cells the fills computed, bytes of the largest chunk."""
+        vals = [C.c_double(0) for _ in range(5)]
+        load().pa_affine4_batch_tiled_info(self._h, *[C.byref(v) for v in vals])
+        return {k: int(v.value) for k, v in zip(("chunks", "rounds", "tile_jobs", "refill_cells", "chunk_bytes_max"), vals)}
+
     def info(self) -> dict:
         """The plan of run(), as AffineBatch.info() reports it, and the chunks of the last align()."""
         vals = [C.c_double(0) for _ in range(5)]
@@ -975,11 +1009,16 @@ class Affine4Batch:
             pass
 
 
-def align_affine4(pairs, cm: AffineCost, trace: bool = True):
-    """Every pair under the four-layer cost model `cm` (one Affine4Batch): [(cost, CIGAR)] with trace=True, else the int32 costs."""
+def align_affine4(pairs, cm: AffineCost, trace: bool = True, tiled: bool = False):
+    """Every pair under the four-layer cost model `cm` (one Affine4Batch): [(cost, CIGAR)] with trace=True, else the int32 costs.
+    tiled=True takes align_tiled() (bounded device memory, the same CIGARs) and needs trace=True."""
+    if tiled and not trace:
+        raise ValueError("tiled=True needs trace=True: the tiled route is a traceback")
     b = Affine4Batch(pairs, cm, trace=trace)
     try:
-        return b.align() if trace else b.run()
+        if not trace:
+            return b.run()
+        return b.align_tiled() if tiled else b.align()
     finally:
         b.close()
 

@@ -34,56 +34,13 @@
 // Codes of rows 1 .. H of column i at codes[i H + j - 1], row 0 at codes[(n + 1) H + i]; the kRows bytes of a lane and step go out as
 // one store.  affine4_walk_kernel walks them backwards from (n, m, main) to (0, 0, main).
 //
-// Global mode only: no ends-free mode, chained strips, tiled traceback or diagonal transition here.
+// The tiled traceback (align_tiled) has its kernels in affine4_tile_kernel.hpp, in a unit of their own.  Global mode only: no ends-free
+// mode, chained strips or diagonal transition here.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "strip_kernel.hpp"
-
-#ifndef PA_AFFINE4_ROWS
-#define PA_AFFINE4_ROWS 16
-#endif
+#include "affine4_common.hpp"  // constants, Costs, Pair, Wave, layer_op: shared with affine4_tile_kernel.hpp
 
 namespace pa {
 namespace affine4 {
-
-// (affine_kernel.hpp's constants and helpers, restated: that header also defines its walk kernels, which must stay in one unit.)
-constexpr int kRows = PA_AFFINE4_ROWS;  // rows of b per lane
-static_assert(kRows == 16 || kRows == 8, "the FILL store packs 16 or 8 code bytes");
-constexpr int kBlockWaves = 4;
-constexpr uint32_t kInf = 1u << 30;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t umin(uint32_t x, uint32_t y) { return x < y ? x : y; }
-__device__ __forceinline__ uint32_t umin3(uint32_t x, uint32_t y, uint32_t z) { return umin(umin(x, y), z); }
-
-// Edge costs: kInf where the model has no such edge; oe[k] = open + extend of layer k, e[k] its extend.
-struct Costs {
-    uint32_t sub, ins, del;
-    uint32_t oe[4], e[4];
-};
-
-// One pair.  Device pointers.
-struct Pair {
-    const uint8_t* a;
-    const uint8_t* b;
-    uint8_t* codes;  // FILL: (n + 1) H + n + 1 bytes
-    uint32_t n, m;   // |a|, |b|
-    uint32_t H;      // rows of a code column: g kRows (segments) or strips 64 kRows
-    uint32_t out;    // index into the cost output
-};
-static_assert(sizeof(Pair) == 40, "Pair layout");
-
-// One wavefront: pairs [first, first + np) of the Pair array, all of segment width 1 << lg; strips > 1 only for a lone pair (lg = 6).
-struct Wave {
-    uint32_t first, np, lg, strips;
-    uint32_t nmax;  // longest a of the wave
-    uint32_t pad_;
-    u32x4* bnd;  // strips > 1: nmax + 1 boundary values {M, I1, I2, 0} of the strip above
-};
-static_assert(sizeof(Wave) == 32, "Wave layout");
 
 template <bool FILL>
 __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* __restrict__ waves, int nwaves, const Pair* __restrict__ pairs, Costs C,
@@ -255,8 +212,6 @@ struct WalkOut {
     int32_t status;  // 0 ok, 1 bad code, 2 ops over capacity
     int32_t nops;
 };
-
-__device__ __forceinline__ uint8_t layer_op(int k) { return k == 0 ? 'i' : k == 1 ? 'd' : k == 2 ? 'j' : 'e'; }
 
 __global__ __launch_bounds__(64) void affine4_walk_kernel(const Walk* __restrict__ walks, int nw, WalkOut* __restrict__ outs) {
     const int t = (int)(blockIdx.x * 64 + threadIdx.x);

@@ -4,9 +4,9 @@
 // insert, delete].  The shape of affine_unit.hip's global-mode routes: every sequence is uploaded once; run() launches
 // affine4_kernel<false> (costs only) over a plan made at creation, short pairs packed into segments, longer ones a wavefront each, most
 // expensive waves first; align() re-runs the pairs with affine4_kernel<true> in chunks whose traceback codes (one byte per cell) fit a
-// device-memory budget, and walks every pair's codes on the GPU (affine4_walk_kernel).  No ends-free mode, chained strips, tiled
-// traceback or diagonal transition here.
-#include "pa_hip_internal.hpp"
+// device-memory budget, and walks every pair's codes on the GPU (affine4_walk_kernel).  align_tiled() is affine4_tiled_unit.hip;
+// the batch and the helpers both units use are in affine4_batch.hpp.  No ends-free mode, chained strips or diagonal transition here.
+#include "affine4_batch.hpp"
 #include "affine4_kernel.hpp"
 #include "../../include/pa_affine4_hip.h"
 
@@ -24,61 +24,8 @@ using namespace pa::affine4;
 namespace {
 
 constexpr int32_t kMaxCost = 1000;
-constexpr size_t kStripRows = 64 * kRows;  // rows of one strip
 
-int seg_lg(size_t m) {  // log2 of the segment width: smallest g = 2^lg with g kRows >= m
-    int lg = 0;
-    while ((size_t(kRows) << lg) < m) ++lg;
-    return lg;
-}
-size_t strips_of(uint32_t m) { return m <= kStripRows ? 1 : (m + kStripRows - 1) / kStripRows; }
-size_t rows_of(uint32_t m) { return m <= kStripRows ? size_t(kRows) << seg_lg(m) : strips_of(m) * kStripRows; }  // H
 size_t code_bytes_of(uint32_t n, uint32_t m) { return (((size_t)n + 1) * (rows_of(m) + 1) + 15) & ~size_t(15); }
-
-// One launch's worth of waves over a subset of the pairs.
-struct Plan {
-    std::vector<Wave> waves;
-    std::vector<Pair> pairs;
-    size_t bnd_vals = 0, code_bytes = 0;  // bnd_vals: 16-byte boundary values
-    double lanes = 0, slots = 0;
-    size_t packed = 0, strip = 0;
-    DeviceBuf d_waves, d_pairs, d_bnd;
-};
-
-}  // namespace
-
-struct pa_affine4_batch {
-    size_t np = 0;
-    bool trace = false;
-    Costs C{};
-    std::vector<uint32_t> n, m;
-    std::vector<size_t> aoff, boff;  // offsets of a and b in d_seq
-    std::vector<uint32_t> order;     // the planner's order: packed pairs by (g, |a|), then strip pairs by |a|
-    DeviceBuf d_seq, d_cost;
-    Plan fwd;
-    double trace_chunks = 0;
-};
-
-namespace {
-
-// The CIGAR text of a walk's ops (recorded from the end backwards): equal ops merge, the ops of every layer print as I / D.
-std::string cigar_of(const uint8_t* op, int32_t nops) {
-    std::string out;
-    char num[16];
-    for (int32_t x = nops - 1; x >= 0;) {
-        int32_t y = x;
-        while (y >= 0 && op[y] == op[x]) --y;
-        const int32_t k = x - y;
-        if (k > 1) {
-            std::snprintf(num, sizeof num, "%d", k);
-            out += num;
-        }
-        const uint8_t c = op[x];
-        out += c == 'i' || c == 'j' ? 'I' : c == 'd' || c == 'e' ? 'D' : (char)c;
-        x = y;
-    }
-    return out;
-}
 
 // Waves over `ids` (in planner order): 64 / g packed pairs of one width per wave, a wave per strip pair; then most expensive first.
 int make_plan(const pa_affine4_batch& ab, const std::vector<uint32_t>& ids, Plan& P, uint8_t* codes_base, hipStream_t s) {
@@ -138,27 +85,6 @@ bool launch(const pa_affine4_batch& ab, const Plan& P, hipStream_t s) {
     hipLaunchKernelGGL((affine4_kernel<FILL>), dim3(grid), dim3(64 * kBlockWaves), 0, s, P.d_waves.as<Wave>(), (int)P.waves.size(), P.d_pairs.as<Pair>(), ab.C,
                        ab.d_cost.as<int32_t>());
     return hip_ok(hipGetLastError(), FILL ? "affine4_kernel<FILL> launch" : "affine4_kernel launch");
-}
-
-struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    bool make() {
-        for (auto& x : e)
-            if (!hip_ok(hipEventCreate(&x), "hipEventCreate")) return false;
-        return true;
-    }
-    ~Events() {
-        for (auto& x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
-// The costs of every pair, to the caller.
-int costs_out(pa_affine4_batch& ab, int32_t* cost_out, hipStream_t s) {
-    if (!cost_out || ab.np == 0) return 0;
-    if (!hip_ok(hipMemcpyAsync(cost_out, ab.d_cost.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
-        return PA_E_HIP;
-    return 0;
 }
 
 }  // namespace

@@ -2,7 +2,7 @@
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
     python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
-                                 [--dt-seg] [--double] [--models affine,unit]
+                                 [--dt-seg] [--double] [--double-tiled] [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
 tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
@@ -39,7 +39,13 @@ Where align_dt_ends refuses the batch (a pair's fronts exceed the budget) its er
 whatever --shapes says: 100 000 x 150 bp and 4096 x 10 kbp at 5 %, a quarter of the pairs with one more indel of 20 to 200 bytes so that
 layers 2 and 3 are used.  Both batches hold the same pairs; run() alternates between them, each warmed once and then three times, and
 the line shows the fastest repeats, their ratio (double over affine) and how many pairs differ in cost between the two models.  align()
-does the same on --trace-pairs of the 10 kbp pairs."""
+does the same on --trace-pairs of the 10 kbp pairs.
+
+--double-tiled measures the tiled traceback of the double-affine batch (Affine4Batch.align_tiled) on the 10 kbp pairs of --double:
+align() and align_tiled() alternating on one batch of --trace-pairs of them, each warmed once and then three times, the fastest repeat
+of each, their ratio, and the results compared in every round; then align_tiled() alone on all 4096 pairs, and on 16 pairs of 100 kbp
+(once, unwarmed, in a process of its own under a time limit of two lone-wavefront passes).  Every leg prints tiled_info(): chunks,
+rounds, tile jobs, the cells re-filled and the bytes of the largest chunk, also per pair."""
 from __future__ import annotations
 
 import argparse
@@ -222,6 +228,51 @@ def double_legs(title, pairs, tp):
     print(f"{'':52s} align() of {len(tp)} pairs: affine forward {f2:9.2f} ms + walks {w2:7.2f} ms | double_affine forward {f4:9.2f} ms + walks"
           f" {w4:7.2f} ms | ratio forward {f4 / f2:6.3f}, all {(f4 + w4) / (f2 + w2):6.3f}  ({cells / (f4 + w4) / 1e6:.1f} GCUPS traced; chunks {chunks};"
           f" {differ} pairs differ in cost; repeats {' '.join(f'{sum(x):.2f}' for x in t2)} | {' '.join(f'{sum(x):.2f}' for x in t4)})", flush=True)
+
+
+def double_tiled_leg(title, tp, untiled, tile_cols, warm=True, reps=3):
+    """Affine4Batch.align() (if `untiled`) and align_tiled() under double_affine(4, 6, 2, 24, 1), alternating on one batch, each warmed once
+    (if `warm`) and then `reps` times; the fastest repeat of each, their ratio, and tiled_info().  -> the tiled route's fastest time."""
+    cm4 = AffineCost.double_affine(4, 6, 2, 24, 1)
+    cells = float(sum(len(x) * len(y) for x, y in tp))
+    b = Affine4Batch(tp, cm4, trace=True)
+    un, ti = [], []
+    base = None
+    for rep in range(reps + (1 if warm else 0)):
+        if untiled:
+            base = b.align()
+            u = (b.last_forward_ms, b.last_trace_ms)
+        got = b.align_tiled(tile_cols)
+        if untiled and got != base:
+            raise SystemExit(f"{title}: align_tiled() differs from align()")
+        if rep or not warm:
+            if untiled:
+                un.append(u)
+            ti.append((b.last_forward_ms, b.last_refill_ms, b.last_walk_ms))
+    info, chunks = b.tiled_info(), b.info()["trace_chunks"]
+    b.run()
+    run_ms = b.last_kernel_ms
+    b.close()
+    f, r, w = min(ti, key=sum)
+    t = f + r + w
+    line = f"{title:52s} align_tiled() of {len(tp)} pairs: {t:10.2f} ms = checkpoint pass {f:.2f} + fills {r:.2f} + walks {w:.2f}  ({cells / t / 1e6:.1f} GCUPS"
+    line += f"; run() {run_ms:.2f} ms, checkpoint pass over run() {f / run_ms:.3f}"
+    if untiled:
+        uf, uw = min(un, key=sum)
+        line += f") | align() {uf + uw:10.2f} ms = forward {uf:.2f} + walks {uw:.2f}, {chunks} chunks | ratio tiled over untiled {t / (uf + uw):6.3f}  ("
+        line += f"repeats {' '.join(f'{sum(x):.2f}' for x in un)} | {' '.join(f'{sum(x):.2f}' for x in ti)}"
+    else:
+        line += f"; repeats {' '.join(f'{sum(x):.2f}' for x in ti)}" + ("" if warm else ", unwarmed")
+    print(line + ")", flush=True)
+    print(f"{'':52s} tiled: {info['chunks']} chunks, {info['rounds']} rounds, {info['tile_jobs']} tile jobs, {info['refill_cells'] / 1e9:.2f} G cells"
+          f" re-filled ({info['refill_cells'] / cells:.3f} of the matrix), largest chunk {info['chunk_bytes_max']} bytes"
+          f" ({info['chunk_bytes_max'] / len(tp) / 1e6:.3f} MB per pair)", flush=True)
+    return t
+
+
+# The 100 kbp leg of --double-tiled: a pair's checkpoint pass runs on one wavefront (no chained strips in the four-layer route), about 7 s
+# for the two-layer kernel times the four-layer ratio of 1.3; the limit is two such passes.
+DOUBLE_100K_LIMIT_S = 2 * 7.0 * 1.3
 
 
 def chain_legs(title, pairs, cm, mname, tile_cols, reps):
@@ -443,6 +494,8 @@ def main():
     ap.add_argument("--dt-ends", action="store_true", help="measure the ends-free diagonal-transition route against the ends-free run() instead (see above)")
     ap.add_argument("--dt-seg", action="store_true", help="measure the segmented DT traceback against align_dt_ends instead (see above)")
     ap.add_argument("--double", action="store_true", help="measure Affine4Batch under double_affine against AffineBatch under affine instead (see above)")
+    ap.add_argument("--double-tiled", action="store_true", help="measure Affine4Batch.align_tiled() against Affine4Batch.align() instead (see above)")
+    ap.add_argument("--double-tiled-100k", action="store_true", help=argparse.SUPPRESS)  # the 100 kbp leg of --double-tiled, in a process of its own
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -451,6 +504,28 @@ def main():
     rng = np.random.default_rng(1)
     models = {"affine(4,6,2)": AffineCost.affine(4, 6, 2), "unit()": AffineCost.unit()}
     models = {k: v for k, v in models.items() if k.split("(")[0] in args.models.split(",")}
+    if args.double_tiled_100k:
+        title, pairs = shape("100k", np.random.default_rng(2))
+        t = double_tiled_leg(title + ", indels of 20-200 bp in a quarter", long_indels(rng, pairs), False, args.tile_cols, warm=False, reps=1)
+        if t > DOUBLE_100K_LIMIT_S * 1e3:
+            raise SystemExit(f"{title}: {t / 1e3:.1f} s is over the limit of {DOUBLE_100K_LIMIT_S:.1f} s (two lone-wavefront passes)")
+        return
+    if args.double_tiled:
+        long_indels(rng, shape("reads", rng)[1])  # (the pairs of --double: its 10 kbp shape comes after its reads)
+        title, pairs = shape("10k", rng)
+        pairs = long_indels(rng, pairs)
+        title += ", indels of 20-200 bp in a quarter"
+        double_tiled_leg(title, pairs[: args.trace_pairs], True, args.tile_cols)
+        double_tiled_leg(title, pairs, False, args.tile_cols)
+        # a process of its own under a wall-clock limit: the pairs (a minute of Python at most) and the one un-warmed call
+        cmd = [sys.executable, str(Path(__file__).resolve()), "--double-tiled-100k", "--tile-cols", str(args.tile_cols)]
+        try:
+            rc = subprocess.run(cmd, timeout=60 + DOUBLE_100K_LIMIT_S).returncode
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"16 x 100 kbp: no result within {60 + DOUBLE_100K_LIMIT_S:.0f} s")
+        if rc:
+            raise SystemExit(rc)
+        return
     if args.double:
         for sname in ("reads", "10k"):
             title, pairs = shape(sname, rng)
