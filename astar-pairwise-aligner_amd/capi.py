@@ -607,25 +607,31 @@ def _s_max_arg(s_max) -> int:
     return int(s_max)
 
 
-class AffineBatch:
-    """Gap-affine global alignment of many pairs on the GPU (pa_affine_batch_*): NW::new(cm, false, false).align(a, b) of pa-base-algos
-    for every pair, a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align().  chain=True runs every
-    pair with |b| > 1024 on a wavefront per strip of 1024 rows in run() and align_tiled() (set_chain); the results are the same.
-    free_start / free_end (set_free_ends) make the ends of a, the text, free: the pattern b is placed in a[start:end]."""
+class _AffineBatchBase:
+    """What AffineBatch (pa_affine_batch_*) and Affine4Batch (pa_affine4_batch_*) share: the C functions of either differ in their
+    prefix, `_PREFIX`, in the cost structure they take, `_cost_c`, and in where align_tiled() keeps the walk time, `_WALK_MS`."""
 
-    def __init__(self, pairs, cm: AffineCost, trace: bool = False, chain: bool = False, free_start: bool = False, free_end: bool = False):
-        free_start, free_end = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+    _PREFIX = ""
+    _WALK_MS = "last_trace_ms"
+
+    @staticmethod
+    def _cost_c(cm: AffineCost):
+        raise NotImplementedError
+
+    def _fn(self, name: str):
+        return getattr(load(), f"{self._PREFIX}_{name}")
+
+    def __init__(self, pairs, cm: AffineCost, trace: bool = False):
         pairs = list(pairs)
         if any(not isinstance(x, bytes) or not isinstance(y, bytes) for x, y in pairs):
             raise ValueError("pairs must be (bytes, bytes)")
         if not isinstance(cm, AffineCost):
             raise ValueError("cm must be an AffineCost")
-        c = cm.to_c()
+        c = self._cost_c(cm)
         big = cm.max_edge()
         for p, (x, y) in enumerate(pairs):
             if (len(x) + len(y) + 1) * big >= 1 << 30:
                 raise ValueError(f"pair {p}: (|a| + |b| + 1) * max edge cost is not below 2^30")
-        L = load()
         self._keep = pairs
         self.npairs = len(pairs)
         self.trace = bool(trace)
@@ -635,16 +641,99 @@ class AffineBatch:
         al = np.array([len(x) for x, _ in pairs] or [0], np.uint64)
         bl = np.array([len(y) for _, y in pairs] or [0], np.uint64)
         self._c = c
-        self._h = L.pa_affine_batch_create(ap, _p(al), bp, _p(bl), len(pairs), C.byref(c), int(self.trace))
+        self._h = self._fn("create")(ap, _p(al), bp, _p(bl), len(pairs), C.byref(c), int(self.trace))
         if not self._h:
             msg = last_error()
-            if msg.startswith("pa_affine_batch_create:"):
+            if msg.startswith(f"{self._PREFIX}_create:"):
                 raise ValueError(msg)
             raise PaError(msg)
         self.last_kernel_ms = 0.0
         self.last_forward_ms = 0.0
         self.last_refill_ms = 0.0
         self.last_trace_ms = 0.0
+
+    def _check(self, rc: int, what: str) -> None:
+        if rc == -4:
+            raise ValueError(last_error())
+        if rc != 0:
+            raise PaError(f"{what} rc={rc}: {last_error()}")
+
+    def run(self) -> np.ndarray:
+        """Costs only: int32[npairs]; the kernel time is kept in `last_kernel_ms`.  May be called again."""
+        costs = np.zeros(max(self.npairs, 1), np.int32)
+        ms = C.c_float(0)
+        self._check(self._fn("run")(self._h, _p(costs), C.byref(ms)), f"{self._PREFIX}_run")
+        self.last_kernel_ms = float(ms.value)
+        return costs[: self.npairs]
+
+    def _traced(self, name: str, args: tuple, times: tuple) -> list[tuple[int, str]]:
+        """[(cost, CIGAR)] of every pair from the C function `name`, which takes `args`, the outputs and one float per attribute of
+        `times`."""
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        cig = (C.c_void_p * max(n, 1))()
+        ms = [C.c_float(0) for _ in times]
+        rc = self._fn(name)(self._h, *args, _p(costs), cig, *[C.byref(t) for t in ms])
+        try:
+            self._check(rc, f"{self._PREFIX}_{name}")
+            cigars = _c_strings(cig, n)
+        finally:
+            load().pa_free_cigars(cig, n)
+        for attr, t in zip(times, ms):
+            setattr(self, attr, float(t.value))
+        return [(int(costs[p]), cigars[p]) for p in range(n)]
+
+    def align(self) -> list[tuple[int, str]]:
+        """[(cost, CIGAR)] of every pair (trace batches only), in chunks whose traceback codes stay within PA_AFFINE_TRACE_BUDGET_MB;
+        ValueError naming a pair whose codes alone exceed it."""
+        return self._traced("align", (), ("last_forward_ms", "last_trace_ms"))
+
+    def align_tiled(self, tile_cols: int = 0) -> list[tuple[int, str]]:
+        """align() in bounded device memory: checkpoints from a cost-only pass, then only the tiles the path crosses are filled with
+        codes and walked.  tile_cols: columns of a tile, 0 for the default of 1024, else in [64, 2^20].  The times are kept in
+        `last_forward_ms` (checkpoint pass), `last_refill_ms` (tile fills) and the walks' in `last_trace_ms` (AffineBatch) or
+        `last_walk_ms` (Affine4Batch)."""
+        if not isinstance(tile_cols, (int, np.integer)) or isinstance(tile_cols, bool) or not 0 <= tile_cols < 1 << 32:
+            raise ValueError(f"tile_cols must be 0 or in [64, 2^20], got {tile_cols!r}")
+        return self._traced("align_tiled", (int(tile_cols),), ("last_forward_ms", "last_refill_ms", self._WALK_MS))
+
+    def tiled_info(self) -> dict:
+        """Shape of the last align_tiled(): chunks, rounds, tile jobs, cells the fills computed, bytes of the largest chunk."""
+        vals = [C.c_double(0) for _ in range(5)]
+        self._fn("tiled_info")(self._h, *[C.byref(v) for v in vals])
+        return {k: int(v.value) for k, v in zip(("chunks", "rounds", "tile_jobs", "refill_cells", "chunk_bytes_max"), vals)}
+
+    def info(self) -> dict:
+        """The plan of run(): waves, packed and strip pairs, the share of lanes that hold rows; and the chunks of the last align()."""
+        vals = [C.c_double(0) for _ in range(5)]
+        self._fn("info")(self._h, *[C.byref(v) for v in vals])
+        return {"waves": int(vals[0].value), "packed_pairs": int(vals[1].value), "strip_pairs": int(vals[2].value), "lane_use": vals[3].value,
+                "trace_chunks": int(vals[4].value)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AffineBatch(_AffineBatchBase):
+    """Gap-affine global alignment of many pairs on the GPU (pa_affine_batch_*): NW::new(cm, false, false).align(a, b) of pa-base-algos
+    for every pair, a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align().  chain=True runs every
+    pair with |b| > 1024 on a wavefront per strip of 1024 rows in run() and align_tiled() (set_chain); the results are the same.
+    free_start / free_end (set_free_ends) make the ends of a, the text, free: the pattern b is placed in a[start:end]."""
+
+    _PREFIX = "pa_affine_batch"
+    _cost_c = staticmethod(AffineCost.to_c)
+
+    def __init__(self, pairs, cm: AffineCost, trace: bool = False, chain: bool = False, free_start: bool = False, free_end: bool = False):
+        free_start, free_end = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+        super().__init__(pairs, cm, trace)
         if chain:
             self.set_chain(True)
         if free_start or free_end:
@@ -692,62 +781,6 @@ class AffineBatch:
         d = {k: int(v.value) for k, v in zip(("on", "chain_pairs", "chain_jobs", "chunks", "bnd_bytes_max"), vals)}
         d["on"] = bool(d["on"])
         return d
-
-    def _check(self, rc: int, what: str) -> None:
-        if rc == -4:
-            raise ValueError(last_error())
-        if rc != 0:
-            raise PaError(f"{what} rc={rc}: {last_error()}")
-
-    def run(self) -> np.ndarray:
-        """Costs only: int32[npairs]; the kernel time is kept in `last_kernel_ms`."""
-        costs = np.zeros(max(self.npairs, 1), np.int32)
-        ms = C.c_float(0)
-        self._check(load().pa_affine_batch_run(self._h, _p(costs), C.byref(ms)), "pa_affine_batch_run")
-        self.last_kernel_ms = float(ms.value)
-        return costs[: self.npairs]
-
-    def align(self) -> list[tuple[int, str]]:
-        """[(cost, CIGAR)] of every pair (trace batches only)."""
-        L = load()
-        n = self.npairs
-        costs = np.zeros(max(n, 1), np.int32)
-        cig = (C.c_void_p * max(n, 1))()
-        f, t = C.c_float(0), C.c_float(0)
-        rc = L.pa_affine_batch_align(self._h, _p(costs), cig, C.byref(f), C.byref(t))
-        try:
-            self._check(rc, "pa_affine_batch_align")
-            cigars = _c_strings(cig, n)
-        finally:
-            L.pa_free_cigars(cig, n)
-        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
-        return [(int(costs[p]), cigars[p]) for p in range(n)]
-
-    def align_tiled(self, tile_cols: int = 0) -> list[tuple[int, str]]:
-        """align() in bounded device memory: checkpoints from a cost-only pass, then only the tiles the path crosses are filled with
-        codes.  tile_cols: columns of a tile, 0 for the default, else in [64, 2^20].  The times are kept in `last_forward_ms`
-        (checkpoint pass), `last_refill_ms` (tile fills) and `last_trace_ms` (walks)."""
-        if not isinstance(tile_cols, (int, np.integer)) or isinstance(tile_cols, bool) or not 0 <= tile_cols < 1 << 32:
-            raise ValueError(f"tile_cols must be 0 or in [64, 2^20], got {tile_cols!r}")
-        L = load()
-        n = self.npairs
-        costs = np.zeros(max(n, 1), np.int32)
-        cig = (C.c_void_p * max(n, 1))()
-        f, r, t = C.c_float(0), C.c_float(0), C.c_float(0)
-        rc = L.pa_affine_batch_align_tiled(self._h, int(tile_cols), _p(costs), cig, C.byref(f), C.byref(r), C.byref(t))
-        try:
-            self._check(rc, "pa_affine_batch_align_tiled")
-            cigars = _c_strings(cig, n)
-        finally:
-            L.pa_free_cigars(cig, n)
-        self.last_forward_ms, self.last_refill_ms, self.last_trace_ms = float(f.value), float(r.value), float(t.value)
-        return [(int(costs[p]), cigars[p]) for p in range(n)]
-
-    def tiled_info(self) -> dict:
-        """Shape of the last align_tiled(): chunks, rounds, tile jobs, cells the fills computed, bytes of the largest chunk."""
-        vals = [C.c_double(0) for _ in range(5)]
-        load().pa_affine_batch_tiled_info(self._h, *[C.byref(v) for v in vals])
-        return {k: int(v.value) for k, v in zip(("chunks", "rounds", "tile_jobs", "refill_cells", "chunk_bytes_max"), vals)}
 
     @staticmethod
     def _s_max(s_max) -> int:
@@ -857,23 +890,6 @@ class AffineBatch:
         load().pa_affine_batch_dt_info(self._h, *[C.byref(v) for v in vals])
         return {k: int(v.value) for k, v in zip(("found", "not_found", "chunks", "front_cells", "extend_chars", "bytes_max"), vals)}
 
-    def info(self) -> dict:
-        vals = [C.c_double(0) for _ in range(5)]
-        load().pa_affine_batch_info(self._h, *[C.byref(v) for v in vals])
-        return {"waves": int(vals[0].value), "packed_pairs": int(vals[1].value), "strip_pairs": int(vals[2].value), "lane_use": vals[3].value,
-                "trace_chunks": int(vals[4].value)}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            load().pa_affine_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False, s_max: int | None = None) -> list[tuple[int, str]]:
     """[(cost, CIGAR)] of every pair under the gap-affine cost model `cm` (one traced AffineBatch); tiled=True takes the
@@ -893,120 +909,20 @@ def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False
         b.close()
 
 
-class Affine4Batch:
+class Affine4Batch(_AffineBatchBase):
     """Double-affine (two-piece gap cost) global alignment of many pairs on the GPU (pa_affine4_batch_*): NW::new(cm, false,
     false).align(a, b) of pa-base-algos under an AffineCost<4> with layers [ins, del, ins, del] (AffineCost.double_affine, or four
     layers with costs of their own), a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align() and
     align_tiled(), the same CIGARs in bounded device memory (include/pa_affine4_tiled_hip.h).  Global mode only: ends-free mode,
     chained strips and diagonal transition are AffineBatch's, for two layers."""
 
+    _PREFIX = "pa_affine4_batch"
+    _WALK_MS = "last_walk_ms"
+    _cost_c = staticmethod(AffineCost.to_c4)
+
     def __init__(self, pairs, cm: AffineCost, trace: bool = False):
-        pairs = list(pairs)
-        if any(not isinstance(x, bytes) or not isinstance(y, bytes) for x, y in pairs):
-            raise ValueError("pairs must be (bytes, bytes)")
-        if not isinstance(cm, AffineCost):
-            raise ValueError("cm must be an AffineCost")
-        c = cm.to_c4()
-        big = cm.max_edge()
-        for p, (x, y) in enumerate(pairs):
-            if (len(x) + len(y) + 1) * big >= 1 << 30:
-                raise ValueError(f"pair {p}: (|a| + |b| + 1) * max edge cost is not below 2^30")
-        L = load()
-        self._keep = pairs
-        self.npairs = len(pairs)
-        self.trace = bool(trace)
-        n = max(len(pairs), 1)
-        ap = (C.c_char_p * n)(*[x for x, _ in pairs])
-        bp = (C.c_char_p * n)(*[y for _, y in pairs])
-        al = np.array([len(x) for x, _ in pairs] or [0], np.uint64)
-        bl = np.array([len(y) for _, y in pairs] or [0], np.uint64)
-        self._c = c
-        self._h = L.pa_affine4_batch_create(ap, _p(al), bp, _p(bl), len(pairs), C.byref(c), int(self.trace))
-        if not self._h:
-            msg = last_error()
-            if msg.startswith("pa_affine4_batch_create:"):
-                raise ValueError(msg)
-            raise PaError(msg)
-        self.last_kernel_ms = 0.0
-        self.last_forward_ms = 0.0
-        self.last_trace_ms = 0.0
-        self.last_refill_ms = 0.0
+        super().__init__(pairs, cm, trace)
         self.last_walk_ms = 0.0
-
-    def _check(self, rc: int, what: str) -> None:
-        if rc == -4:
-            raise ValueError(last_error())
-        if rc != 0:
-            raise PaError(f"{what} rc={rc}: {last_error()}")
-
-    def run(self) -> np.ndarray:
-        """Costs only: int32[npairs]; the kernel time is kept in `last_kernel_ms`.  May be called again."""
-        costs = np.zeros(max(self.npairs, 1), np.int32)
-        ms = C.c_float(0)
-        self._check(load().pa_affine4_batch_run(self._h, _p(costs), C.byref(ms)), "pa_affine4_batch_run")
-        self.last_kernel_ms = float(ms.value)
-        return costs[: self.npairs]
-
-    def align(self) -> list[tuple[int, str]]:
-        """[(cost, CIGAR)] of every pair (trace batches only), in chunks whose traceback codes stay within PA_AFFINE_TRACE_BUDGET_MB;
-        ValueError naming a pair whose codes alone exceed it."""
-        L = load()
-        n = self.npairs
-        costs = np.zeros(max(n, 1), np.int32)
-        cig = (C.c_void_p * max(n, 1))()
-        f, t = C.c_float(0), C.c_float(0)
-        rc = L.pa_affine4_batch_align(self._h, _p(costs), cig, C.byref(f), C.byref(t))
-        try:
-            self._check(rc, "pa_affine4_batch_align")
-            cigars = _c_strings(cig, n)
-        finally:
-            L.pa_free_cigars(cig, n)
-        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
-        return [(int(costs[p]), cigars[p]) for p in range(n)]
-
-    def align_tiled(self, tile_cols: int = 0) -> list[tuple[int, str]]:
-        """align(), byte for byte, in bounded device memory: checkpoints from a cost-only pass, then only the tiles the path crosses
-        are filled with codes and walked.  tile_cols: columns of a tile, 0 for the default of 1024, else in [64, 2^20].  The times are
-        kept in `last_forward_ms` (checkpoint pass), `last_refill_ms` (tile fills) and `last_walk_ms` (walks)."""
-        if not isinstance(tile_cols, (int, np.integer)) or isinstance(tile_cols, bool) or not 0 <= tile_cols < 1 << 32:
-            raise ValueError(f"tile_cols must be 0 or in [64, 2^20], got {tile_cols!r}")
-        L = load()
-        n = self.npairs
-        costs = np.zeros(max(n, 1), np.int32)
-        cig = (C.c_void_p * max(n, 1))()
-        f, r, t = C.c_float(0), C.c_float(0), C.c_float(0)
-        rc = L.pa_affine4_batch_align_tiled(self._h, int(tile_cols), _p(costs), cig, C.byref(f), C.byref(r), C.byref(t))
-        try:
-            self._check(rc, "pa_affine4_batch_align_tiled")
-            cigars = _c_strings(cig, n)
-        finally:
-            L.pa_free_cigars(cig, n)
-        self.last_forward_ms, self.last_refill_ms, self.last_walk_ms = float(f.value), float(r.value), float(t.value)
-        return [(int(costs[p]), cigars[p]) for p in range(n)]
-
-    def tiled_info(self) -> dict:
-        """Shape of the last align_tiled(): chunks, rounds, tile jobs, cells the fills computed, bytes of the largest chunk."""
-        vals = [C.c_double(0) for _ in range(5)]
-        load().pa_affine4_batch_tiled_info(self._h, *[C.byref(v) for v in vals])
-        return {k: int(v.value) for k, v in zip(("chunks", "rounds", "tile_jobs", "refill_cells", "chunk_bytes_max"), vals)}
-
-    def info(self) -> dict:
-        """The plan of run(), as AffineBatch.info() reports it, and the chunks of the last align()."""
-        vals = [C.c_double(0) for _ in range(5)]
-        load().pa_affine4_batch_info(self._h, *[C.byref(v) for v in vals])
-        return {"waves": int(vals[0].value), "packed_pairs": int(vals[1].value), "strip_pairs": int(vals[2].value), "lane_use": vals[3].value,
-                "trace_chunks": int(vals[4].value)}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            load().pa_affine4_batch_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def align_affine4(pairs, cm: AffineCost, trace: bool = True, tiled: bool = False):

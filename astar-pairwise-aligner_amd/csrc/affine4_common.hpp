@@ -46,8 +46,8 @@ static_assert(sizeof(Pair) == 40, "Pair layout");
 struct Wave {
     uint32_t first, np, lg, strips;
     uint32_t nmax;  // longest a of the wave
-    uint32_t pad_;
-    u32x4* bnd;  // strips > 1: nmax + 1 boundary values {M, I1, I2, 0} of the strip above
+    uint32_t tile_cols;  // 0: no kernel reads it here (CkWave's place for it, affine4_tile_kernel.hpp; the host fills both alike)
+    u32x4* bnd;          // strips > 1: nmax + 1 boundary values {M, I1, I2, 0} of the strip above
 };
 static_assert(sizeof(Wave) == 32, "Wave layout");
 
