@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine_batch_run_dt_ends", "pa_affine_batch_align_dt_ends",
     "pa_affine_batch_align_dt_seg", "pa_affine_batch_dt_seg_info",
     "pa_affine4_batch_create", "pa_affine4_batch_run", "pa_affine4_batch_align", "pa_affine4_batch_info", "pa_affine4_batch_destroy",
-    "pa_affine4_batch_align_tiled", "pa_affine4_batch_tiled_info",
+    "pa_affine4_batch_align_tiled", "pa_affine4_batch_tiled_info", "pa_affine4_batch_set_chain", "pa_affine4_batch_chain_info",
 ]
 
 _lib = None
@@ -142,6 +142,10 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine4_batch_align_tiled.argtypes = [vp, C.c_uint32, vp, vp] + [C.POINTER(C.c_float)] * 3
         L.pa_affine4_batch_tiled_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
         L.pa_affine4_batch_tiled_info.restype = None
+    if hasattr(L, "pa_affine4_batch_set_chain"):
+        L.pa_affine4_batch_set_chain.argtypes = [vp, C.c_int]
+        L.pa_affine4_batch_chain_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
+        L.pa_affine4_batch_chain_info.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -609,7 +613,8 @@ def _s_max_arg(s_max) -> int:
 
 class _AffineBatchBase:
     """What AffineBatch (pa_affine_batch_*) and Affine4Batch (pa_affine4_batch_*) share: the C functions of either differ in their
-    prefix, `_PREFIX`, in the cost structure they take, `_cost_c`, and in where align_tiled() keeps the walk time, `_WALK_MS`."""
+    prefix, `_PREFIX`, in the cost structure they take, `_cost_c`, and in where align_tiled() keeps the walk time, `_WALK_MS`.  Both have
+    the chained route (set_chain, chain_info)."""
 
     _PREFIX = ""
     _WALK_MS = "last_trace_ms"
@@ -710,6 +715,18 @@ class _AffineBatchBase:
         return {"waves": int(vals[0].value), "packed_pairs": int(vals[1].value), "strip_pairs": int(vals[2].value), "lane_use": vals[3].value,
                 "trace_chunks": int(vals[4].value)}
 
+    def set_chain(self, on: bool) -> None:
+        """Chained strips for pairs with |b| > 1024 in run() and align_tiled() (align() ignores it).  Off by default."""
+        self._check(self._fn("set_chain")(self._h, 1 if on else 0), f"{self._PREFIX}_set_chain")
+
+    def chain_info(self) -> dict:
+        """The setting, and the last chained pass: pairs and strip jobs run chained, chunks, boundary-row bytes of the largest chunk."""
+        vals = [C.c_double(0) for _ in range(5)]
+        self._fn("chain_info")(self._h, *[C.byref(v) for v in vals])
+        d = {k: int(v.value) for k, v in zip(("on", "chain_pairs", "chain_jobs", "chunks", "bnd_bytes_max"), vals)}
+        d["on"] = bool(d["on"])
+        return d
+
     def close(self):
         if getattr(self, "_h", None):
             self._fn("destroy")(self._h)
@@ -769,18 +786,6 @@ class AffineBatch(_AffineBatchBase):
         out = np.zeros(max(total, 1), np.int32)
         self._check(load().pa_affine_batch_last_row(self._h, _p(out), _p(offs)), "pa_affine_batch_last_row")
         return [out[int(offs[p]): int(offs[p]) + len(self._keep[p][0]) + 1].copy() for p in ids]
-
-    def set_chain(self, on: bool) -> None:
-        """Chained strips for pairs with |b| > 1024 in run() and align_tiled() (align() ignores it).  Off by default."""
-        self._check(load().pa_affine_batch_set_chain(self._h, 1 if on else 0), "pa_affine_batch_set_chain")
-
-    def chain_info(self) -> dict:
-        """The setting, and the last chained pass: pairs and strip jobs run chained, chunks, boundary-row bytes of the largest chunk."""
-        vals = [C.c_double(0) for _ in range(5)]
-        load().pa_affine_batch_chain_info(self._h, *[C.byref(v) for v in vals])
-        d = {k: int(v.value) for k, v in zip(("on", "chain_pairs", "chain_jobs", "chunks", "bnd_bytes_max"), vals)}
-        d["on"] = bool(d["on"])
-        return d
 
     @staticmethod
     def _s_max(s_max) -> int:
@@ -913,16 +918,19 @@ class Affine4Batch(_AffineBatchBase):
     """Double-affine (two-piece gap cost) global alignment of many pairs on the GPU (pa_affine4_batch_*): NW::new(cm, false,
     false).align(a, b) of pa-base-algos under an AffineCost<4> with layers [ins, del, ins, del] (AffineCost.double_affine, or four
     layers with costs of their own), a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align() and
-    align_tiled(), the same CIGARs in bounded device memory (include/pa_affine4_tiled_hip.h).  Global mode only: ends-free mode,
-    chained strips and diagonal transition are AffineBatch's, for two layers."""
+    align_tiled(), the same CIGARs in bounded device memory (include/pa_affine4_tiled_hip.h).  chain=True runs every pair with
+    |b| > 1024 on a wavefront per strip of 1024 rows in run() and align_tiled() (set_chain, include/pa_affine4_chain_hip.h); the results
+    are the same.  Global mode only: ends-free mode and diagonal transition are AffineBatch's, for two layers."""
 
     _PREFIX = "pa_affine4_batch"
     _WALK_MS = "last_walk_ms"
     _cost_c = staticmethod(AffineCost.to_c4)
 
-    def __init__(self, pairs, cm: AffineCost, trace: bool = False):
+    def __init__(self, pairs, cm: AffineCost, trace: bool = False, chain: bool = False):
         super().__init__(pairs, cm, trace)
         self.last_walk_ms = 0.0
+        if chain:
+            self.set_chain(True)
 
 
 def align_affine4(pairs, cm: AffineCost, trace: bool = True, tiled: bool = False):

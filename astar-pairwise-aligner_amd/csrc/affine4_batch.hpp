@@ -1,9 +1,12 @@
 // affine4_batch.hpp -- what the two double-affine units share: the batch, and the part of affine_host.hpp's traits that both
 // affine4_unit.hip (create, run, align, info) and affine4_tiled_unit.hip (align_tiled, tiled_info) give.  Each unit adds the records and
-// launches of its own kernels; no kernel is defined or launched here.
+// launches of its own kernels; no kernel is launched here.  The chained route (set_chain) is split the same way: its state is the
+// batch's, its host side affine_chain_host.hpp's, and of affine4_chain_kernel<CKPT> (a template: each unit instantiates what it
+// launches) affine4_unit.hip runs the cost-only form in run() and affine4_tiled_unit.hip the checkpointing one in align_tiled().
 #pragma once
 #include "affine4_common.hpp"
-#include "affine_host.hpp"
+#include "affine4_chain_kernel.hpp"
+#include "affine_chain_host.hpp"
 
 #include <cstdio>
 #include <string>
@@ -11,6 +14,7 @@
 
 struct pa_affine4_batch : pa::affine_host::Batch<pa::affine4::Pair, pa::affine4::Wave> {
     pa::affine4::Costs C{};
+    pa::affine_host::ChainState<pa::affine_host::Plan<pa::affine4::Pair, pa::affine4::Wave>> chain;  // set_chain
 };
 
 namespace pa {
@@ -20,6 +24,7 @@ struct HostBase {
     using Batch = pa_affine4_batch;
     using Pair = affine4::Pair;
     using Wave = affine4::Wave;
+    using ChainJob = affine4::ChainJob;
     // 16-byte boundary values {M, I1, I2, 0}, 12-byte checkpoint rows {M, D1, D2}; a pair's checkpoints are loaded as 16-byte values
     static constexpr affine_plan::Layout kLayout{kRows, 16, 12, 16};
     static constexpr const char* kName = "pa_affine4_batch";

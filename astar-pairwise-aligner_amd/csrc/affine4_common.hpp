@@ -51,6 +51,16 @@ struct Wave {
 };
 static_assert(sizeof(Wave) == 32, "Wave layout");
 
+// A column checkpoint (affine4_tile_kernel.hpp has the layout): what affine4_ckpt_kernel and affine4_chain_kernel<true> store alike.
+constexpr int kCkWords = 3;                    // uint32 words of one row of a column checkpoint: M, D1, D2
+constexpr int kCkVecs = kCkWords * kRows / 4;  // 16-byte values of one lane's rows
+static_assert((kCkWords * kRows) % 4 == 0, "a lane's checkpoint rows are whole 16-byte values");
+
+// Word q of a lane's checkpoint rows: {M, D1, D2} of row q / 3.
+__device__ __forceinline__ uint32_t ck_word(const uint32_t (&Mp)[kRows], const uint32_t (&D1p)[kRows], const uint32_t (&D2p)[kRows], int q) {
+    return q % 3 == 0 ? Mp[q / 3] : q % 3 == 1 ? D1p[q / 3] : D2p[q / 3];
+}
+
 // The op byte of a step inside layer k: distinct per layer, so that the host merges only the gaps of one layer.
 __device__ __forceinline__ uint8_t layer_op(int k) { return k == 0 ? 'i' : k == 1 ? 'd' : k == 2 ? 'j' : 'e'; }
 

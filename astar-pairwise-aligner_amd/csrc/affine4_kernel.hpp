@@ -34,8 +34,9 @@
 // Codes of rows 1 .. H of column i at codes[i H + j - 1], row 0 at codes[(n + 1) H + i]; the kRows bytes of a lane and step go out as
 // one store.  affine4_walk_kernel walks them backwards from (n, m, main) to (0, 0, main).
 //
-// The tiled traceback (align_tiled) has its kernels in affine4_tile_kernel.hpp, in a unit of their own.  Global mode only: no ends-free
-// mode, chained strips or diagonal transition here.
+// The tiled traceback (align_tiled) has its kernels in affine4_tile_kernel.hpp, in a unit of their own, and the chained route (set_chain:
+// the strips of a longer pair on a wavefront each, side by side) its kernel in affine4_chain_kernel.hpp.  Global mode only.  Not
+// supported: ends-free mode, diagonal transition, other layer lists.
 #pragma once
 #include "affine4_common.hpp"  // constants, Costs, Pair, Wave, layer_op: shared with affine4_tile_kernel.hpp
 

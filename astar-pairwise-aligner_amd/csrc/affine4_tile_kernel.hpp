@@ -29,9 +29,7 @@
 namespace pa {
 namespace affine4 {
 
-constexpr int kCkWords = 3;                          // uint32 words of one row of a column checkpoint: M, D1, D2
-constexpr int kCkVecs = kCkWords * kRows / 4;        // 16-byte values of one lane's rows
-static_assert((kCkWords * kRows) % 4 == 0, "a lane's checkpoint rows are whole 16-byte values");
+// (kCkWords, kCkVecs and ck_word, the column checkpoint of one lane, are affine4_common.hpp's: affine4_chain_kernel<true> stores them too.)
 
 // One wavefront of the checkpoint pass: Wave with the tile width, and every strip's boundary row kept.
 struct CkWave {
@@ -41,11 +39,6 @@ struct CkWave {
     u32x4* bnd;          // strips > 1: strips - 1 rows of nmax + 1 boundary values {M, I1, I2, 0}
 };
 static_assert(sizeof(CkWave) == 32, "CkWave layout");
-
-// Word q of a lane's checkpoint rows: {M, D1, D2} of row q / 3.
-__device__ __forceinline__ uint32_t ck_word(const uint32_t (&Mp)[kRows], const uint32_t (&D1p)[kRows], const uint32_t (&D2p)[kRows], int q) {
-    return q % 3 == 0 ? Mp[q / 3] : q % 3 == 1 ? D1p[q / 3] : D2p[q / 3];
-}
 
 // Four wavefronts per SIMD, the cost kernel's occupancy, asked for in the launch bounds: left to itself the compiler takes 131
 // registers for this kernel (three wavefronts); told the target it fits 127, without scratch or AGPRs.

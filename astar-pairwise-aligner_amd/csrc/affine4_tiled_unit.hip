@@ -4,7 +4,8 @@
 // Per chunk: a cost-only pass that keeps checkpoints (affine4_ckpt_kernel), then rounds.  In a round the host reads every pair's walk
 // state, makes one tile job per unfinished pair, and launches one fill (affine4_tile_kernel) and one walk (affine4_tile_walk_kernel); a
 // pair can visit only so many tiles, so the rounds end.  The driver is affine_host.hpp's align_tiled, shared with the two-layer batch;
-// the layouts are in affine4_tile_kernel.hpp, the byte formula in the header.
+// the layouts are in affine4_tile_kernel.hpp, the byte formula in the header.  With set_chain(1) the checkpoint pass runs the pairs with
+// |b| > 1024 through affine4_chain_kernel<true>, which keeps the same checkpoints in the same places.
 #include "affine4_tile_kernel.hpp"
 #include "affine4_batch.hpp"
 #include "../../include/pa_affine4_tiled_hip.h"
@@ -22,18 +23,24 @@ struct Host : HostBase {
     using TileWave = affine4::TileWave;
     static_assert(kLayout.ck_row_bytes == kCkWords * 4, "a checkpoint row is kCkWords uint32");
 
-    static void begin_tiled(Batch&) {}
-    // The checkpoint pass of a chunk: one launch over the chunk's plan.
-    static int ckpt_pass(Batch& ab, affine_host::TiledChunk<Host>& ch, uint32_t, hipStream_t s, float* ms) {
-        affine_host::Events ev;
-        if (!ev.make() || !hip_ok(hipEventRecord(ev.e[0], s), "event")) return PA_E_HIP;
-        const int nw = (int)ch.plan.waves.size();
-        hipLaunchKernelGGL(affine4_ckpt_kernel, dim3((nw + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, ch.plan.d_waves.as<CkWave>(), nw,
-                           ch.plan.d_pairs.as<Pair>(), ab.C, ab.d_cost.as<int32_t>());
-        if (!hip_ok(hipGetLastError(), "affine4_ckpt_kernel launch") || !hip_ok(hipEventRecord(ev.e[1], s), "event") ||
-            !hip_ok(hipStreamSynchronize(s), "sync") || !hip_ok(hipEventElapsedTime(ms, ev.e[0], ev.e[1]), "hipEventElapsedTime"))
-            return PA_E_HIP;
-        return 0;
+    static void begin_tiled(Batch& ab) { affine_host::chain_begin(ab); }
+    // The checkpoint pass of a chunk: one launch over the chunk's plan or, with chaining on, over its one-strip waves, and the strip
+    // pairs chained (affine_chain_host.hpp).
+    static int ckpt_pass(Batch& ab, affine_host::TiledChunk<Host>& ch, uint32_t C, hipStream_t s, float* ms) {
+        return affine_host::ckpt_pass<Host>(ab, ch, C, s, ms);
+    }
+    static bool launch_ckpt(const Batch& ab, const CkWave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s) {
+        if (nwaves == 0) return true;
+        const int nw = (int)nwaves;
+        hipLaunchKernelGGL(affine4_ckpt_kernel, dim3((nw + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, d_waves, nw, d_pairs, ab.C,
+                           ab.d_cost.as<int32_t>());
+        return hip_ok(hipGetLastError(), "affine4_ckpt_kernel launch");
+    }
+    static bool launch_chain_ckpt(const Batch& ab, const ChainJob* d_jobs, int njobs, const Pair* d_pairs, uint32_t tile_cols, uint32_t* ticket_err,
+                                  hipStream_t s) {
+        hipLaunchKernelGGL((affine4_chain_kernel<true>), dim3((njobs + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, d_jobs, njobs, d_pairs,
+                           ab.C, tile_cols, ticket_err, ab.d_cost.as<int32_t>());
+        return hip_ok(hipGetLastError(), "affine4_chain_kernel<CKPT> launch");
     }
     static bool launch_tile_fill(const Batch& ab, const TileWave* d_waves, int nw, const TileJob* d_jobs, hipStream_t s) {
         hipLaunchKernelGGL(affine4_tile_kernel, dim3((nw + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, d_waves, nw, d_jobs, ab.C);

@@ -6,10 +6,12 @@
 // expensive waves first; align() re-runs the pairs with affine4_kernel<true> in chunks whose traceback codes (one byte per cell) fit a
 // device-memory budget, and walks every pair's codes on the GPU (affine4_walk_kernel).  align_tiled() is affine4_tiled_unit.hip; the
 // batch is in affine4_batch.hpp, and the plan, the tail of create and the driver of align() are affine_host.hpp's, shared with the
-// two-layer batch.  No ends-free mode, chained strips or diagonal transition here.
+// two-layer batch.  set_chain(1) (include/pa_affine4_chain_hip.h) sends the pairs with |b| > 1024 through affine4_chain_kernel<false>
+// in run(), a wavefront per strip, the strips of a pair chained through their boundary rows; the host side of that route is
+// affine_chain_host.hpp's, shared likewise.  Not supported: ends-free mode, diagonal transition, other layer lists.
 #include "affine4_kernel.hpp"
 #include "affine4_batch.hpp"
-#include "../../include/pa_affine4_hip.h"
+#include "../../include/pa_affine4_chain_hip.h"
 
 #include <algorithm>
 
@@ -39,6 +41,12 @@ struct Host : HostBase {
         return hip_ok(hipGetLastError(), "affine4_walk_kernel launch");
     }
     static int64_t walk_start(const WalkOut&) { return 0; }
+    // affine4_chain_kernel<false> over one chunk's jobs (the chained route's host side is affine_chain_host.hpp's)
+    static bool launch_chain_run(const Batch& ab, const ChainJob* d_jobs, int njobs, const Pair* d_pairs, uint32_t* ticket_err, hipStream_t s) {
+        hipLaunchKernelGGL((affine4_chain_kernel<false>), dim3((njobs + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, d_jobs, njobs, d_pairs,
+                           ab.C, 0u, ticket_err, ab.d_cost.as<int32_t>());
+        return hip_ok(hipGetLastError(), "affine4_chain_kernel launch");
+    }
 };
 
 }  // namespace
@@ -88,8 +96,12 @@ extern "C" int pa_affine4_batch_run(pa_affine4_batch* ab, int32_t* cost_out, flo
     if (ab->np == 0) return 0;
     hipStream_t s = 0;
     affine_host::Events ev;
-    if (!ev.make() || !hip_ok(hipEventRecord(ev.e[0], s), "event") || !Host::launch<false>(*ab, ab->fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event") ||
-        !hip_ok(hipStreamSynchronize(s), "sync"))
+    if (!ev.make()) return PA_E_HIP;
+    affine_host::chain_begin(*ab);
+    if (ab->chain.on && !ab->chain.ids.empty()) {  // the packed pairs' launch, then a wavefront per strip of the others
+        if (const int rc = affine_host::run_chained<Host>(*ab, ev, s)) return rc;
+    } else if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !Host::launch<false>(*ab, ab->fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event") ||
+               !hip_ok(hipStreamSynchronize(s), "sync"))
         return PA_E_HIP;
     if (const int rc = Host::finish(*ab, cost_out, s)) return rc;
     if (kernel_ms && !hip_ok(hipEventElapsedTime(kernel_ms, ev.e[0], ev.e[1]), "hipEventElapsedTime")) return PA_E_HIP;
@@ -103,6 +115,13 @@ extern "C" int pa_affine4_batch_align(pa_affine4_batch* ab, int32_t* cost_out, c
 extern "C" void pa_affine4_batch_info(const pa_affine4_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,
                                       double* trace_chunks) {
     affine_host::batch_info(ab, waves, packed_pairs, strip_pairs, lane_use, trace_chunks);
+}
+
+extern "C" int pa_affine4_batch_set_chain(pa_affine4_batch* ab, int on) { return affine_host::set_chain<Host>(ab, on); }
+
+extern "C" void pa_affine4_batch_chain_info(const pa_affine4_batch* ab, double* on, double* chain_pairs, double* chain_jobs, double* chunks,
+                                            double* bnd_bytes_max) {
+    affine_host::chain_info(ab, on, chain_pairs, chain_jobs, chunks, bnd_bytes_max);
 }
 
 extern "C" void pa_affine4_batch_destroy(pa_affine4_batch* ab) {

@@ -12,12 +12,12 @@
 // routes: the launches then pick the kernels' ENDS instantiations, which leave every pair's end in d_end; the walks start there, and
 // pa_affine_batch_ends reports where they started and stopped.  last_row() is a cost-only pass of its own that also stores row |b|.
 // The diagonal-transition route (run_dt, align_dt) is a unit of its own, affine_dt_unit.hip, which sees a batch through dt_view().
-// The plan, the chunking and the drivers of align() and align_tiled() are affine_host.hpp's, shared with the four-layer batch; this
-// unit gives them its records and launches (Host) and keeps what only two layers have: chaining, ends-free mode, last_row(), dt_view().
+// The plan, the chunking and the drivers of align() and align_tiled() are affine_host.hpp's and the chained route's host side is
+// affine_chain_host.hpp's, both shared with the four-layer batch; this unit gives them its records and launches (Host) and keeps what
+// only two layers have: ends-free mode, last_row(), dt_view().
 #include "engine.hpp"
 #include "affine_kernel.hpp"
-#include "affine_host.hpp"
-#include "affine_chain_plan.hpp"
+#include "affine_chain_host.hpp"
 #include "affine_dt_view.hpp"
 #include "../../include/pa_affine_hip.h"
 
@@ -34,7 +34,6 @@ using namespace pa::affine;
 namespace {
 
 constexpr uint32_t kMaxCost = 1000;
-constexpr size_t kStripRows = 64 * kRows;  // rows of one strip
 
 using Plan = affine_host::Plan<Pair, Wave>;
 
@@ -43,14 +42,7 @@ using Plan = affine_host::Plan<Pair, Wave>;
 struct pa_affine_batch : affine_host::Batch<Pair, Wave> {
     Costs C{};
     // The chained route (set_chain): the packed pairs keep a plan of their own, the others are listed in planner order.
-    struct {
-        bool on = false, built = false;
-        std::vector<uint32_t> ids;  // pairs with |b| > 1024, in planner order
-        Plan packed;                // the plan of the rest
-        DeviceBuf d_pairs;          // Pair of every id
-        DeviceBuf d_jobs, d_bnd, d_ticket_err;
-        double pairs = 0, jobs = 0, chunks = 0, bnd_bytes_max = 0;  // the last chained pass
-    } chain;
+    affine_host::ChainState<Plan> chain;
     // Ends-free mode (set_free_ends): the switches are C.ends, the kernels leave every pair's end in d_end.
     DeviceBuf d_end;
     struct {
@@ -84,6 +76,7 @@ struct Host {
     using WalkState = affine::WalkState;
     using TileJob = affine::TileJob;
     using TileWave = affine::TileWave;
+    using ChainJob = affine::ChainJob;
     // 8-byte boundary values (M | I << 32) and checkpoint rows (M | D << 32): a pair's checkpoints are whole 8-byte values as they are
     static constexpr affine_plan::Layout kLayout{kRows, 8, 8, 8};
     static constexpr const char* kName = "pa_affine_batch";
@@ -102,10 +95,19 @@ struct Host {
         return hip_ok(hipGetLastError(), "affine_walk_kernel launch");
     }
     static int64_t walk_start(const WalkOut& o) { return o.start; }
-    static void begin_tiled(Batch& ab) {  // the chain counters are those of the last chained pass
-        if (ab.chain.on) ab.chain.pairs = ab.chain.jobs = ab.chain.chunks = ab.chain.bnd_bytes_max = 0;
-    }
+    static void begin_tiled(Batch& ab) { affine_host::chain_begin(ab); }
     static int ckpt_pass(Batch& ab, affine_host::TiledChunk<Host>& ch, uint32_t C, hipStream_t s, float* ms);
+    // what affine_chain_host.hpp launches
+    static bool launch_ckpt(const Batch& ab, const Wave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s);
+    template <bool CKPT>
+    static bool launch_chain(const Batch& ab, const ChainJob* d_jobs, int njobs, const Pair* d_pairs, uint32_t tile_cols, uint32_t* ticket_err, hipStream_t s);
+    static bool launch_chain_run(const Batch& ab, const ChainJob* d_jobs, int njobs, const Pair* d_pairs, uint32_t* ticket_err, hipStream_t s) {
+        return launch_chain<false>(ab, d_jobs, njobs, d_pairs, 0, ticket_err, s);
+    }
+    static bool launch_chain_ckpt(const Batch& ab, const ChainJob* d_jobs, int njobs, const Pair* d_pairs, uint32_t tile_cols, uint32_t* ticket_err,
+                                  hipStream_t s) {
+        return launch_chain<true>(ab, d_jobs, njobs, d_pairs, tile_cols, ticket_err, s);
+    }
     static bool launch_tile_fill(const Batch& ab, const TileWave* d_waves, int nw, const TileJob* d_jobs, hipStream_t s);
     static bool launch_tile_walk(const Batch& ab, const TileJob* d_jobs, int nj, hipStream_t s) {
         hipLaunchKernelGGL(affine_tile_walk_kernel, dim3((nj + 63) / 64), dim3(64), 0, s, d_jobs, nj, (ab.C.ends & kFreeStart) ? 1 : 0);
@@ -155,103 +157,23 @@ bool Host::launch(const Batch& ab, const Plan& P, hipStream_t s) {
     return ::launch<FILL>(ab, P, s);
 }
 
-using affine_host::Events;
-
-// The device jobs of a chain plan, chunk after chunk, every chunk's rows at `rows`.  Pair p of the plan is pair at[p] of the kernel's Pair
-// array (p itself without `at`).
-std::vector<ChainJob> chain_jobs_of(const affine_chain::Plan& cp, const std::vector<affine_chain::Shape>& shapes, uint64_t* rows,
-                                    const std::vector<uint32_t>* at = nullptr) {
-    std::vector<ChainJob> jobs;
-    jobs.reserve(cp.jobs.size());
-    for (const affine_chain::Job& q : cp.jobs) {
-        const size_t S = affine_chain::strips_of(shapes[q.pair].m), w = affine_chain::row_words(shapes[q.pair].n);
-        uint64_t* row0 = rows + cp.row_off[q.pair];
-        ChainJob J;
-        J.pair = at ? (*at)[q.pair] : q.pair;
-        J.strip = q.strip;
-        J.bnd_in = q.strip ? row0 + (size_t)(q.strip - 1) * w : nullptr;
-        J.bnd_out = q.strip + 1 < S ? row0 + (size_t)q.strip * w : nullptr;
-        jobs.push_back(J);
-    }
-    return jobs;
+bool Host::launch_ckpt(const Batch& ab, const Wave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s) {
+    return ::launch<false, true>(ab, d_waves, nwaves, d_pairs, s);
 }
-
-// One chained pass, a launch per chunk of the plan: ticket and error word cleared and the chunk's rows (at `rows`) set to all-ones on the
-// stream, the kernel over the chunk's jobs at d_jobs (chain_jobs_of), and the copy of its error word to errs, for chain_check to read once
-// the stream is synchronised.  Counts the pass in chain.*.
+// affine_chain_kernel over one chunk's jobs (the chained route's host side is affine_chain_host.hpp's).
 template <bool CKPT>
-bool launch_chain(pa_affine_batch& ab, const affine_chain::Plan& cp, const ChainJob* d_jobs, const Pair* d_pairs, uint32_t tile_cols, void* rows,
-                  std::vector<uint32_t>& errs, hipStream_t s) {
-    uint32_t* te = ab.chain.d_ticket_err.as<uint32_t>();
-    errs.assign(cp.chunks.size(), 0);
-    for (size_t k = 0; k < cp.chunks.size(); ++k) {
-        const affine_chain::Chunk& c = cp.chunks[k];
-        if (!hip_ok(hipMemsetAsync(te, 0, 8, s), "hipMemsetAsync") || (c.words && !hip_ok(hipMemsetAsync(rows, 0xFF, c.words * 8, s), "hipMemsetAsync")))
-            return false;
-        const int grid = (int)((c.njobs + kBlockWaves - 1) / kBlockWaves);
-        if (ab.C.ends)
-            hipLaunchKernelGGL((affine_chain_kernel<CKPT, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs + c.first_job, (int)c.njobs, d_pairs, ab.C,
-                               tile_cols, te, ab.d_cost.as<int32_t>(), ends_of(ab));
-        else
-            hipLaunchKernelGGL((affine_chain_kernel<CKPT, false>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs + c.first_job, (int)c.njobs, d_pairs, ab.C,
-                               tile_cols, te, ab.d_cost.as<int32_t>(), Ends{});
-        if (!hip_ok(hipGetLastError(), CKPT ? "affine_chain_kernel<CKPT> launch" : "affine_chain_kernel launch") ||
-            !hip_ok(hipMemcpyAsync(&errs[k], te + 1, 4, hipMemcpyDeviceToHost, s), "D2H"))
-            return false;
-    }
-    ab.chain.pairs += (double)cp.row_off.size();
-    ab.chain.jobs += (double)cp.jobs.size();
-    ab.chain.chunks += (double)cp.chunks.size();
-    ab.chain.bnd_bytes_max = std::max(ab.chain.bnd_bytes_max, (double)cp.words_max * 8);
-    return true;
+bool Host::launch_chain(const Batch& ab, const ChainJob* d_jobs, int njobs, const Pair* d_pairs, uint32_t tile_cols, uint32_t* ticket_err, hipStream_t s) {
+    const int grid = (njobs + kBlockWaves - 1) / kBlockWaves;
+    if (ab.C.ends)
+        hipLaunchKernelGGL((affine_chain_kernel<CKPT, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs, njobs, d_pairs, ab.C, tile_cols, ticket_err,
+                           ab.d_cost.as<int32_t>(), ends_of(ab));
+    else
+        hipLaunchKernelGGL((affine_chain_kernel<CKPT, false>), dim3(grid), dim3(64 * kBlockWaves), 0, s, d_jobs, njobs, d_pairs, ab.C, tile_cols, ticket_err,
+                           ab.d_cost.as<int32_t>(), Ends{});
+    return hip_ok(hipGetLastError(), CKPT ? "affine_chain_kernel<CKPT> launch" : "affine_chain_kernel launch");
 }
 
-int chain_check(const char* fn, const std::vector<uint32_t>& errs) {
-    uint32_t err = 0;
-    for (const uint32_t e : errs)
-        if (e) err = e;
-    if (!err) return 0;
-    return fail(PA_E_INTERNAL, "%s: chained route: a strip never received its boundary row (device spin timeout, err=%u); no result of this call is valid", fn,
-                err);
-}
-
-// What set_chain(1) needs once: the chained pairs, their Pair array and the plan of the packed rest.
-int chain_build(pa_affine_batch& ab, hipStream_t s) {
-    if (ab.chain.built) return 0;
-    std::vector<uint32_t> rest;
-    ab.chain.ids.clear();  // (an earlier attempt may have failed half-way)
-    for (const uint32_t p : ab.order) (ab.m[p] > kStripRows ? ab.chain.ids : rest).push_back(p);
-    std::vector<Pair> pairs;
-    for (const uint32_t p : ab.chain.ids) pairs.push_back(affine_host::make_pair<Host>(ab, p, (uint32_t)affine_plan::rows_of(Host::kLayout, ab.m[p])));
-    if (!upload(ab.chain.d_pairs, pairs.data(), pairs.size() * sizeof(Pair), s) || !ab.chain.d_ticket_err.alloc(16)) return PA_E_HIP;
-    if (!ab.chain.ids.empty())  // (without chained pairs run() keeps the batch's own plan)
-        if (const int rc = affine_host::make_plan<Host>(ab, rest, ab.chain.packed, affine_host::Keep::kNone, nullptr, s)) return rc;
-    if (!hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
-    ab.chain.built = true;
-    return 0;
-}
-
-// run() with chaining on and pairs to chain: the packed pairs' launch, then the chained pairs in chunks whose boundary rows fit the budget.
-int run_chained(pa_affine_batch& ab, Events& ev, hipStream_t s) {
-    std::vector<affine_chain::Shape> shapes;
-    for (const uint32_t p : ab.chain.ids) shapes.push_back(affine_chain::Shape{ab.n[p], ab.m[p]});
-    const size_t budget = trace_budget("PA_AFFINE_TRACE_BUDGET_MB");
-    const affine_chain::Plan cp = affine_chain::plan(shapes, budget);
-    if (cp.refused >= 0)
-        return fail(PA_E_ARG, "pa_affine_batch_run: pair %u: %zu bytes of boundary rows of the chained route exceed the budget of %zu bytes",
-                    ab.chain.ids[(size_t)cp.refused], affine_chain::pair_words(shapes[(size_t)cp.refused]) * 8, budget);
-    if (!ab.chain.d_bnd.reserve(std::max<size_t>(cp.words_max * 8, 16))) return PA_E_HIP;
-    const std::vector<ChainJob> jobs = chain_jobs_of(cp, shapes, ab.chain.d_bnd.as<uint64_t>());
-    std::vector<uint32_t> errs;
-    if (!ab.chain.d_jobs.reserve(jobs.size() * sizeof(ChainJob)) ||
-        !hip_ok(hipMemcpyAsync(ab.chain.d_jobs.ptr, jobs.data(), jobs.size() * sizeof(ChainJob), hipMemcpyHostToDevice, s), "H2D") ||
-        !hip_ok(hipStreamSynchronize(s), "sync") ||  // (jobs is pageable memory of this call)
-        !hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(ab, ab.chain.packed, s) ||
-        !launch_chain<false>(ab, cp, ab.chain.d_jobs.as<ChainJob>(), ab.chain.d_pairs.as<Pair>(), 0, ab.chain.d_bnd.ptr, errs, s) ||
-        !hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync"))
-        return PA_E_HIP;
-    return chain_check("pa_affine_batch_run", errs);
-}
+using affine_host::Events;
 
 // Every pair's end after an ends-free pass (global mode: |a|, without a copy).
 int fetch_ends(const pa_affine_batch& ab, std::vector<int32_t>& end, hipStream_t s) {
@@ -325,9 +247,9 @@ extern "C" int pa_affine_batch_run(pa_affine_batch* ab, int32_t* cost_out, float
     if (ab->np == 0) return costs_out(*ab, cost_out, s);  // (nothing to copy: the call counts for pa_affine_batch_ends)
     Events ev;
     if (!ev.make()) return PA_E_HIP;
-    if (ab->chain.on) ab->chain.pairs = ab->chain.jobs = ab->chain.chunks = ab->chain.bnd_bytes_max = 0;
+    affine_host::chain_begin(*ab);
     if (ab->chain.on && !ab->chain.ids.empty()) {
-        if (const int rc = run_chained(*ab, ev, s)) return rc;
+        if (const int rc = affine_host::run_chained<Host>(*ab, ev, s)) return rc;
     } else if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(*ab, ab->fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event"))
         return PA_E_HIP;
     if (const int rc = costs_out(*ab, cost_out, s)) return rc;
@@ -343,44 +265,9 @@ namespace {
 
 // The checkpoint pass of a chunk of align_tiled; with a free end every walk then starts at (end, m, main).
 int Host::ckpt_pass(pa_affine_batch& ab, affine_host::TiledChunk<Host>& ch, uint32_t C, hipStream_t s, float* ms) {
-    Plan& P = ch.plan;
+    if (const int rc = affine_host::ckpt_pass<Host>(ab, ch, C, s, ms)) return rc;
+    const Plan& P = ch.plan;
     const size_t np = P.pairs.size();
-    Events ev;
-    if (!ev.make()) return PA_E_HIP;
-    DeviceBuf d_pwaves, d_cjobs;  // chained: the plan's one-strip waves, and the chain jobs of the others
-    const Wave* d_waves = P.d_waves.as<Wave>();
-    size_t nwaves = P.waves.size();
-    affine_chain::Plan cp;
-    if (ab.chain.on) {  // the strip pairs leave the plan's launch for the chained one; their rows stay where make_plan put them
-        std::vector<Wave> one;
-        std::vector<affine_chain::Shape> shapes;
-        std::vector<uint32_t> at;  // index into P.pairs
-        for (const Wave& W : P.waves)
-            if (W.strips == 1) one.push_back(W);
-        for (size_t k = 0; k < np; ++k)  // (P.pairs keeps the order of ids; the waves are sorted by cost)
-            if (P.pairs[k].m > kStripRows) {
-                shapes.push_back(affine_chain::Shape{P.pairs[k].n, P.pairs[k].m});
-                at.push_back((uint32_t)k);
-            }
-        cp = affine_chain::plan(shapes, SIZE_MAX);  // (this chunk was cut by tiled_bytes_of, which counts the rows)
-        for (size_t x = 0; x < shapes.size(); ++x)
-            if (cp.chunks.size() != 1 || ch.rowck[at[x]] != P.d_bnd.as<uint8_t>() + cp.row_off[x] * 8 || cp.words_max != P.at.bnd_vals)
-                return fail(PA_E_INTERNAL, "pa_affine_batch_align_tiled: chained route: the planner and the checkpoint plan disagree on pair %u's rows",
-                            P.pairs[at[x]].out);
-        const std::vector<ChainJob> cjobs = chain_jobs_of(cp, shapes, P.d_bnd.as<uint64_t>(), &at);
-        if (!upload(d_pwaves, one.data(), one.size() * sizeof(Wave), s) || !upload(d_cjobs, cjobs.data(), cjobs.size() * sizeof(ChainJob), s) ||
-            !hip_ok(hipStreamSynchronize(s), "sync"))
-            return PA_E_HIP;
-        d_waves = d_pwaves.as<Wave>();
-        nwaves = one.size();
-    }
-    std::vector<uint32_t> errs;
-    if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !::launch<false, true>(ab, d_waves, nwaves, P.d_pairs.as<Pair>(), s) ||
-        !launch_chain<true>(ab, cp, d_cjobs.as<ChainJob>(), P.d_pairs.as<Pair>(), C, P.d_bnd.ptr, errs, s) ||
-        !hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync") ||
-        !hip_ok(hipEventElapsedTime(ms, ev.e[0], ev.e[1]), "hipEventElapsedTime"))
-        return PA_E_HIP;
-    if (const int rc = chain_check("pa_affine_batch_align_tiled", errs)) return rc;
     if (ab.C.ends & kFreeEnd) {  // every walk starts at (end, m, main), the end the checkpoint pass found
         std::vector<int32_t> end;
         if (const int rc = fetch_ends(ab, end, s)) return rc;
@@ -410,12 +297,7 @@ extern "C" void pa_affine_batch_tiled_info(const pa_affine_batch* ab, double* ch
 }
 
 extern "C" int pa_affine_batch_set_chain(pa_affine_batch* ab, int on) {
-    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_set_chain: NULL batch");
-    if (on != 0 && on != 1) return fail(PA_E_ARG, "pa_affine_batch_set_chain: on = %d is neither 0 nor 1", on);
-    if (on)
-        if (const int rc = chain_build(*ab, 0)) return rc;
-    ab->chain.on = on != 0;
-    return 0;
+    return affine_host::set_chain<Host>(ab, on);
 }
 
 extern "C" int pa_affine_batch_set_free_ends(pa_affine_batch* ab, int free_start, int free_end) {
@@ -481,11 +363,7 @@ extern "C" int pa_affine_batch_last_row(pa_affine_batch* ab, int32_t* out, const
 
 extern "C" void pa_affine_batch_chain_info(const pa_affine_batch* ab, double* on, double* chain_pairs, double* chain_jobs, double* chunks,
                                            double* bnd_bytes_max) {
-    if (on) *on = ab && ab->chain.on ? 1 : 0;
-    if (chain_pairs) *chain_pairs = ab ? ab->chain.pairs : 0;
-    if (chain_jobs) *chain_jobs = ab ? ab->chain.jobs : 0;
-    if (chunks) *chunks = ab ? ab->chain.chunks : 0;
-    if (bnd_bytes_max) *bnd_bytes_max = ab ? ab->chain.bnd_bytes_max : 0;
+    affine_host::chain_info(ab, on, chain_pairs, chain_jobs, chunks, bnd_bytes_max);
 }
 
 extern "C" void pa_affine_batch_info(const pa_affine_batch* ab, double* waves, double* packed_pairs, double* strip_pairs, double* lane_use,

@@ -13,9 +13,10 @@
  * layers: open before extend), printed as AffineCigar::to_string() (= X I D, the affine ops of every layer as I / D, the count left out
  * when 1).  Ops of different layers, and linear against affine, stay separate elements (push_op merges equal ops only).
  *
- * The tiled traceback, pa_affine4_batch_align in bounded device memory, is declared in pa_affine4_tiled_hip.h.  Not here
- * (pa_affine_hip.h has them for the models with at most two layers): ends-free mode, chained strips, every diagonal-transition
- * route, and layer lists other than [insert, delete, insert, delete].
+ * The tiled traceback, pa_affine4_batch_align in bounded device memory, is declared in pa_affine4_tiled_hip.h, and chained strips (a
+ * wavefront per strip of a long pair, in run and in the tiled traceback's checkpoint pass) in pa_affine4_chain_hip.h.  Not supported
+ * (pa_affine_hip.h has them for the models with at most two layers): ends-free mode, every diagonal-transition route, and layer lists
+ * other than [insert, delete, insert, delete].
  *
  * Errors follow pa_bitpacking_hip.h: 0 or a negative PA_E_* code, pa_last_error() for the message.
  */

@@ -2,7 +2,7 @@
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
     python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
-                                 [--dt-seg] [--double] [--double-tiled] [--models affine,unit]
+                                 [--dt-seg] [--double] [--double-tiled] [--double-chain] [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
 tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
@@ -45,7 +45,13 @@ does the same on --trace-pairs of the 10 kbp pairs.
 align() and align_tiled() alternating on one batch of --trace-pairs of them, each warmed once and then three times, the fastest repeat
 of each, their ratio, and the results compared in every round; then align_tiled() alone on all 4096 pairs, and on 16 pairs of 100 kbp
 (once, unwarmed, in a process of its own under a time limit of two lone-wavefront passes).  Every leg prints tiled_info(): chunks,
-rounds, tile jobs, the cells re-filled and the bytes of the largest chunk, also per pair."""
+rounds, tile jobs, the cells re-filled and the bytes of the largest chunk, also per pair.
+
+--double-chain is --chain's protocol on an Affine4Batch under double_affine(4, 6, 2, 24, 1) (Affine4Batch.set_chain), whatever --shapes
+says: one 100 kbp pair, 16 of them, 4096 x 10 kbp and the reads (which have no pair to chain), with the long indels of --double.  Cost
+only, the tiled forward pass and traced in all, chained and unchained alternating on one batch, each warmed once and then R times, the
+results compared in every round.  Every shape runs in a process of its own under a wall-clock limit sized for its unchained passes (a
+100 kbp pair alone on a wavefront takes 7 to 10 s a pass)."""
 from __future__ import annotations
 
 import argparse
@@ -270,15 +276,15 @@ def double_tiled_leg(title, tp, untiled, tile_cols, warm=True, reps=3):
     return t
 
 
-# The 100 kbp leg of --double-tiled: a pair's checkpoint pass runs on one wavefront (no chained strips in the four-layer route), about 7 s
+# The 100 kbp leg of --double-tiled: a pair's checkpoint pass runs on one wavefront (chaining is off by default; --double-chain measures it on), about 7 s
 # for the two-layer kernel times the four-layer ratio of 1.3; the limit is two such passes.
 DOUBLE_100K_LIMIT_S = 2 * 7.0 * 1.3
 
 
-def chain_legs(title, pairs, cm, mname, tile_cols, reps):
+def chain_legs(title, pairs, cm, mname, tile_cols, reps, Batch=AffineBatch):
     """Chaining off and on, alternating on one traced batch: run() and align_tiled()."""
     cells = float(sum(len(x) * len(y) for x, y in pairs))
-    b = AffineBatch(pairs, cm, trace=True)
+    b = Batch(pairs, cm, trace=True)
     cost = {False: [], True: []}
     tiled = {False: [], True: []}
     results = {}
@@ -294,7 +300,7 @@ def chain_legs(title, pairs, cm, mname, tile_cols, reps):
                 raise SystemExit(f"{title} {mname}: the chained and the unchained route disagree")
             if rep:
                 cost[on].append(k)
-                tiled[on].append((b.last_forward_ms, b.last_refill_ms, b.last_trace_ms))
+                tiled[on].append((b.last_forward_ms, b.last_refill_ms, getattr(b, b._WALK_MS)))
     ci = b.chain_info()
     b.close()
     k0, k1 = min(cost[False]), min(cost[True])
@@ -306,6 +312,15 @@ def chain_legs(title, pairs, cm, mname, tile_cols, reps):
           f"  (fills {r1:.2f} ms, walks {w1:.2f} ms; repeats {' '.join(f'{sum(x):.2f}' for x in tiled[False])} |"
           f" {' '.join(f'{sum(x):.2f}' for x in tiled[True])})", flush=True)
     print(f"{'':44s} {mname:14s} chain_info: {ci}", flush=True)
+
+
+# --double-chain: a shape's process may take its pairs (a minute of Python at most) and, per round, four passes (run() and align_tiled(),
+# unchained and chained) of which the two unchained ones are lone-wavefront passes.
+DOUBLE_CHAIN_SHAPES = ("100k1", "100k", "10k", "reads")
+
+
+def double_chain_limit_s(reps):
+    return 60 + (reps + 1) * 2 * DOUBLE_100K_LIMIT_S
 
 
 def dt_legs(title, pairs, cm, mname, chain):
@@ -496,6 +511,8 @@ def main():
     ap.add_argument("--double", action="store_true", help="measure Affine4Batch under double_affine against AffineBatch under affine instead (see above)")
     ap.add_argument("--double-tiled", action="store_true", help="measure Affine4Batch.align_tiled() against Affine4Batch.align() instead (see above)")
     ap.add_argument("--double-tiled-100k", action="store_true", help=argparse.SUPPRESS)  # the 100 kbp leg of --double-tiled, in a process of its own
+    ap.add_argument("--double-chain", action="store_true", help="measure Affine4Batch's chained route against its unchained one instead (see above)")
+    ap.add_argument("--double-chain-shape", default="", help=argparse.SUPPRESS)  # one shape of --double-chain, in a process of its own
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -504,6 +521,22 @@ def main():
     rng = np.random.default_rng(1)
     models = {"affine(4,6,2)": AffineCost.affine(4, 6, 2), "unit()": AffineCost.unit()}
     models = {k: v for k, v in models.items() if k.split("(")[0] in args.models.split(",")}
+    if args.double_chain_shape:
+        rng = np.random.default_rng(2)
+        title, pairs = shape(args.double_chain_shape, rng)
+        chain_legs(title + ", indels in a quarter", long_indels(rng, pairs), AffineCost.double_affine(4, 6, 2, 24, 1), "double_affine", args.tile_cols,
+                   args.reps, Affine4Batch)
+        return
+    if args.double_chain:
+        for sname in DOUBLE_CHAIN_SHAPES:
+            cmd = [sys.executable, str(Path(__file__).resolve()), "--double-chain-shape", sname, "--tile-cols", str(args.tile_cols), "--reps", str(args.reps)]
+            try:
+                rc = subprocess.run(cmd, timeout=double_chain_limit_s(args.reps)).returncode
+            except subprocess.TimeoutExpired:
+                raise SystemExit(f"{sname}: no result within {double_chain_limit_s(args.reps):.0f} s")
+            if rc:  # (nothing more is started after a failure)
+                raise SystemExit(rc)
+        return
     if args.double_tiled_100k:
         title, pairs = shape("100k", np.random.default_rng(2))
         t = double_tiled_leg(title + ", indels of 20-200 bp in a quarter", long_indels(rng, pairs), False, args.tile_cols, warm=False, reps=1)
