@@ -2,7 +2,8 @@
 // with |b| > 64 kRows is a job of its own, run by its own wavefront, the strips of a pair side by side, strip s + 1 a few dozen columns
 // behind strip s.  The design is affine_chain_kernel's (affine_kernel.hpp); the recurrence, the lane layout (kRows rows per lane, M, D1,
 // D2 per row, M, I1, I2 and the byte of a handed down by dpp_wave_shr1), the row-0 recurrence on strip 0 and the unpredicated steps with
-// guarded stores are affine4_kernel<false>'s, step for step.  A template, so that each unit instantiates what it launches:
+// guarded stores are affine4_kernel<false>'s: the same rows_step, and row0_step, of affine4_common.hpp.  A template, so that each
+// unit instantiates what it launches:
 // affine4_unit.hip the cost-only pass of run(), affine4_tiled_unit.hip the checkpoint pass of align_tiled().
 //   * Jobs.  A wavefront claims job `ticket++` when it starts.  The host lists every pair's strips 0, 1, .. S - 1 next to each other in
 //     that order (affine_chain_plan.hpp), so the producer of a job holds the ticket just below it.  A ticket is only ever taken by a
@@ -22,8 +23,9 @@
 //     wall clock.
 //   * Bounded wait.  On a timeout the wavefront sets the launch's error word and leaves; every poll also reads that word and leaves when
 //     it is set, so one lost producer ends the launch after one timeout.  The host then reports PA_E_INTERNAL and no result is valid.
-// CKPT stores the column checkpoints of the strip's own rows exactly as affine4_ckpt_kernel does (same columns, same layout, row 0's by
-// strip 0); the boundary rows are the row checkpoints, so affine4_tile_kernel and affine4_tile_walk_kernel read both unchanged.
+// CKPT stores the column checkpoints of the strip's own rows as affine4_ckpt_kernel's store_col_ckpt does (same columns, same layout,
+// row 0's by strip 0; written out here, see ck_word); the boundary rows are the row checkpoints, so affine4_tile_kernel and
+// affine4_tile_walk_kernel read both unchanged.
 // (chain_wait and ChainJob of affine_kernel.hpp are restated here: that header also defines the two-layer walk kernels, which must stay
 // in one unit.)
 #pragma once
@@ -68,6 +70,13 @@ static __device__ __attribute__((noinline)) affine4_chain::Halves chain4_wait(co
         const uint32_t naps = spins < 8u ? 1u : (spins < 64u ? 4u : 16u);  // resolve_granule's back-off
         for (uint32_t k = 0; k < naps; ++k) __builtin_amdgcn_s_sleep(8);
     }
+}
+
+// Word q of a lane's checkpoint rows: {M, D1, D2} of row q / 3.  CKPT keeps store_col_ckpt's stores in its body, with this select:
+// called, the kernel loses the register tuples it holds Mp / D1p / D2p in ready for the twelve stores (128 VGPRs for 100, 48 moves
+// before them) and the chained checkpoint pass of 4096 x 10 kbp took 304 to 307 ms for 298 (2 %) in every process of four variants.
+__device__ __forceinline__ uint32_t ck_word(const uint32_t (&Mp)[kRows], const uint32_t (&D1p)[kRows], const uint32_t (&D2p)[kRows], int q) {
+    return q % 3 == 0 ? Mp[q / 3] : q % 3 == 1 ? D1p[q / 3] : D2p[q / 3];
 }
 
 // ticket_err[0]: the job ticket, ticket_err[1]: the error word; both zero at launch.  tile_cols: CKPT only.
@@ -155,15 +164,12 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_chain_kernel(const C
                 fM = (uint32_t)__builtin_amdgcn_readlane((int)curM, u);
                 fI1 = (uint32_t)__builtin_amdgcn_readlane((int)curI1, u);
                 fI2 = (uint32_t)__builtin_amdgcn_readlane((int)curI2, u);
-            } else {  // row 0 of column t, the same in every lane: the delete layers and the linear deletion
-                const uint32_t d1o = r0M + C.oe[1], d2o = r0M + C.oe[3], cdl = r0M + C.del;
-                const uint32_t D1 = umin3(d1o, r0D1 + C.e[1], kInf);
-                const uint32_t D2 = umin3(d2o, r0D2 + C.e[3], kInf);
-                const uint32_t M = t == 0 ? 0u : umin(umin3(cdl, D1, D2), kInf);
-                r0M = M;
-                r0D1 = D1;
-                r0D2 = D2;
-                fM = M;
+            } else {  // row 0 of column t, the same in every lane
+                const Row0 R = row0_step(C, r0M, r0D1, r0D2, t == 0);
+                r0M = R.M;
+                r0D1 = R.D1;
+                r0D2 = R.D2;
+                fM = R.M;
                 fI1 = kInf;
                 fI2 = kInf;
             }
@@ -174,32 +180,15 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_chain_kernel(const C
             uint32_t Mdiag = topPrev;
             topPrev = inM;
             uint32_t Mup = inM, I1up = inI1, I2up = inI2;
-#pragma unroll
-            for (int k = 0; k < kRows; ++k) {
-                const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
-                const uint32_t i1o = Mup + C.oe[0], i2o = Mup + C.oe[2];
-                const uint32_t I1 = umin(i1o, I1up + C.e[0]);
-                const uint32_t I2 = umin(i2o, I2up + C.e[2]);
-                const uint32_t d1o = Mp[k] + C.oe[1], d2o = Mp[k] + C.oe[3];
-                const uint32_t D1 = umin(d1o, D1p[k] + C.e[1]);
-                const uint32_t D2 = umin(d2o, D2p[k] + C.e[3]);
-                const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del;
-                const uint32_t M = umin(umin(umin3(cd, ci, cdl), umin3(I1, D1, I2)), umin(D2, kInf));
-                Mdiag = Mp[k];
-                Mp[k] = M;
-                D1p[k] = D1;
-                D2p[k] = D2;
-                Mup = M;
-                I1up = I1;
-                I2up = I2;
-            }
+            rows_step(C, bk, Mp, D1p, D2p, inC, Mdiag, Mup, I1up, I2up);
             if (active) {
                 if (last && bout) {  // the two halves of column i, in no particular order
                     const Halves w = affine4_chain::pack(Mup, I1up, I2up);
                     __hip_atomic_store(bout + 2 * (size_t)i, w.lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(bout + 2 * (size_t)i + 1, w.hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                if (CKPT && i == ck_col && kck > 0 && i < n) {  // lanes reach the column at different steps: each stores its own rows
+                // store_col_ckpt, written out (see ck_word): lanes reach the column at different steps, each stores its own rows
+                if (CKPT && i == ck_col && kck > 0 && i < n) {
                     PA_GLOBAL u32x4* const dst = (PA_GLOBAL u32x4*)(ck + ((size_t)(kck - 1) * P.H + j0) * kCkWords);
 #pragma unroll
                     for (int q = 0; q < kCkVecs; ++q) {
@@ -214,12 +203,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_chain_kernel(const C
                         row0[2] = r0D2;
                     }
                 }
-                if (i == n && m > j0 && m <= j0 + kRows) {
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
-                    out[P.out] = (int32_t)v;
-                }
+                if (i == n && m > j0 && m <= j0 + kRows) out[P.out] = (int32_t)row_m_of(Mp, m, j0);
             }
             outM = Mup;
             outI1 = I1up;

@@ -34,11 +34,19 @@
 // Codes of rows 1 .. H of column i at codes[i H + j - 1], row 0 at codes[(n + 1) H + i]; the kRows bytes of a lane and step go out as
 // one store.  affine4_walk_kernel walks them backwards from (n, m, main) to (0, 0, main).
 //
+// The cost-only instance takes its row loop from affine4_common.hpp (rows_step), as the checkpoint pass and the chained kernel do, and
+// affine4_walk_kernel its step (walk_step).  The loop with the code byte, row 0 with its byte and the cost pick stand in this kernel's
+// body and, the same text, in affine4_tile_kernel's.  Called (rows_step<FILL> with the byte and its pin, row0_step returning the byte,
+// row_m_of), on one MI355X against the written-out form built twice, six processes: run() of 4096 x 10 kbp 264.2 ms for 262.6 to
+// 263.2 (1083 instructions for 1145), the forward pass of align() on 512 of them 189.2 ms for 188.4 to 188.9 (1352 for 1348), the
+// tile fills of 4096 x 10 kbp 109.2 ms for 108.5 to 108.9 (1361 for 1357); with only rows_step<true> called both FILL kernels are
+// those four instructions longer.  A change to the recurrence or the code byte is made in rows_step, here and in affine4_tile_kernel.
+//
 // The tiled traceback (align_tiled) has its kernels in affine4_tile_kernel.hpp, in a unit of their own, and the chained route (set_chain:
 // the strips of a longer pair on a wavefront each, side by side) its kernel in affine4_chain_kernel.hpp.  Global mode only.  Not
 // supported: ends-free mode, diagonal transition, other layer lists.
 #pragma once
-#include "affine4_common.hpp"  // constants, Costs, Pair, Wave, layer_op: shared with affine4_tile_kernel.hpp
+#include "affine4_common.hpp"  // constants, Costs, Pair, Wave; rows_step, walk_step
 
 namespace pa {
 namespace affine4 {
@@ -132,18 +140,18 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* _
             uint32_t code[kRows / 4];  // FILL: the step's code bytes
 #pragma unroll
             for (int k = 0; k < kRows / 4; ++k) code[k] = 0;
+            if (FILL) {  // rows_step with the code byte, written out: see the note at the top
 #pragma unroll
-            for (int k = 0; k < kRows; ++k) {
-                const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
-                const uint32_t i1o = Mup + C.oe[0], i2o = Mup + C.oe[2];
-                const uint32_t I1 = umin(i1o, I1up + C.e[0]);
-                const uint32_t I2 = umin(i2o, I2up + C.e[2]);
-                const uint32_t d1o = Mp[k] + C.oe[1], d2o = Mp[k] + C.oe[3];
-                const uint32_t D1 = umin(d1o, D1p[k] + C.e[1]);
-                const uint32_t D2 = umin(d2o, D2p[k] + C.e[3]);
-                const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del;
-                const uint32_t M = umin(umin(umin3(cd, ci, cdl), umin3(I1, D1, I2)), umin(D2, kInf));
-                if (FILL) {
+                for (int k = 0; k < kRows; ++k) {
+                    const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
+                    const uint32_t i1o = Mup + C.oe[0], i2o = Mup + C.oe[2];
+                    const uint32_t I1 = umin(i1o, I1up + C.e[0]);
+                    const uint32_t I2 = umin(i2o, I2up + C.e[2]);
+                    const uint32_t d1o = Mp[k] + C.oe[1], d2o = Mp[k] + C.oe[3];
+                    const uint32_t D1 = umin(d1o, D1p[k] + C.e[1]);
+                    const uint32_t D2 = umin(d2o, D2p[k] + C.e[3]);
+                    const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del;
+                    const uint32_t M = umin(umin(umin3(cd, ci, cdl), umin3(I1, D1, I2)), umin(D2, kInf));
                     uint32_t c = M == I2 ? 5u : 6u;
                     c = M == D1 ? 4u : c;
                     c = M == I1 ? 3u : c;
@@ -159,14 +167,16 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* _
                     // spilled to AGPRs.  With each row's byte pinned where it is computed: 136 VGPRs, none spilled.
                     asm volatile("" : "+v"(c));
                     code[k >> 2] |= c << (8 * (k & 3));
+                    Mdiag = Mp[k];
+                    Mp[k] = M;
+                    D1p[k] = D1;
+                    D2p[k] = D2;
+                    Mup = M;
+                    I1up = I1;
+                    I2up = I2;
                 }
-                Mdiag = Mp[k];
-                Mp[k] = M;
-                D1p[k] = D1;
-                D2p[k] = D2;
-                Mup = M;
-                I1up = I1;
-                I2up = I2;
+            } else {
+                rows_step(C, bk, Mp, D1p, D2p, inC, Mdiag, Mup, I1up, I2up);
             }
             if (active) {
                 if (FILL) {  // one store of kRows bytes
@@ -199,8 +209,8 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* _
 }
 
 // One traceback (AffineNwFronts::trace): from (n, m, main) back to (0, 0, main), the first matching parent of every state as the FILL
-// codes recorded it.  ops[] receives the steps from the end backwards: '=', 'X', 'I', 'D' (linear), and kLayerOp[k] for a step inside
-// layer k, so that the host can keep the gaps of different layers apart before it prints them as I / D.
+// codes recorded it (walk_step).  ops[] receives the steps from the end backwards: '=', 'X', 'I', 'D' (linear), and layer_op(k) for a
+// step inside layer k, so that the host can keep the gaps of different layers apart before it prints them as I / D.
 struct Walk {
     const uint8_t* a;
     const uint8_t* b;
@@ -224,52 +234,9 @@ __global__ __launch_bounds__(64) void affine4_walk_kernel(const Walk* __restrict
     WalkOut o;
     o.status = 0;
     o.nops = 0;
-    auto emit = [&](uint8_t op) {
-        if ((uint32_t)o.nops < Q.cap) Q.ops[o.nops] = op;
-        ++o.nops;
-    };
     while (o.status == 0 && !(i == 0 && j == 0 && layer == 0)) {
         const uint32_t c = j > 0 ? Q.codes[(size_t)i * Q.H + (size_t)(j - 1)] : Q.codes[row0 + (size_t)i];
-        if (layer == 0) {
-            const uint32_t p = c & 7u;
-            if (p == 0) {
-                if (i == 0 || j == 0) o.status = 1;
-                else {
-                    emit(Q.a[i - 1] == Q.b[j - 1] ? '=' : 'X');
-                    --i;
-                    --j;
-                }
-            } else if (p == 1) {
-                if (j == 0) o.status = 1;
-                else {
-                    emit('I');
-                    --j;
-                }
-            } else if (p == 2) {
-                if (i == 0) o.status = 1;
-                else {
-                    emit('D');
-                    --i;
-                }
-            } else if (p <= 6) {
-                layer = (int)p - 2;
-            } else {
-                o.status = 1;
-            }
-        } else {
-            const int k = layer - 1;
-            if (k & 1) {  // delete layer
-                if (i == 0) o.status = 1;
-                else --i;
-            } else {
-                if (j == 0) o.status = 1;
-                else --j;
-            }
-            if (o.status == 0) {
-                emit(layer_op(k));
-                if (!(c & (8u << k))) layer = 0;
-            }
-        }
+        walk_step(c, Q, i, j, layer, o.nops, o.status);
     }
     if (o.status == 0 && (uint32_t)o.nops > Q.cap) o.status = 2;
     outs[t] = o;

@@ -1,18 +1,18 @@
 // affine4_tile_kernel.hpp -- the device side of the tiled traceback of the batched double-affine alignment
 // (pa_affine4_batch_align_tiled, affine4_tiled_unit.hip): affine_kernel.hpp's tiled route (affine_kernel<false, true>, affine_tile_kernel,
-// affine_tile_walk_kernel), restated for the recurrence, the code byte and the walk of affine4_kernel.hpp: three values per row and per
-// boundary column, five walk layers.
+// affine_tile_walk_kernel) around the recurrence and the code byte of the double-affine batch (the checkpoint pass through affine4_common.hpp's
+// rows_step, row0_step and store_col_ckpt): three values per row and per boundary column, five walk layers.
 //
 // Tiles: row tile rt of a state (i, j) is 0 for j = 0, else (j - 1) / (64 kRows), i.e. the strip that owns row j (the one row tile of a
 // packed pair, its segment of H = g kRows rows); column tile ct is 0 for i = 0, else (i - 1) / C with C = tile_cols.
 //
-//   1. affine4_ckpt_kernel: the cost-only recurrence of affine4_kernel<false>, step for step, which also keeps
+//   1. affine4_ckpt_kernel: the cost-only pass of affine4_kernel<false> (rows_step, row0_step), which also keeps
 //        * the row checkpoints: the 16-byte boundary row {M, I1, I2, 0} of every strip but the last, strip s at bnd + s (nmax + 1);
 //        * the column checkpoints, in Pair::codes as 12-byte values {M, D1, D2} (uint32 each): after columns C, 2C, .. < n, checkpoint
 //          k = 0 .. K - 1 (column (k + 1) C, K = (n - 1) / C) of row j = 1 .. H at byte 12 (k H + j - 1), then row 0's at byte
 //          12 (K H + k).  A lane's kRows rows are 12 kRows contiguous bytes, stored as 16-byte values when its own column gets there.
 //      A pair's column checkpoints are K (H + 1) 12 bytes, rounded up to 16.
-//   2. affine4_tile_kernel: the FILL recurrence of affine4_kernel<true> (same code byte, same first-parent order, same pin per row) over
+//   2. affine4_tile_kernel: the FILL recurrence of affine4_kernel<true> (same code byte, same first-parent order, same pin per row; see there) over
 //      the rows of strip rt and the columns cs .. c1, where c0 = ct C, cs = c0 + 1 (0 for c0 = 0: column 0 is a border of column tile 0)
 //      and c1 is the column at which the walk entered the tile.  The state to the left comes from the column checkpoint at c0 (kInf in
 //      column tile 0), the row above from the row checkpoint of strip rt - 1 or, on strip 0, from the row-0 recurrence restarted at its
@@ -29,25 +29,16 @@
 namespace pa {
 namespace affine4 {
 
-// (kCkWords, kCkVecs and ck_word, the column checkpoint of one lane, are affine4_common.hpp's: affine4_chain_kernel<true> stores them too.)
-
-// One wavefront of the checkpoint pass: Wave with the tile width, and every strip's boundary row kept.
-struct CkWave {
-    uint32_t first, np, lg, strips;
-    uint32_t nmax;       // longest a of the wave
-    uint32_t tile_cols;  // columns between two column checkpoints
-    u32x4* bnd;          // strips > 1: strips - 1 rows of nmax + 1 boundary values {M, I1, I2, 0}
-};
-static_assert(sizeof(CkWave) == 32, "CkWave layout");
-
 // Four wavefronts per SIMD, the cost kernel's occupancy, asked for in the launch bounds: left to itself the compiler takes 131
-// registers for this kernel (three wavefronts); told the target it fits 127, without scratch or AGPRs.
-__global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const CkWave* __restrict__ waves, int nwaves, const Pair* __restrict__ pairs,
+// registers for this kernel (three wavefronts); told the target it fits 127, without scratch or AGPRs.  That leaves no register to
+// spare, so the final-cost pick stays written out: with row_m_of called, as affine4_chain_kernel has it,
+// it compiles to 128 VGPRs and 76 bytes of scratch (19 values spilled) in every form of the helper tried.
+__global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const Wave* __restrict__ waves, int nwaves, const Pair* __restrict__ pairs,
                                                                         Costs C, int32_t* __restrict__ cost_out) {
     const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
     if (wave >= nwaves) return;
     const int lane = (int)(threadIdx.x & 63);
-    const CkWave W = waves[wave];
+    const Wave W = waves[wave];
     const int g = 1 << W.lg;
     const int seg = lane >> W.lg, r = lane & (g - 1);
     const bool present = (uint32_t)seg < W.np;
@@ -108,15 +99,12 @@ __global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const
             uint32_t inC = dpp_wave_shr1(0x100u, outC);
             if (first) {
                 inC = nextC;
-                if (top) {  // row 0: the delete layers and the linear deletion
-                    const uint32_t d1o = r0M + C.oe[1], d2o = r0M + C.oe[3], cdl = r0M + C.del;
-                    const uint32_t D1 = umin3(d1o, r0D1 + C.e[1], kInf);
-                    const uint32_t D2 = umin3(d2o, r0D2 + C.e[3], kInf);
-                    const uint32_t M = t == 0 ? 0u : umin(umin3(cdl, D1, D2), kInf);
-                    r0M = M;
-                    r0D1 = D1;
-                    r0D2 = D2;
-                    inM = M;
+                if (top) {
+                    const Row0 R = row0_step(C, r0M, r0D1, r0D2, t == 0);
+                    r0M = R.M;
+                    r0D1 = R.D1;
+                    r0D2 = R.D2;
+                    inM = R.M;
                     inI1 = kInf;
                     inI2 = kInf;
                 } else {
@@ -132,46 +120,15 @@ __global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const
             uint32_t Mdiag = topPrev;
             topPrev = inM;
             uint32_t Mup = inM, I1up = inI1, I2up = inI2;
-#pragma unroll
-            for (int k = 0; k < kRows; ++k) {
-                const uint32_t cd = Mdiag + (inC == bk[k] ? 0u : C.sub);
-                const uint32_t i1o = Mup + C.oe[0], i2o = Mup + C.oe[2];
-                const uint32_t I1 = umin(i1o, I1up + C.e[0]);
-                const uint32_t I2 = umin(i2o, I2up + C.e[2]);
-                const uint32_t d1o = Mp[k] + C.oe[1], d2o = Mp[k] + C.oe[3];
-                const uint32_t D1 = umin(d1o, D1p[k] + C.e[1]);
-                const uint32_t D2 = umin(d2o, D2p[k] + C.e[3]);
-                const uint32_t ci = Mup + C.ins, cdl = Mp[k] + C.del;
-                const uint32_t M = umin(umin(umin3(cd, ci, cdl), umin3(I1, D1, I2)), umin(D2, kInf));
-                Mdiag = Mp[k];
-                Mp[k] = M;
-                D1p[k] = D1;
-                D2p[k] = D2;
-                Mup = M;
-                I1up = I1;
-                I2up = I2;
-            }
+            rows_step(C, bk, Mp, D1p, D2p, inC, Mdiag, Mup, I1up, I2up);
             if (active) {
                 if (last && s + 1 < (int)W.strips) {
                     const u32x4 w = {Mup, I1up, I2up, 0u};
                     bnd_out[i] = w;
                 }
-                if (i == ck_col && kck > 0 && i < n) {  // lanes reach the column at different steps: each stores its own rows
-                    PA_GLOBAL u32x4* const dst = (PA_GLOBAL u32x4*)(ck + ((size_t)(kck - 1) * H + j0) * kCkWords);
-#pragma unroll
-                    for (int q = 0; q < kCkVecs; ++q) {
-                        const u32x4 w = {ck_word(Mp, D1p, D2p, 4 * q), ck_word(Mp, D1p, D2p, 4 * q + 1), ck_word(Mp, D1p, D2p, 4 * q + 2),
-                                         ck_word(Mp, D1p, D2p, 4 * q + 3)};
-                        dst[q] = w;
-                    }
-                    if (top) {
-                        PA_GLOBAL uint32_t* const row0 = ck + ((size_t)((P.n - 1) / W.tile_cols) * H + (kck - 1)) * kCkWords;
-                        row0[0] = r0M;
-                        row0[1] = r0D1;
-                        row0[2] = r0D2;
-                    }
-                }
-                if (i == n && m > j0 && m <= j0 + kRows) {
+                // lanes reach the column at different steps: each stores its own rows
+                if (i == ck_col && kck > 0 && i < n) store_col_ckpt(ck, H, (P.n - 1) / W.tile_cols, kck - 1, j0, Mp, D1p, D2p, top, r0M, r0D1, r0D2);
+                if (i == n && m > j0 && m <= j0 + kRows) {  // row_m_of, written out: see the note above this kernel
                     uint32_t v = 0;
 #pragma unroll
                     for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
@@ -365,6 +322,9 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_tile_kernel(const Ti
     }
 }
 
+// The walk step stands in this kernel's body, not walk_step: called (in either signature) the kernel is 364 instructions for 352 and
+// its launches took 2 to 2.5 % longer in every process of two sessions (16 x 100 kbp: 132.2 ms against 129.0; 4096 x 10 kbp: 22.1
+// against 21.6), where the written-out form built twice differs by 0.3 %.  A change to walk_step is made here too.
 __global__ __launch_bounds__(64) void affine4_tile_walk_kernel(const TileJob* __restrict__ jobs, int nj) {
     const int t = (int)(blockIdx.x * 64 + threadIdx.x);
     if (t >= nj) return;

@@ -17,7 +17,6 @@ namespace {
 
 // affine_host.hpp's traits for the route of this unit: align_tiled().
 struct Host : HostBase {
-    using CkWave = affine4::CkWave;
     using WalkState = affine4::WalkState;
     using TileJob = affine4::TileJob;
     using TileWave = affine4::TileWave;
@@ -29,7 +28,7 @@ struct Host : HostBase {
     static int ckpt_pass(Batch& ab, affine_host::TiledChunk<Host>& ch, uint32_t C, hipStream_t s, float* ms) {
         return affine_host::ckpt_pass<Host>(ab, ch, C, s, ms);
     }
-    static bool launch_ckpt(const Batch& ab, const CkWave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s) {
+    static bool launch_ckpt(const Batch& ab, const Wave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s) {
         if (nwaves == 0) return true;
         const int nw = (int)nwaves;
         hipLaunchKernelGGL(affine4_ckpt_kernel, dim3((nw + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, d_waves, nw, d_pairs, ab.C,

@@ -163,21 +163,21 @@ template <class T>
 int ckpt_pass(typename T::Batch& ab, TiledChunk<T>& ch, uint32_t C, hipStream_t s, float* ms) {
     using ChainJob = typename T::ChainJob;
     using Pair = typename T::Pair;
-    using CkWave = typename T::CkWave;
+    using Wave = typename T::Wave;
     constexpr size_t vb = T::kLayout.bnd_bytes;
     auto& P = ch.plan;
     const size_t np = P.pairs.size();
     Events ev;
     if (!ev.make()) return PA_E_HIP;
     DeviceBuf d_pwaves, d_cjobs;  // chained: the plan's one-strip waves, and the chain jobs of the others
-    const CkWave* d_waves = P.d_waves.template as<CkWave>();
+    const Wave* d_waves = P.d_waves.template as<Wave>();
     size_t nwaves = P.waves.size();
     affine_chain::Plan cp;
     if (ab.chain.on) {  // the strip pairs leave the plan's launch for the chained one; their rows stay where make_plan put them
-        std::vector<CkWave> one;
+        std::vector<Wave> one;
         std::vector<affine_chain::Shape> shapes;
         std::vector<uint32_t> at;  // index into P.pairs
-        for (const CkWave& W : P.waves)
+        for (const Wave& W : P.waves)
             if (W.strips == 1) one.push_back(W);
         for (size_t k = 0; k < np; ++k)  // (P.pairs keeps the order of ids; the waves are sorted by cost)
             if (P.pairs[k].m > affine_chain::kStripRows) {
@@ -190,10 +190,10 @@ int ckpt_pass(typename T::Batch& ab, TiledChunk<T>& ch, uint32_t C, hipStream_t 
                 return fail(PA_E_INTERNAL, "%s_align_tiled: chained route: the planner and the checkpoint plan disagree on pair %u's rows", T::kName,
                             P.pairs[at[x]].out);
         const std::vector<ChainJob> cjobs = chain_jobs_of<T>(cp, shapes, P.d_bnd.ptr, &at);
-        if (!upload(d_pwaves, one.data(), one.size() * sizeof(CkWave), s) || !upload(d_cjobs, cjobs.data(), cjobs.size() * sizeof(ChainJob), s) ||
+        if (!upload(d_pwaves, one.data(), one.size() * sizeof(Wave), s) || !upload(d_cjobs, cjobs.data(), cjobs.size() * sizeof(ChainJob), s) ||
             !hip_ok(hipStreamSynchronize(s), "sync"))
             return PA_E_HIP;
-        d_waves = d_pwaves.template as<CkWave>();
+        d_waves = d_pwaves.template as<Wave>();
         nwaves = one.size();
     }
     std::vector<uint32_t> errs;

@@ -4,7 +4,7 @@
 //
 // No kernel is named here: the kernels are non-template __global__ functions defined in headers and must stay in one unit each.  A unit
 // includes its kernel header, then this one, and instantiates the templates with a traits struct T of its own:
-//   Batch, Pair, Wave, CkWave (the checkpoint pass's wave), Walk, WalkOut, WalkState, TileJob, TileWave   the records
+//   Batch, Pair, Wave, Walk, WalkOut, WalkState, TileJob, TileWave   the records
 //   kLayout                              affine_plan.hpp's description of the batch type
 //   kName                                the C prefix that begins every error text ("pa_affine_batch")
 //   kMaxLayer, kVisitSlack               the highest layer of a walk state; what the visit guard allows beyond tile_visits_max
@@ -246,7 +246,7 @@ int align(typename T::Batch* ab, int32_t* cost_out, char** cigar_out, float* for
 // its rest.
 template <class T>
 struct TiledChunk {
-    Plan<typename T::Pair, typename T::CkWave> plan;
+    Plan<typename T::Pair, typename T::Wave> plan;
     std::vector<const uint8_t*> ck;     // column checkpoints
     std::vector<const uint8_t*> rowck;  // row checkpoints: strip s at rowck + s (n + 1) values; nullptr for one strip
     std::vector<typename T::WalkState> st;

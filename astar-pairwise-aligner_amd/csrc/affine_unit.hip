@@ -70,7 +70,6 @@ struct Host {
     using Batch = pa_affine_batch;
     using Pair = affine::Pair;
     using Wave = affine::Wave;
-    using CkWave = affine::Wave;
     using Walk = affine::Walk;
     using WalkOut = affine::WalkOut;
     using WalkState = affine::WalkState;
