@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine_batch_align_dt_seg", "pa_affine_batch_dt_seg_info",
     "pa_affine4_batch_create", "pa_affine4_batch_run", "pa_affine4_batch_align", "pa_affine4_batch_info", "pa_affine4_batch_destroy",
     "pa_affine4_batch_align_tiled", "pa_affine4_batch_tiled_info", "pa_affine4_batch_set_chain", "pa_affine4_batch_chain_info",
+    "pa_affine4_batch_set_free_ends", "pa_affine4_batch_ends", "pa_affine4_batch_last_row",
 ]
 
 _lib = None
@@ -146,6 +147,10 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine4_batch_set_chain.argtypes = [vp, C.c_int]
         L.pa_affine4_batch_chain_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
         L.pa_affine4_batch_chain_info.restype = None
+    if hasattr(L, "pa_affine4_batch_set_free_ends"):
+        L.pa_affine4_batch_set_free_ends.argtypes = [vp, C.c_int, C.c_int]
+        L.pa_affine4_batch_ends.argtypes = [vp, vp, vp]
+        L.pa_affine4_batch_last_row.argtypes = [vp, vp, vp]
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -614,7 +619,7 @@ def _s_max_arg(s_max) -> int:
 class _AffineBatchBase:
     """What AffineBatch (pa_affine_batch_*) and Affine4Batch (pa_affine4_batch_*) share: the C functions of either differ in their
     prefix, `_PREFIX`, in the cost structure they take, `_cost_c`, and in where align_tiled() keeps the walk time, `_WALK_MS`.  Both have
-    the chained route (set_chain, chain_info)."""
+    the chained route (set_chain, chain_info) and ends-free mode (set_free_ends, ends, last_row)."""
 
     _PREFIX = ""
     _WALK_MS = "last_trace_ms"
@@ -727,6 +732,37 @@ class _AffineBatchBase:
         d["on"] = bool(d["on"])
         return d
 
+    def set_free_ends(self, free_start: bool, free_end: bool) -> None:
+        """Ends-free (semi-global) mode for every later run(), align() and align_tiled(): with free_start a prefix of a costs nothing
+        (row 0 is zero), with free_end the cost is the lowest value of the last row and `end` the lowest column that holds it.  The
+        CIGARs then describe a[start:end] against b (ends()).  Both off (the default): global alignment."""
+        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+        self._check(self._fn("set_free_ends")(self._h, fs, fe), f"{self._PREFIX}_set_free_ends")
+
+    def ends(self) -> np.ndarray:
+        """int64[npairs, 2]: (start, end) of every pair in the last run(), align() or align_tiled() under the current setting; after a
+        cost-only run() start is -1 under free_start and 0 otherwise.  ValueError before any such call or after set_free_ends."""
+        n = max(self.npairs, 1)
+        st, en = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self._check(self._fn("ends")(self._h, _p(st), _p(en)), f"{self._PREFIX}_ends")
+        return np.stack([st, en], axis=1)[: self.npairs]
+
+    def last_row(self, pairs=None) -> list:
+        """M(i, |b|) for i = 0 .. |a| of every pair in `pairs` (indices; None: all), a list of int32 arrays, under the current setting: in
+        global mode the cost of b against every prefix of a.  Runs a cost-only pass of its own, in chunks within
+        PA_AFFINE_TRACE_BUDGET_MB; ValueError for a pair whose row alone exceeds it."""
+        ids = list(range(self.npairs)) if pairs is None else [int(p) for p in pairs]
+        if any(not 0 <= p < self.npairs for p in ids) or len(set(ids)) != len(ids):
+            raise ValueError("pairs must be distinct indices of the batch")
+        offs = np.full(max(self.npairs, 1), np.iinfo(np.uint64).max, np.uint64)
+        total = 0
+        for p in ids:
+            offs[p] = total
+            total += len(self._keep[p][0]) + 1
+        out = np.zeros(max(total, 1), np.int32)
+        self._check(self._fn("last_row")(self._h, _p(out), _p(offs)), f"{self._PREFIX}_last_row")
+        return [out[int(offs[p]): int(offs[p]) + len(self._keep[p][0]) + 1].copy() for p in ids]
+
     def close(self):
         if getattr(self, "_h", None):
             self._fn("destroy")(self._h)
@@ -755,37 +791,6 @@ class AffineBatch(_AffineBatchBase):
             self.set_chain(True)
         if free_start or free_end:
             self.set_free_ends(free_start, free_end)
-
-    def set_free_ends(self, free_start: bool, free_end: bool) -> None:
-        """Ends-free (semi-global) mode for every later run(), align() and align_tiled(): with free_start a prefix of a costs nothing
-        (row 0 is zero), with free_end the cost is the lowest value of the last row and `end` the lowest column that holds it.  The
-        CIGARs then describe a[start:end] against b (ends()).  Both off (the default): global alignment."""
-        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
-        self._check(load().pa_affine_batch_set_free_ends(self._h, fs, fe), "pa_affine_batch_set_free_ends")
-
-    def ends(self) -> np.ndarray:
-        """int64[npairs, 2]: (start, end) of every pair in the last run(), align() or align_tiled() under the current setting; after a
-        cost-only run() start is -1 under free_start and 0 otherwise.  ValueError before any such call or after set_free_ends."""
-        n = max(self.npairs, 1)
-        st, en = np.zeros(n, np.int64), np.zeros(n, np.int64)
-        self._check(load().pa_affine_batch_ends(self._h, _p(st), _p(en)), "pa_affine_batch_ends")
-        return np.stack([st, en], axis=1)[: self.npairs]
-
-    def last_row(self, pairs=None) -> list:
-        """M(i, |b|) for i = 0 .. |a| of every pair in `pairs` (indices; None: all), a list of int32 arrays, under the current setting: in
-        global mode the cost of b against every prefix of a.  Runs a cost-only pass of its own, in chunks within
-        PA_AFFINE_TRACE_BUDGET_MB; ValueError for a pair whose row alone exceeds it."""
-        ids = list(range(self.npairs)) if pairs is None else [int(p) for p in pairs]
-        if any(not 0 <= p < self.npairs for p in ids) or len(set(ids)) != len(ids):
-            raise ValueError("pairs must be distinct indices of the batch")
-        offs = np.full(max(self.npairs, 1), np.iinfo(np.uint64).max, np.uint64)
-        total = 0
-        for p in ids:
-            offs[p] = total
-            total += len(self._keep[p][0]) + 1
-        out = np.zeros(max(total, 1), np.int32)
-        self._check(load().pa_affine_batch_last_row(self._h, _p(out), _p(offs)), "pa_affine_batch_last_row")
-        return [out[int(offs[p]): int(offs[p]) + len(self._keep[p][0]) + 1].copy() for p in ids]
 
     @staticmethod
     def _s_max(s_max) -> int:
@@ -920,7 +925,10 @@ class Affine4Batch(_AffineBatchBase):
     layers with costs of their own), a and b in the orientation given (I consumes b, D consumes a).  trace=True allows align() and
     align_tiled(), the same CIGARs in bounded device memory (include/pa_affine4_tiled_hip.h).  chain=True runs every pair with
     |b| > 1024 on a wavefront per strip of 1024 rows in run() and align_tiled() (set_chain, include/pa_affine4_chain_hip.h); the results
-    are the same.  Global mode only: ends-free mode and diagonal transition are AffineBatch's, for two layers."""
+    are the same.  set_free_ends(free_start, free_end) (include/pa_affine4_ends_hip.h) makes the ends of a, the text, free in all of
+    these routes: the pattern b is placed in a[start:end] (ends()), and last_row() gives M(i, |b|) of every column; map_affine does
+    all of it in one call.  (The constructor keeps its four arguments, which tests/test_affine4_chain_api.py pins: the switches are set
+    on the batch.)  Not supported: diagonal transition, which is AffineBatch's, for two layers."""
 
     _PREFIX = "pa_affine4_batch"
     _WALK_MS = "last_walk_ms"
@@ -951,9 +959,13 @@ def map_affine(pairs, cm: AffineCost, free_start: bool = True, free_end: bool = 
                s_max: int | None = None) -> list[tuple[int, str, int, int]]:
     """[(cost, CIGAR, start, end)] of every pair (a the text, b the pattern) under the gap-affine cost model `cm` with the text's ends
     free (AffineBatch.set_free_ends): b is placed in a[start:end], which the CIGAR describes.  tiled and chain as in align_affine.
+    A four-layer `cm` (AffineCost.double_affine) runs an Affine4Batch instead, tiled and chain likewise.
     s_max=K takes the diagonal-transition route instead (AffineBatch.align_dt_ends(K, free_start, free_end), without tiled or chain):
-    (-1, "", -1, -1) for a pair whose cost exceeds K."""
+    (-1, "", -1, -1) for a pair whose cost exceeds K; ValueError with four layers, which have no such route."""
     free_start, free_end = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+    four = isinstance(cm, AffineCost) and len(cm.layers) == 4
+    if four and s_max is not None:
+        raise ValueError("s_max selects the diagonal-transition route, and diagonal transition has no double-affine route")
     if s_max is not None and (tiled or chain):
         raise ValueError("s_max selects the diagonal-transition route, which has no tiled or chained form")
     if chain and not tiled:
@@ -965,8 +977,13 @@ def map_affine(pairs, cm: AffineCost, free_start: bool = True, free_end: bool = 
             return b.align_dt_ends(s_max, free_start, free_end)
         finally:
             b.close()
-    b = AffineBatch(pairs, cm, trace=True, chain=chain, free_start=free_start, free_end=free_end)
+    if four:
+        b = Affine4Batch(pairs, cm, trace=True, chain=chain)
+    else:
+        b = AffineBatch(pairs, cm, trace=True, chain=chain, free_start=free_start, free_end=free_end)
     try:
+        if four:
+            b.set_free_ends(free_start, free_end)
         res = b.align_tiled() if tiled else b.align()
         se = b.ends()
         return [(c, g, int(se[p, 0]), int(se[p, 1])) for p, (c, g) in enumerate(res)]

@@ -15,6 +15,11 @@
 struct pa_affine4_batch : pa::affine_host::Batch<pa::affine4::Pair, pa::affine4::Wave> {
     pa::affine4::Costs C{};
     pa::affine_host::ChainState<pa::affine_host::Plan<pa::affine4::Pair, pa::affine4::Wave>> chain;  // set_chain
+    // Ends-free mode (set_free_ends, include/pa_affine4_ends_hip.h): the switches (kFreeStart | kFreeEnd; they reach the ENDS
+    // instantiations in their Ends record, Costs stays as it is), and every pair's end as those kernels leave it.
+    uint32_t free_ends = 0;
+    pa::DeviceBuf d_end;
+    pa::affine_host::EndsState ends;
 };
 
 namespace pa {
@@ -49,14 +54,16 @@ struct HostBase {
         }
         return out;
     }
-    // The costs of every pair, to the caller (global mode: every walk starts at 0).
-    static int finish(Batch& ab, int32_t* cost_out, hipStream_t s, const std::vector<int64_t>* = nullptr) {
-        if (!cost_out || ab.np == 0) return 0;
-        if (!hip_ok(hipMemcpyAsync(cost_out, ab.d_cost.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
-            return PA_E_HIP;
-        return 0;
+    // Ends-free mode (the host side is affine_host.hpp's): the switches, the record the ENDS instantiations take, and the end of every
+    // call, which keeps what pa_affine4_batch_ends reports.
+    static uint32_t ends_flags(const Batch& ab) { return ab.free_ends; }
+    static void set_ends_flags(Batch& ab, uint32_t f) { ab.free_ends = f; }
+    static Ends ends_of(const Batch& ab) { return Ends{ab.d_end.as<int32_t>(), nullptr, nullptr, ab.free_ends}; }
+    static int finish(Batch& ab, int32_t* cost_out, hipStream_t s, const std::vector<int64_t>* starts = nullptr) {
+        return affine_host::costs_out<HostBase>(ab, cost_out, s, starts);
     }
 };
+static_assert(kFreeStart == affine_host::kFreeStart && kFreeEnd == affine_host::kFreeEnd, "affine_host.hpp restates the switches");
 
 }  // namespace affine4
 }  // namespace pa

@@ -80,10 +80,12 @@ __device__ __forceinline__ uint32_t ck_word(const uint32_t (&Mp)[kRows], const u
 }
 
 // ticket_err[0]: the job ticket, ticket_err[1]: the error word; both zero at launch.  tile_cols: CKPT only.
-template <bool CKPT>
+// ENDS: under kFreeStart row 0 is zero in every lane of strip 0; the lane of the last strip's job that owns row |b| keeps the pair's
+// (best, end) (last_row_step).
+template <bool CKPT, bool ENDS = false>
 __global__ __launch_bounds__(64 * kBlockWaves) void affine4_chain_kernel(const ChainJob* __restrict__ jobs, int njobs, const Pair* __restrict__ pairs,
                                                                          Costs C, uint32_t tile_cols, uint32_t* ticket_err,
-                                                                         int32_t* __restrict__ cost_out) {
+                                                                         int32_t* __restrict__ cost_out, Ends E) {
     using affine4_chain::Halves;
     const int lane = (int)(threadIdx.x & 63);
     uint32_t tk = 0;
@@ -114,6 +116,9 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_chain_kernel(const C
         D2p[k] = kInf;
     }
     const int T = n + 64;  // the last lane reaches column n at step n + 63
+    LastRow LR;
+    if constexpr (ENDS) LR = last_row_init(E, P.out, true);
+    const bool fs = ENDS && (E.flags & kFreeStart);
     // The last checkpoint column the first lane has reached, and how many it has reached (affine4_ckpt_kernel's, the wavefront's: lane r
     // reaches column ck_col at step ck_col + r, and r < 64 <= tile_cols, so before the first lane reaches the next one).
     int ck_col = 0;
@@ -165,7 +170,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_chain_kernel(const C
                 fI1 = (uint32_t)__builtin_amdgcn_readlane((int)curI1, u);
                 fI2 = (uint32_t)__builtin_amdgcn_readlane((int)curI2, u);
             } else {  // row 0 of column t, the same in every lane
-                const Row0 R = row0_step(C, r0M, r0D1, r0D2, t == 0);
+                const Row0 R = row0_step(C, r0M, r0D1, r0D2, t == 0 || fs);
                 r0M = R.M;
                 r0D1 = R.D1;
                 r0D2 = R.D2;
@@ -203,7 +208,11 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_chain_kernel(const C
                         row0[2] = r0D2;
                     }
                 }
-                if (i == n && m > j0 && m <= j0 + kRows) out[P.out] = (int32_t)row_m_of(Mp, m, j0);
+                if constexpr (ENDS) {  // every column of the lane that owns row |b|
+                    if (m > j0 && m <= j0 + kRows) last_row_step(LR, E, P.out, row_m_of(Mp, m, j0), i, n, out);
+                } else if (i == n && m > j0 && m <= j0 + kRows) {
+                    out[P.out] = (int32_t)row_m_of(Mp, m, j0);
+                }
             }
             outM = Mup;
             outI1 = I1up;

@@ -12,6 +12,10 @@
 //   affine4_ckpt_kernel                   calls rows_step, row0_step, store_col_ckpt; the cost pick stays (it spills, called)
 //   affine4_chain_kernel                  calls rows_step, row0_step, row_m_of; <true> keeps the checkpoint store (2 % slower called)
 //   affine4_walk_kernel calls walk_step; affine4_tile_walk_kernel keeps the step (2 to 2.5 % slower called)
+// The ENDS instantiations (ends-free mode, below) share each kernel's text and therefore its choices above; what they add is called:
+// last_row_init, last_row_step and, for the pick at every column, row_m_of, in all three fills (affine4_ckpt_kernel<true> too, which
+// has launch bounds of its own for it: affine4_tile_kernel.hpp).  affine4_walk_kernel calls walk_done; affine4_tile_walk_kernel<FS>
+// keeps the test in its body (called, <false> is 366 instructions for the 352 it had, and its walks took 1 % longer).
 // So a change to the cost model, the tie order or the code byte is made here and under each of those notes.  DESIGN.md, "One step
 // for the double-affine kernels, where it holds", and profiles/affine4_step/ have the forms tried and the times.
 #pragma once
@@ -65,6 +69,47 @@ struct Wave {
                          // checkpoint pass: strips - 1 of them, every strip's but the last kept (the row checkpoints)
 };
 static_assert(sizeof(Wave) == 32, "Wave layout");
+
+// ---- ends-free mode (the ENDS / FS instantiations; the global-mode ones never look at it) ----
+//
+// include/pa_affine4_ends_hip.h has the definition: with kFreeStart row 0 is zero in every column; with kFreeEnd a pair's cost is the
+// lowest value of row |b|, and its end the lowest column that holds it.  The switches travel in this record, an argument of the ENDS
+// instantiations only: Costs stays at its 11 words.  The lane that owns row |b| keeps (best, end) while its columns go by and stores
+// them at column n (affine_kernel.hpp's Ends / LastRow, restated for the reason given above).
+constexpr uint32_t kFreeStart = 1, kFreeEnd = 2;
+struct Ends {
+    int32_t* end_out;         // by Pair::out, next to cost_out
+    int32_t* rows;            // last_row(): M(i, |b|) of column i at rows[row_off[Pair::out] + i]; nullptr: not asked for
+    const uint64_t* row_off;  // ~0 skips the pair
+    uint32_t flags;           // kFreeStart | kFreeEnd
+};
+struct LastRow {
+    uint32_t best = 0xFFFFFFFFu;
+    int32_t end = 0;
+    PA_GLOBAL int32_t* row = nullptr;
+};
+__device__ __forceinline__ LastRow last_row_init(const Ends& E, uint32_t out, bool present) {
+    LastRow L;
+    if (E.rows && present) {
+        const uint64_t off = ((gcu64)E.row_off)[out];
+        if (off != ~uint64_t(0)) L.row = (gi32)E.rows + off;
+    }
+    return L;
+}
+// Column i (0 .. n, in order) of row |b| holds v.
+__device__ __forceinline__ void last_row_step(LastRow& L, const Ends& E, uint32_t out, uint32_t v, int i, int n, gi32 cost_out) {
+    if (L.row) L.row[i] = (int32_t)v;
+    if ((E.flags & kFreeEnd) ? v < L.best : i == n) {  // strict: the lowest column wins
+        L.best = v;
+        L.end = i;
+    }
+    if (i == n) {
+        cost_out[out] = (int32_t)L.best;
+        ((gi32)E.end_out)[out] = L.end;
+    }
+}
+// The walk is over: (0, 0, main), or with a free start any (i, 0, main).
+__device__ __forceinline__ bool walk_done(int64_t i, int64_t j, int layer, bool free_start) { return j == 0 && layer == 0 && (free_start || i == 0); }
 
 // ---- the fill's pieces ----
 

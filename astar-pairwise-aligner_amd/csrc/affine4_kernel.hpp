@@ -32,7 +32,7 @@
 //   bits 2:0  main layer: 0 diagonal, 1 linear insertion, 2 linear deletion, 3 .. 6 close of layer 0 .. 3
 //   bit 3 + k layer k: 0 open (from the main layer), 1 extend; open comes before extend
 // Codes of rows 1 .. H of column i at codes[i H + j - 1], row 0 at codes[(n + 1) H + i]; the kRows bytes of a lane and step go out as
-// one store.  affine4_walk_kernel walks them backwards from (n, m, main) to (0, 0, main).
+// one store.  affine4_walk_kernel walks them backwards from (n, m, main) to (0, 0, main) (ends-free: from (end, m, main), see below).
 //
 // The cost-only instance takes its row loop from affine4_common.hpp (rows_step), as the checkpoint pass and the chained kernel do, and
 // affine4_walk_kernel its step (walk_step).  The loop with the code byte, row 0 with its byte and the cost pick stand in this kernel's
@@ -43,17 +43,23 @@
 // those four instructions longer.  A change to the recurrence or the code byte is made in rows_step, here and in affine4_tile_kernel.
 //
 // The tiled traceback (align_tiled) has its kernels in affine4_tile_kernel.hpp, in a unit of their own, and the chained route (set_chain:
-// the strips of a longer pair on a wavefront each, side by side) its kernel in affine4_chain_kernel.hpp.  Global mode only.  Not
-// supported: ends-free mode, diagonal transition, other layer lists.
+// the strips of a longer pair on a wavefront each, side by side) its kernel in affine4_chain_kernel.hpp.
+//
+// Ends-free mode (include/pa_affine4_ends_hip.h; no counterpart in the reference): the same recurrence with another row 0 (zero in every
+// column under kFreeStart), another answer (the lowest value of row |b| and its lowest column under kFreeEnd) and other endpoints of the
+// walk.  Every fill kernel has a second set of instantiations for it (ENDS, FS), which read the switches from their Ends argument
+// (affine4_common.hpp: Costs stays at 11 words); the global-mode ones compile to the instructions they had before the mode existed.
+// ENDS: 127 VGPRs cost-only, 144 FILL, no scratch; they call row_m_of and last_row_step.  Not supported: diagonal transition, other
+// layer lists.
 #pragma once
 #include "affine4_common.hpp"  // constants, Costs, Pair, Wave; rows_step, walk_step
 
 namespace pa {
 namespace affine4 {
 
-template <bool FILL>
+template <bool FILL, bool ENDS = false>
 __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* __restrict__ waves, int nwaves, const Pair* __restrict__ pairs, Costs C,
-                                                                   int32_t* __restrict__ cost_out) {
+                                                                   int32_t* __restrict__ cost_out, Ends E) {
     const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
     if (wave >= nwaves) return;
     const int lane = (int)(threadIdx.x & 63);
@@ -80,6 +86,9 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* _
     PA_GLOBAL u32x4* const bnd = (PA_GLOBAL u32x4*)W.bnd;
     const int T = (int)W.nmax + g;  // steps per strip: the last lane reaches column nmax at step nmax + g - 1
     const u32x4 kBndPad = {kInf, kInf, kInf, 0u};
+    LastRow LR;
+    if constexpr (ENDS) LR = last_row_init(E, P.out, present);
+    const bool fs = ENDS && (E.flags & kFreeStart);
     for (int s = 0; s < (int)W.strips; ++s) {
         const uint32_t j0 = (uint32_t)(64 * s + r) * kRows;
         uint32_t bk[kRows], Mp[kRows], D1p[kRows], D2p[kRows];
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* _
                     const uint32_t d1o = r0M + C.oe[1], d2o = r0M + C.oe[3], cdl = r0M + C.del;
                     const uint32_t D1 = umin3(d1o, r0D1 + C.e[1], kInf);
                     const uint32_t D2 = umin3(d2o, r0D2 + C.e[3], kInf);
-                    const uint32_t M = t == 0 ? 0u : umin(umin3(cdl, D1, D2), kInf);
+                    const uint32_t M = t == 0 || fs ? 0u : umin(umin3(cdl, D1, D2), kInf);
                     if (FILL && active) {
                         uint32_t c = M == D1 ? 4u : 6u;
                         c = M == cdl ? 2u : c;
@@ -132,7 +141,11 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* _
                 // prefetch the next column's byte and boundary value
                 nextC = present && t + 1 <= n ? (uint32_t)ga[t] : 0x100u;
                 if (from_bnd && present && t + 1 <= n) nextB = bnd[t + 1];
-                if (top && active && i == n && m == 0) out[P.out] = (int32_t)inM;
+                if constexpr (ENDS) {
+                    if (top && active && m == 0) last_row_step(LR, E, P.out, inM, i, n, out);  // row |b| is row 0
+                } else {
+                    if (top && active && i == n && m == 0) out[P.out] = (int32_t)inM;
+                }
             }
             uint32_t Mdiag = topPrev;
             topPrev = inM;
@@ -192,7 +205,9 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* _
                     const u32x4 w = {Mup, I1up, I2up, 0u};
                     bnd[i] = w;
                 }
-                if (i == n && m > j0 && m <= j0 + kRows) {
+                if constexpr (ENDS) {  // every column of the lane that owns row |b|
+                    if (m > j0 && m <= j0 + kRows) last_row_step(LR, E, P.out, row_m_of(Mp, m, j0), i, n, out);
+                } else if (i == n && m > j0 && m <= j0 + kRows) {
                     uint32_t v = 0;
 #pragma unroll
                     for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
@@ -217,28 +232,35 @@ struct Walk {
     const uint8_t* codes;
     uint8_t* ops;
     uint32_t n, m, H, cap;
+    uint32_t out, pad_;  // out: Pair::out, the walk's index into ends[]
 };
-static_assert(sizeof(Walk) == 48, "Walk layout");
+static_assert(sizeof(Walk) == 56, "Walk layout");
 struct WalkOut {
     int32_t status;  // 0 ok, 1 bad code, 2 ops over capacity
     int32_t nops;
+    int32_t start;  // the column the walk stopped in
 };
 
-__global__ __launch_bounds__(64) void affine4_walk_kernel(const Walk* __restrict__ walks, int nw, WalkOut* __restrict__ outs) {
+// ends: the ends the forward pass left by Pair::out (free end), or nullptr: every walk starts at (n, m, main).  free_start: the walk
+// stops at the first state (i, 0, main), whose i is the start.
+__global__ __launch_bounds__(64) void affine4_walk_kernel(const Walk* __restrict__ walks, int nw, WalkOut* __restrict__ outs,
+                                                          const int32_t* __restrict__ ends, int free_start) {
     const int t = (int)(blockIdx.x * 64 + threadIdx.x);
     if (t >= nw) return;
     const Walk Q = walks[t];
-    int64_t i = Q.n, j = Q.m;
+    int64_t i = ends ? ends[Q.out] : Q.n, j = Q.m;
+    if (i < 0 || i > (int64_t)Q.n) i = Q.n;  // (never: the forward pass stores a column of the pair)
     int layer = 0;  // 0 main, 1 + k: layer k
     const size_t row0 = (size_t)(Q.n + 1) * Q.H;
     WalkOut o;
     o.status = 0;
     o.nops = 0;
-    while (o.status == 0 && !(i == 0 && j == 0 && layer == 0)) {
+    while (o.status == 0 && !walk_done(i, j, layer, free_start != 0)) {
         const uint32_t c = j > 0 ? Q.codes[(size_t)i * Q.H + (size_t)(j - 1)] : Q.codes[row0 + (size_t)i];
         walk_step(c, Q, i, j, layer, o.nops, o.status);
     }
     if (o.status == 0 && (uint32_t)o.nops > Q.cap) o.status = 2;
+    o.start = (int32_t)i;
     outs[t] = o;
 }
 

@@ -23,6 +23,9 @@
 //   3. affine4_tile_walk_kernel: affine4_walk_kernel's loop from the pair's stored state (i, j, layer 0 .. 4, ops so far, status) until
 //      the state leaves the tile or reaches (0, 0, main).  The layer travels with the state: a gap that is open in layer k at a tile
 //      edge goes on in layer k in the next tile.
+// Ends-free mode (affine4_kernel.hpp): affine4_ckpt_kernel<true> keeps (best, end) of row |b| like affine4_kernel<false, true>,
+// affine4_tile_kernel<true> reproduces a zero row 0, and the walk starts at the state the host seeded, (end, m, main), and stops on
+// walk_done.
 #pragma once
 #include "affine4_common.hpp"
 
@@ -33,8 +36,15 @@ namespace affine4 {
 // registers for this kernel (three wavefronts); told the target it fits 127, without scratch or AGPRs.  That leaves no register to
 // spare, so the final-cost pick stays written out: with row_m_of called, as affine4_chain_kernel has it,
 // it compiles to 128 VGPRs and 76 bytes of scratch (19 values spilled) in every form of the helper tried.
-__global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const Wave* __restrict__ waves, int nwaves, const Pair* __restrict__ pairs,
-                                                                        Costs C, int32_t* __restrict__ cost_out) {
+// The ENDS instantiation keeps two more values per lane (best and end; it never stores last rows, so no pointer): held to four
+// wavefronts it is 128 VGPRs and 80 bytes of scratch (164 with the pick as a tree of selects on the bits of the row index), so it has
+// bounds of its own, three wavefronts: 149 VGPRs, nothing spilled.
+template <bool ENDS>
+constexpr int kCkptWavesPerSimd = ENDS ? 3 : 4;
+template <bool ENDS = false>
+__global__ __launch_bounds__(64 * kBlockWaves, kCkptWavesPerSimd<ENDS>) void affine4_ckpt_kernel(const Wave* __restrict__ waves, int nwaves,
+                                                                                             const Pair* __restrict__ pairs, Costs C,
+                                                                                             int32_t* __restrict__ cost_out, Ends E) {
     const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
     if (wave >= nwaves) return;
     const int lane = (int)(threadIdx.x & 63);
@@ -61,6 +71,8 @@ __global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const
     PA_GLOBAL uint32_t* const ck = (PA_GLOBAL uint32_t*)P.codes;
     const int T = (int)W.nmax + g;  // steps per strip: the last lane reaches column nmax at step nmax + g - 1
     const u32x4 kBndPad = {kInf, kInf, kInf, 0u};
+    LastRow LR;  // (no last_row_init: last_row() is a pass of affine4_kernel's, so this one never stores rows)
+    const bool fs = ENDS && (E.flags & kFreeStart);
     for (int s = 0; s < (int)W.strips; ++s) {
         const uint32_t j0 = (uint32_t)(64 * s + r) * kRows;
         const gcu8 gb = present ? (gcu8)((PA_GLOBAL const Pair*)pairs)[W.first + seg].b : (gcu8) nullptr;  // (not kept across the steps)
@@ -100,7 +112,7 @@ __global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const
             if (first) {
                 inC = nextC;
                 if (top) {
-                    const Row0 R = row0_step(C, r0M, r0D1, r0D2, t == 0);
+                    const Row0 R = row0_step(C, r0M, r0D1, r0D2, t == 0 || fs);
                     r0M = R.M;
                     r0D1 = R.D1;
                     r0D2 = R.D2;
@@ -115,7 +127,11 @@ __global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const
                 // prefetch the next column's byte and boundary value
                 nextC = present && t + 1 <= n ? (uint32_t)ga[t] : 0x100u;
                 if (from_bnd && present && t + 1 <= n) nextB = bnd_in[t + 1];
-                if (top && active && i == n && m == 0) out[P.out] = (int32_t)inM;
+                if constexpr (ENDS) {
+                    if (top && active && m == 0) last_row_step(LR, E, P.out, inM, i, n, out);  // row |b| is row 0
+                } else {
+                    if (top && active && i == n && m == 0) out[P.out] = (int32_t)inM;
+                }
             }
             uint32_t Mdiag = topPrev;
             topPrev = inM;
@@ -128,7 +144,9 @@ __global__ __launch_bounds__(64 * kBlockWaves, 4) void affine4_ckpt_kernel(const
                 }
                 // lanes reach the column at different steps: each stores its own rows
                 if (i == ck_col && kck > 0 && i < n) store_col_ckpt(ck, H, (P.n - 1) / W.tile_cols, kck - 1, j0, Mp, D1p, D2p, top, r0M, r0D1, r0D2);
-                if (i == n && m > j0 && m <= j0 + kRows) {  // row_m_of, written out: see the note above this kernel
+                if constexpr (ENDS) {  // every column of the lane that owns row |b|
+                    if (m > j0 && m <= j0 + kRows) last_row_step(LR, E, P.out, row_m_of(Mp, m, j0), i, n, out);
+                } else if (i == n && m > j0 && m <= j0 + kRows) {  // row_m_of, written out: see the note above this kernel
                     uint32_t v = 0;
 #pragma unroll
                     for (int k = 0; k < kRows; ++k) v = m == j0 + k + 1 ? Mp[k] : v;
@@ -172,6 +190,8 @@ struct TileWave {
     uint32_t first, np, lg, steps;
 };
 
+// FS: row 0 is zero in every column (kFreeStart), as the checkpoint pass had it, whatever D1 / D2 its checkpoint holds.
+template <bool FS = false>
 __global__ __launch_bounds__(64 * kBlockWaves) void affine4_tile_kernel(const TileWave* __restrict__ waves, int nwaves, const TileJob* __restrict__ jobs,
                                                                         Costs C) {
     const int wave = (int)(blockIdx.x * kBlockWaves + (threadIdx.x >> 6));
@@ -248,7 +268,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_tile_kernel(const Ti
                 const uint32_t d1o = r0M + C.oe[1], d2o = r0M + C.oe[3], cdl = r0M + C.del;
                 const uint32_t D1 = umin3(d1o, r0D1 + C.e[1], kInf);
                 const uint32_t D2 = umin3(d2o, r0D2 + C.e[3], kInf);
-                const uint32_t M = i == 0 ? 0u : umin(umin3(cdl, D1, D2), kInf);
+                const uint32_t M = i == 0 || FS ? 0u : umin(umin3(cdl, D1, D2), kInf);
                 if (active) {
                     uint32_t c = M == D1 ? 4u : 6u;
                     c = M == cdl ? 2u : c;
@@ -325,6 +345,11 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_tile_kernel(const Ti
 // The walk step stands in this kernel's body, not walk_step: called (in either signature) the kernel is 364 instructions for 352 and
 // its launches took 2 to 2.5 % longer in every process of two sessions (16 x 100 kbp: 132.2 ms against 129.0; 4096 x 10 kbp: 22.1
 // against 21.6), where the written-out form built twice differs by 0.3 %.  A change to walk_step is made here too.
+// FS (kFreeStart): the walk is over at the first state (i, 0, main), walk_done's rule.  A template parameter, not an argument: with
+// walk_done(.., free_start) in the loop the global-mode walks of 4096 x 10 kbp took 21.4 ms for 21.1 (1 %, 367 instructions for 352).
+// Written as below, <false> is the kernel as it was before the mode existed, instruction for instruction (called with a constant, or
+// through a lambda, walk_done's own order of the three tests gives 366 and 386).
+template <bool FS = false>
 __global__ __launch_bounds__(64) void affine4_tile_walk_kernel(const TileJob* __restrict__ jobs, int nj) {
     const int t = (int)(blockIdx.x * 64 + threadIdx.x);
     if (t >= nj) return;
@@ -339,7 +364,7 @@ __global__ __launch_bounds__(64) void affine4_tile_walk_kernel(const TileJob* __
     };
     const int64_t cs = J.c0 ? (int64_t)J.c0 + 1 : 0;
     const int64_t jt = (int64_t)J.rt * (64 * kRows), jmin = J.rt ? jt + 1 : 0;  // rows jmin .. of the pair are the tile's
-    while (status == 0 && !(i == 0 && j == 0 && layer == 0) && i >= cs && j >= jmin) {
+    while (status == 0 && !(FS ? j == 0 && layer == 0 : i == 0 && j == 0 && layer == 0) && i >= cs && j >= jmin) {
         const uint32_t c = j > 0 ? J.codes[(size_t)(i - cs) * J.Ht + (size_t)(j - 1 - jt)] : J.codes[(size_t)J.row0 + (size_t)(i - cs)];
         if (layer == 0) {
             const uint32_t p = c & 7u;
@@ -382,7 +407,7 @@ __global__ __launch_bounds__(64) void affine4_tile_walk_kernel(const TileJob* __
             }
         }
     }
-    if (status == 0 && i == 0 && j == 0 && layer == 0 && (uint32_t)nops > J.cap) status = 2;
+    if (status == 0 && (FS ? j == 0 && layer == 0 : i == 0 && j == 0 && layer == 0) && (uint32_t)nops > J.cap) status = 2;
     WalkState R;
     R.i = (int32_t)i;
     R.j = (int32_t)j;

@@ -8,10 +8,15 @@
 // batch is in affine4_batch.hpp, and the plan, the tail of create and the driver of align() are affine_host.hpp's, shared with the
 // two-layer batch.  set_chain(1) (include/pa_affine4_chain_hip.h) sends the pairs with |b| > 1024 through affine4_chain_kernel<false>
 // in run(), a wavefront per strip, the strips of a pair chained through their boundary rows; the host side of that route is
-// affine_chain_host.hpp's, shared likewise.  Not supported: ends-free mode, diagonal transition, other layer lists.
+// affine_chain_host.hpp's, shared likewise.  set_free_ends() (include/pa_affine4_ends_hip.h) makes the ends of a free in all of these
+// routes: the launches then pick the kernels' ENDS instantiations, which leave every pair's end in d_end; the walks start there, and
+// pa_affine4_batch_ends reports where they started and stopped.  last_row() is a cost-only pass of its own that also stores row |b|.
+// The host side of all three is affine_host.hpp's, shared with the two-layer batch.  Not supported: diagonal transition, other layer
+// lists.
 #include "affine4_kernel.hpp"
 #include "affine4_batch.hpp"
 #include "../../include/pa_affine4_chain_hip.h"
+#include "../../include/pa_affine4_ends_hip.h"
 
 #include <algorithm>
 
@@ -30,21 +35,44 @@ struct Host : HostBase {
     template <bool FILL>
     static bool launch(const Batch& ab, const affine_host::Plan<Pair, Wave>& P, hipStream_t s) {
         if (P.waves.empty()) return true;
+        return launch_ends<FILL>(ab, P, s, nullptr);
+    }
+    // Global mode runs the instantiation without the ends-free state; a free end, or `rows` (last_row(): where the last rows go), the one with.
+    template <bool FILL>
+    static bool launch_ends(const Batch& ab, const affine_host::Plan<Pair, Wave>& P, hipStream_t s, const Ends* rows) {
         const int grid = (int)((P.waves.size() + kBlockWaves - 1) / kBlockWaves);
-        hipLaunchKernelGGL((affine4_kernel<FILL>), dim3(grid), dim3(64 * kBlockWaves), 0, s, P.d_waves.as<Wave>(), (int)P.waves.size(), P.d_pairs.as<Pair>(), ab.C,
-                           ab.d_cost.as<int32_t>());
+        if (ab.free_ends || rows)
+            hipLaunchKernelGGL((affine4_kernel<FILL, true>), dim3(grid), dim3(64 * kBlockWaves), 0, s, P.d_waves.as<Wave>(), (int)P.waves.size(),
+                               P.d_pairs.as<Pair>(), ab.C, ab.d_cost.as<int32_t>(), rows ? *rows : ends_of(ab));
+        else
+            hipLaunchKernelGGL((affine4_kernel<FILL, false>), dim3(grid), dim3(64 * kBlockWaves), 0, s, P.d_waves.as<Wave>(), (int)P.waves.size(),
+                               P.d_pairs.as<Pair>(), ab.C, ab.d_cost.as<int32_t>(), Ends{});
         return hip_ok(hipGetLastError(), FILL ? "affine4_kernel<FILL> launch" : "affine4_kernel launch");
     }
-    static void walk_extra(const Batch&, const Pair&, Walk&) {}
-    static bool launch_walk(const Batch&, const Walk* d_walks, int nw, WalkOut* d_outs, hipStream_t s) {
-        hipLaunchKernelGGL(affine4_walk_kernel, dim3((nw + 63) / 64), dim3(64), 0, s, d_walks, nw, d_outs);
+    static bool launch_rows(const Batch& ab, const affine_host::Plan<Pair, Wave>& P, int32_t* d_rows, const uint64_t* d_off, hipStream_t s) {
+        if (P.waves.empty()) return true;
+        const Ends E{ab.d_end.as<int32_t>(), d_rows, d_off, ab.free_ends};
+        return launch_ends<false>(ab, P, s, &E);
+    }
+    static void walk_extra(const Batch&, const Pair& Q, Walk& w) {
+        w.out = Q.out;
+        w.pad_ = 0;
+    }
+    static bool launch_walk(const Batch& ab, const Walk* d_walks, int nw, WalkOut* d_outs, hipStream_t s) {
+        hipLaunchKernelGGL(affine4_walk_kernel, dim3((nw + 63) / 64), dim3(64), 0, s, d_walks, nw, d_outs,
+                           (ab.free_ends & kFreeEnd) ? ab.d_end.as<int32_t>() : nullptr, (ab.free_ends & kFreeStart) ? 1 : 0);
         return hip_ok(hipGetLastError(), "affine4_walk_kernel launch");
     }
-    static int64_t walk_start(const WalkOut&) { return 0; }
+    static int64_t walk_start(const WalkOut& o) { return o.start; }
     // affine4_chain_kernel<false> over one chunk's jobs (the chained route's host side is affine_chain_host.hpp's)
     static bool launch_chain_run(const Batch& ab, const ChainJob* d_jobs, int njobs, const Pair* d_pairs, uint32_t* ticket_err, hipStream_t s) {
-        hipLaunchKernelGGL((affine4_chain_kernel<false>), dim3((njobs + kBlockWaves - 1) / kBlockWaves), dim3(64 * kBlockWaves), 0, s, d_jobs, njobs, d_pairs,
-                           ab.C, 0u, ticket_err, ab.d_cost.as<int32_t>());
+        const dim3 grid((njobs + kBlockWaves - 1) / kBlockWaves), block(64 * kBlockWaves);
+        if (ab.free_ends)
+            hipLaunchKernelGGL((affine4_chain_kernel<false, true>), grid, block, 0, s, d_jobs, njobs, d_pairs, ab.C, 0u, ticket_err, ab.d_cost.as<int32_t>(),
+                               ends_of(ab));
+        else
+            hipLaunchKernelGGL((affine4_chain_kernel<false, false>), grid, block, 0, s, d_jobs, njobs, d_pairs, ab.C, 0u, ticket_err,
+                               ab.d_cost.as<int32_t>(), Ends{});
         return hip_ok(hipGetLastError(), "affine4_chain_kernel launch");
     }
 };
@@ -93,8 +121,8 @@ extern "C" pa_affine4_batch* pa_affine4_batch_create(const uint8_t* const* a, co
 extern "C" int pa_affine4_batch_run(pa_affine4_batch* ab, int32_t* cost_out, float* kernel_ms) {
     if (!ab) return fail(PA_E_ARG, "pa_affine4_batch_run: NULL batch");
     if (kernel_ms) *kernel_ms = 0;
-    if (ab->np == 0) return 0;
     hipStream_t s = 0;
+    if (ab->np == 0) return Host::finish(*ab, cost_out, s);  // (nothing to copy: the call counts for pa_affine4_batch_ends)
     affine_host::Events ev;
     if (!ev.make()) return PA_E_HIP;
     affine_host::chain_begin(*ab);
@@ -122,6 +150,18 @@ extern "C" int pa_affine4_batch_set_chain(pa_affine4_batch* ab, int on) { return
 extern "C" void pa_affine4_batch_chain_info(const pa_affine4_batch* ab, double* on, double* chain_pairs, double* chain_jobs, double* chunks,
                                             double* bnd_bytes_max) {
     affine_host::chain_info(ab, on, chain_pairs, chain_jobs, chunks, bnd_bytes_max);
+}
+
+extern "C" int pa_affine4_batch_set_free_ends(pa_affine4_batch* ab, int free_start, int free_end) {
+    return affine_host::set_free_ends<Host>(ab, free_start, free_end);
+}
+
+extern "C" int pa_affine4_batch_ends(const pa_affine4_batch* ab, int64_t* start_out, int64_t* end_out) {
+    return affine_host::batch_ends<Host>(ab, start_out, end_out);
+}
+
+extern "C" int pa_affine4_batch_last_row(pa_affine4_batch* ab, int32_t* out, const uint64_t* offsets) {
+    return affine_host::last_row<Host>(ab, out, offsets);
 }
 
 extern "C" void pa_affine4_batch_destroy(pa_affine4_batch* ab) {

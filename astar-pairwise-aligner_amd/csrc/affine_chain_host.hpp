@@ -158,7 +158,8 @@ int run_chained(typename T::Batch& ab, Events& ev, hipStream_t s) {
 }
 
 // The checkpoint pass of a chunk of align_tiled, timed, the stream synchronised: the chunk's plan with the unchained checkpoint kernel
-// or, with chaining on, its one-strip waves with that kernel and the strip pairs chained, into the rows make_plan has placed.
+// or, with chaining on, its one-strip waves with that kernel and the strip pairs chained, into the rows make_plan has placed.  Under a
+// free end the walks are then seeded with the ends it found (seed_walks).
 template <class T>
 int ckpt_pass(typename T::Batch& ab, TiledChunk<T>& ch, uint32_t C, hipStream_t s, float* ms) {
     using ChainJob = typename T::ChainJob;
@@ -204,7 +205,8 @@ int ckpt_pass(typename T::Batch& ab, TiledChunk<T>& ch, uint32_t C, hipStream_t 
         !hip_ok(hipEventRecord(ev.e[1], s), "event") || !hip_ok(hipStreamSynchronize(s), "sync") ||
         !hip_ok(hipEventElapsedTime(ms, ev.e[0], ev.e[1]), "hipEventElapsedTime"))
         return PA_E_HIP;
-    return chain_check<T>("align_tiled", errs);
+    if (const int rc = chain_check<T>("align_tiled", errs)) return rc;
+    return seed_walks<T>(ab, ch, s);  // a free end: every walk starts at the end this pass found
 }
 
 }  // namespace affine_host

@@ -16,6 +16,8 @@
 //   walk_done(ab, S)                     whether a walk state needs no further tile
 //   cigar_of(ops, nops)                  the CIGAR text of a walk's ops
 //   finish(ab, cost_out, s, starts)      the costs to the caller, and whatever else the batch keeps of a call
+// and for ends-free mode (set_free_ends, batch_ends, last_row, costs_out, seed_walks: near the end of this header) ends_flags,
+// set_ends_flags and launch_rows.
 // A unit's traits need only what the templates it instantiates use.
 #pragma once
 #include "pa_hip_internal.hpp"
@@ -411,6 +413,126 @@ int align_tiled(typename T::Batch* ab, uint32_t tile_cols, int32_t* cost_out, ch
     if (refill_ms) *refill_ms = refill_total;
     if (walk_ms) *walk_ms = walk_total;
     return cigar_out ? give_cstrings(cigars, cigar_out) : 0;
+}
+
+// ---- ends-free mode (set_free_ends, ends, last_row), the same for both batches ----
+//
+// The batch keeps `DeviceBuf d_end` (every pair's end, left there by the kernels' ENDS instantiations) and `EndsState ends`; the traits
+// add
+//   ends_flags(ab), set_ends_flags(ab, f)   the switches, kFreeStart | kFreeEnd, wherever the batch's kernels read them
+//   launch_rows(ab, P, d_rows, d_off, s)    the cost-only ENDS kernel over a plan, which also stores the last rows (last_row())
+// and finish() is costs_out<T>.
+
+constexpr uint32_t kFreeStart = 1, kFreeEnd = 2;
+
+// What *_batch_ends reports.
+struct EndsState {
+    bool valid = false;               // a run, align or align_tiled has succeeded under the current setting
+    std::vector<int64_t> start, end;  // of that call
+};
+
+// Every pair's end after an ends-free pass (global mode: |a|, without a copy).
+template <class T>
+int fetch_ends(const typename T::Batch& ab, std::vector<int32_t>& end, hipStream_t s) {
+    end.assign(ab.n.begin(), ab.n.end());
+    if (ab.np == 0 || !T::ends_flags(ab)) return 0;
+    if (!hip_ok(hipMemcpyAsync(end.data(), ab.d_end.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
+        return PA_E_HIP;
+    return 0;
+}
+
+// The costs of every pair, to the caller; the end of run(), align() and align_tiled().  Keeps what *_batch_ends reports: the ends, and
+// the starts a traced call found (start; a cost-only run has none: -1 under a free start, else 0).
+template <class T>
+int costs_out(typename T::Batch& ab, int32_t* cost_out, hipStream_t s, const std::vector<int64_t>* start = nullptr) {
+    ab.ends.valid = false;
+    std::vector<int32_t> c(ab.np), e;
+    if (ab.np && (!hip_ok(hipMemcpyAsync(c.data(), ab.d_cost.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync")))
+        return PA_E_HIP;
+    if (const int rc = fetch_ends<T>(ab, e, s)) return rc;
+    if (cost_out && ab.np) std::memcpy(cost_out, c.data(), ab.np * 4);
+    ab.ends.end.assign(e.begin(), e.end());
+    if (start) ab.ends.start = *start;
+    else ab.ends.start.assign(ab.np, (T::ends_flags(ab) & kFreeStart) ? -1 : 0);
+    ab.ends.valid = true;
+    return 0;
+}
+
+// *_batch_set_free_ends.
+template <class T>
+int set_free_ends(typename T::Batch* ab, int free_start, int free_end) {
+    if (!ab) return fail(PA_E_ARG, "%s_set_free_ends: NULL batch", T::kName);
+    if ((free_start != 0 && free_start != 1) || (free_end != 0 && free_end != 1))
+        return fail(PA_E_ARG, "%s_set_free_ends: free_start = %d, free_end = %d: each is 0 or 1", T::kName, free_start, free_end);
+    if ((free_start || free_end) && !ab->d_end.reserve(std::max<size_t>(ab->np, 1) * 4)) return PA_E_HIP;
+    T::set_ends_flags(*ab, (free_start ? kFreeStart : 0) | (free_end ? kFreeEnd : 0));
+    ab->ends.valid = false;
+    return 0;
+}
+
+// *_batch_ends.
+template <class T>
+int batch_ends(const typename T::Batch* ab, int64_t* start_out, int64_t* end_out) {
+    if (!ab) return fail(PA_E_ARG, "%s_ends: NULL batch", T::kName);
+    if (!ab->ends.valid) return fail(PA_E_ARG, "%s_ends: no run, align or align_tiled has succeeded under the current setting", T::kName);
+    if (start_out && ab->np) std::memcpy(start_out, ab->ends.start.data(), ab->np * 8);
+    if (end_out && ab->np) std::memcpy(end_out, ab->ends.end.data(), ab->np * 8);
+    return 0;
+}
+
+// With a free end every walk of a tiled chunk starts at (end, m, main), the end the checkpoint pass found.
+template <class T>
+int seed_walks(typename T::Batch& ab, TiledChunk<T>& ch, hipStream_t s) {
+    if (!(T::ends_flags(ab) & kFreeEnd)) return 0;
+    const size_t np = ch.plan.pairs.size();
+    std::vector<int32_t> end;
+    if (const int rc = fetch_ends<T>(ab, end, s)) return rc;
+    for (size_t k = 0; k < np; ++k) ch.st[k].i = end[ch.plan.pairs[k].out];
+    if (!upload(ch.d_state, ch.st.data(), np * sizeof(typename T::WalkState), s) || !hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
+    return 0;
+}
+
+// *_batch_last_row: a cost-only pass of its own over the pairs that are asked for, in chunks whose rows fit the budget.  (It leaves costs
+// and ends of its chunks in d_cost and d_end, which every other call reads only right after its own pass.)
+template <class T>
+int last_row(typename T::Batch* ab, int32_t* out, const uint64_t* offsets) {
+    if (!ab) return fail(PA_E_ARG, "%s_last_row: NULL batch", T::kName);
+    if (ab->np == 0) return 0;
+    if (!out || !offsets) return fail(PA_E_ARG, "%s_last_row: NULL array", T::kName);
+    const size_t budget = trace_budget("PA_AFFINE_TRACE_BUDGET_MB");
+    std::vector<uint32_t> want;
+    for (const uint32_t p : ab->order)
+        if (offsets[p] != UINT64_MAX) {
+            if (((size_t)ab->n[p] + 1) * 4 > budget)
+                return fail(PA_E_ARG, "%s_last_row: pair %u: %zu bytes of last row exceed the budget of %zu bytes", T::kName, p, ((size_t)ab->n[p] + 1) * 4,
+                            budget);
+            want.push_back(p);
+        }
+    hipStream_t s = 0;
+    DeviceBuf d_rows, d_off;
+    if (!ab->d_end.reserve(ab->np * 4)) return PA_E_HIP;
+    std::vector<uint64_t> off(ab->np);
+    std::vector<int32_t> rows;
+    for (size_t c0 = 0; c0 < want.size();) {
+        std::fill(off.begin(), off.end(), UINT64_MAX);
+        size_t c1 = c0, words = 0;
+        while (c1 < want.size() && (c1 == c0 || (words + ab->n[want[c1]] + 1) * 4 <= budget)) {
+            off[want[c1]] = words;
+            words += (size_t)ab->n[want[c1]] + 1;
+            ++c1;
+        }
+        const std::vector<uint32_t> ids(want.begin() + c0, want.begin() + c1);
+        Plan<typename T::Pair, typename T::Wave> P;
+        if (const int rc = make_plan<T>(*ab, ids, P, Keep::kNone, nullptr, s)) return rc;
+        rows.resize(words);
+        if (!d_rows.reserve(words * 4) || !upload(d_off, off.data(), off.size() * 8, s)) return PA_E_HIP;
+        if (!T::launch_rows(*ab, P, d_rows.as<int32_t>(), d_off.as<uint64_t>(), s) ||
+            !hip_ok(hipMemcpyAsync(rows.data(), d_rows.ptr, words * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
+            return PA_E_HIP;
+        for (const uint32_t p : ids) std::memcpy(out + offsets[p], rows.data() + off[p], ((size_t)ab->n[p] + 1) * 4);
+        c0 = c1;
+    }
+    return 0;
 }
 
 template <class BatchT>

@@ -13,8 +13,8 @@
 // pa_affine_batch_ends reports where they started and stopped.  last_row() is a cost-only pass of its own that also stores row |b|.
 // The diagonal-transition route (run_dt, align_dt) is a unit of its own, affine_dt_unit.hip, which sees a batch through dt_view().
 // The plan, the chunking and the drivers of align() and align_tiled() are affine_host.hpp's and the chained route's host side is
-// affine_chain_host.hpp's, both shared with the four-layer batch; this unit gives them its records and launches (Host) and keeps what
-// only two layers have: ends-free mode, last_row(), dt_view().
+// affine_chain_host.hpp's, both shared with the four-layer batch, as is the host side of ends-free mode and last_row(); this unit gives
+// them its records and launches (Host) and keeps what only two layers have: dt_view().
 #include "engine.hpp"
 #include "affine_kernel.hpp"
 #include "affine_chain_host.hpp"
@@ -45,10 +45,7 @@ struct pa_affine_batch : affine_host::Batch<Pair, Wave> {
     affine_host::ChainState<Plan> chain;
     // Ends-free mode (set_free_ends): the switches are C.ends, the kernels leave every pair's end in d_end.
     DeviceBuf d_end;
-    struct {
-        bool valid = false;               // a run, align or align_tiled has succeeded under the current setting
-        std::vector<int64_t> start, end;  // of that call
-    } ends;
+    affine_host::EndsState ends;
     DtState* dt = nullptr;  // the diagonal-transition route's own state (affine_dt_unit.hip)
 };
 
@@ -63,7 +60,7 @@ DtView pa::affine::dt_view(pa_affine_batch* ab) {
 
 namespace {
 
-int costs_out(pa_affine_batch& ab, int32_t* cost_out, hipStream_t s, const std::vector<int64_t>* start = nullptr);
+static_assert(kFreeStart == affine_host::kFreeStart && kFreeEnd == affine_host::kFreeEnd, "affine_host.hpp restates the switches");
 
 // What affine_host.hpp's templates need of this batch type (the list is at the top of that header).
 struct Host {
@@ -95,7 +92,12 @@ struct Host {
     }
     static int64_t walk_start(const WalkOut& o) { return o.start; }
     static void begin_tiled(Batch& ab) { affine_host::chain_begin(ab); }
-    static int ckpt_pass(Batch& ab, affine_host::TiledChunk<Host>& ch, uint32_t C, hipStream_t s, float* ms);
+    static int ckpt_pass(Batch& ab, affine_host::TiledChunk<Host>& ch, uint32_t C, hipStream_t s, float* ms) {
+        return affine_host::ckpt_pass<Host>(ab, ch, C, s, ms);
+    }
+    static uint32_t ends_flags(const Batch& ab) { return ab.C.ends; }
+    static void set_ends_flags(Batch& ab, uint32_t f) { ab.C.ends = f; }
+    static bool launch_rows(const Batch& ab, const Plan& P, int32_t* d_rows, const uint64_t* d_off, hipStream_t s);
     // what affine_chain_host.hpp launches
     static bool launch_ckpt(const Batch& ab, const Wave* d_waves, size_t nwaves, const Pair* d_pairs, hipStream_t s);
     template <bool CKPT>
@@ -126,7 +128,9 @@ struct Host {
         cig.reverse();
         return cig.to_string();
     }
-    static int finish(Batch& ab, int32_t* cost_out, hipStream_t s, const std::vector<int64_t>* starts) { return costs_out(ab, cost_out, s, starts); }
+    static int finish(Batch& ab, int32_t* cost_out, hipStream_t s, const std::vector<int64_t>* starts) {
+        return affine_host::costs_out<Host>(ab, cost_out, s, starts);
+    }
 };
 
 // affine_kernel over nwaves device waves; a whole plan's, or (the checkpoint pass with chaining on) the one-strip waves of a plan.
@@ -174,29 +178,10 @@ bool Host::launch_chain(const Batch& ab, const ChainJob* d_jobs, int njobs, cons
 
 using affine_host::Events;
 
-// Every pair's end after an ends-free pass (global mode: |a|, without a copy).
-int fetch_ends(const pa_affine_batch& ab, std::vector<int32_t>& end, hipStream_t s) {
-    end.assign(ab.n.begin(), ab.n.end());
-    if (ab.np == 0 || !ab.C.ends) return 0;
-    if (!hip_ok(hipMemcpyAsync(end.data(), ab.d_end.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
-        return PA_E_HIP;
-    return 0;
-}
-
-// The costs of every pair, to the caller; the end of run(), align() and align_tiled().  Keeps what pa_affine_batch_ends reports: the ends,
-// and the starts a traced call found (start; a cost-only run has none: -1 under a free start, else 0).
-int costs_out(pa_affine_batch& ab, int32_t* cost_out, hipStream_t s, const std::vector<int64_t>* start) {
-    ab.ends.valid = false;
-    std::vector<int32_t> c(ab.np), e;
-    if (ab.np && (!hip_ok(hipMemcpyAsync(c.data(), ab.d_cost.ptr, ab.np * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync")))
-        return PA_E_HIP;
-    if (const int rc = fetch_ends(ab, e, s)) return rc;
-    if (cost_out && ab.np) std::memcpy(cost_out, c.data(), ab.np * 4);
-    ab.ends.end.assign(e.begin(), e.end());
-    if (start) ab.ends.start = *start;
-    else ab.ends.start.assign(ab.np, (ab.C.ends & kFreeStart) ? -1 : 0);
-    ab.ends.valid = true;
-    return 0;
+// last_row(): the cost-only ENDS kernel over a plan, the last rows to d_rows.
+bool Host::launch_rows(const Batch& ab, const Plan& P, int32_t* d_rows, const uint64_t* d_off, hipStream_t s) {
+    const Ends E{ab.d_end.as<int32_t>(), d_rows, d_off};
+    return ::launch<false>(ab, P.d_waves.as<Wave>(), P.waves.size(), P.d_pairs.as<Pair>(), s, &E);
 }
 
 }  // namespace
@@ -243,7 +228,7 @@ extern "C" int pa_affine_batch_run(pa_affine_batch* ab, int32_t* cost_out, float
     if (!ab) return fail(PA_E_ARG, "pa_affine_batch_run: NULL batch");
     if (kernel_ms) *kernel_ms = 0;
     hipStream_t s = 0;
-    if (ab->np == 0) return costs_out(*ab, cost_out, s);  // (nothing to copy: the call counts for pa_affine_batch_ends)
+    if (ab->np == 0) return Host::finish(*ab, cost_out, s, nullptr);  // (nothing to copy: the call counts for pa_affine_batch_ends)
     Events ev;
     if (!ev.make()) return PA_E_HIP;
     affine_host::chain_begin(*ab);
@@ -251,7 +236,7 @@ extern "C" int pa_affine_batch_run(pa_affine_batch* ab, int32_t* cost_out, float
         if (const int rc = affine_host::run_chained<Host>(*ab, ev, s)) return rc;
     } else if (!hip_ok(hipEventRecord(ev.e[0], s), "event") || !launch<false>(*ab, ab->fwd, s) || !hip_ok(hipEventRecord(ev.e[1], s), "event"))
         return PA_E_HIP;
-    if (const int rc = costs_out(*ab, cost_out, s)) return rc;
+    if (const int rc = Host::finish(*ab, cost_out, s, nullptr)) return rc;
     if (kernel_ms && !hip_ok(hipEventElapsedTime(kernel_ms, ev.e[0], ev.e[1]), "hipEventElapsedTime")) return PA_E_HIP;
     return 0;
 }
@@ -261,20 +246,6 @@ extern "C" int pa_affine_batch_align(pa_affine_batch* ab, int32_t* cost_out, cha
 }
 
 namespace {
-
-// The checkpoint pass of a chunk of align_tiled; with a free end every walk then starts at (end, m, main).
-int Host::ckpt_pass(pa_affine_batch& ab, affine_host::TiledChunk<Host>& ch, uint32_t C, hipStream_t s, float* ms) {
-    if (const int rc = affine_host::ckpt_pass<Host>(ab, ch, C, s, ms)) return rc;
-    const Plan& P = ch.plan;
-    const size_t np = P.pairs.size();
-    if (ab.C.ends & kFreeEnd) {  // every walk starts at (end, m, main), the end the checkpoint pass found
-        std::vector<int32_t> end;
-        if (const int rc = fetch_ends(ab, end, s)) return rc;
-        for (size_t k = 0; k < np; ++k) ch.st[k].i = end[P.pairs[k].out];
-        if (!upload(ch.d_state, ch.st.data(), np * sizeof(WalkState), s) || !hip_ok(hipStreamSynchronize(s), "sync")) return PA_E_HIP;
-    }
-    return 0;
-}
 
 // The fill of a round's tiles.  FS: row 0 is zero in every column, as the checkpoint pass had it.
 bool Host::launch_tile_fill(const Batch& ab, const TileWave* d_waves, int nw, const TileJob* d_jobs, hipStream_t s) {
@@ -300,64 +271,15 @@ extern "C" int pa_affine_batch_set_chain(pa_affine_batch* ab, int on) {
 }
 
 extern "C" int pa_affine_batch_set_free_ends(pa_affine_batch* ab, int free_start, int free_end) {
-    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_set_free_ends: NULL batch");
-    if ((free_start != 0 && free_start != 1) || (free_end != 0 && free_end != 1))
-        return fail(PA_E_ARG, "pa_affine_batch_set_free_ends: free_start = %d, free_end = %d: each is 0 or 1", free_start, free_end);
-    if ((free_start || free_end) && !ab->d_end.reserve(std::max<size_t>(ab->np, 1) * 4)) return PA_E_HIP;
-    ab->C.ends = (free_start ? kFreeStart : 0) | (free_end ? kFreeEnd : 0);
-    ab->ends.valid = false;
-    return 0;
+    return affine_host::set_free_ends<Host>(ab, free_start, free_end);
 }
 
 extern "C" int pa_affine_batch_ends(const pa_affine_batch* ab, int64_t* start_out, int64_t* end_out) {
-    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_ends: NULL batch");
-    if (!ab->ends.valid) return fail(PA_E_ARG, "pa_affine_batch_ends: no run, align or align_tiled has succeeded under the current setting");
-    if (start_out && ab->np) std::memcpy(start_out, ab->ends.start.data(), ab->np * 8);
-    if (end_out && ab->np) std::memcpy(end_out, ab->ends.end.data(), ab->np * 8);
-    return 0;
+    return affine_host::batch_ends<Host>(ab, start_out, end_out);
 }
 
-// A cost-only pass of its own over the pairs that are asked for, in chunks whose rows fit the budget.  (It leaves costs and ends of its
-// chunks in d_cost and d_end, which every other call reads only right after its own pass.)
 extern "C" int pa_affine_batch_last_row(pa_affine_batch* ab, int32_t* out, const uint64_t* offsets) {
-    if (!ab) return fail(PA_E_ARG, "pa_affine_batch_last_row: NULL batch");
-    if (ab->np == 0) return 0;
-    if (!out || !offsets) return fail(PA_E_ARG, "pa_affine_batch_last_row: NULL array");
-    const size_t budget = trace_budget("PA_AFFINE_TRACE_BUDGET_MB");
-    std::vector<uint32_t> want;
-    for (const uint32_t p : ab->order)
-        if (offsets[p] != UINT64_MAX) {
-            if (((size_t)ab->n[p] + 1) * 4 > budget)
-                return fail(PA_E_ARG, "pa_affine_batch_last_row: pair %u: %zu bytes of last row exceed the budget of %zu bytes", p, ((size_t)ab->n[p] + 1) * 4,
-                            budget);
-            want.push_back(p);
-        }
-    hipStream_t s = 0;
-    DeviceBuf d_rows, d_off;
-    if (!ab->d_end.reserve(ab->np * 4)) return PA_E_HIP;
-    std::vector<uint64_t> off(ab->np);
-    std::vector<int32_t> rows;
-    for (size_t c0 = 0; c0 < want.size();) {
-        std::fill(off.begin(), off.end(), UINT64_MAX);
-        size_t c1 = c0, words = 0;
-        while (c1 < want.size() && (c1 == c0 || (words + ab->n[want[c1]] + 1) * 4 <= budget)) {
-            off[want[c1]] = words;
-            words += (size_t)ab->n[want[c1]] + 1;
-            ++c1;
-        }
-        const std::vector<uint32_t> ids(want.begin() + c0, want.begin() + c1);
-        Plan P;
-        if (const int rc = affine_host::make_plan<Host>(*ab, ids, P, affine_host::Keep::kNone, nullptr, s)) return rc;
-        rows.resize(words);
-        if (!d_rows.reserve(words * 4) || !upload(d_off, off.data(), off.size() * 8, s)) return PA_E_HIP;
-        const Ends E{ab->d_end.as<int32_t>(), d_rows.as<int32_t>(), d_off.as<uint64_t>()};
-        if (!launch<false>(*ab, P.d_waves.as<Wave>(), P.waves.size(), P.d_pairs.as<Pair>(), s, &E) ||
-            !hip_ok(hipMemcpyAsync(rows.data(), d_rows.ptr, words * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))
-            return PA_E_HIP;
-        for (const uint32_t p : ids) std::memcpy(out + offsets[p], rows.data() + off[p], ((size_t)ab->n[p] + 1) * 4);
-        c0 = c1;
-    }
-    return 0;
+    return affine_host::last_row<Host>(ab, out, offsets);
 }
 
 extern "C" void pa_affine_batch_chain_info(const pa_affine_batch* ab, double* on, double* chain_pairs, double* chain_jobs, double* chunks,

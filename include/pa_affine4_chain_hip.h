@@ -6,7 +6,7 @@
  * pa_affine4_batch_run and in the checkpoint pass of pa_affine4_batch_align_tiled every strip of such a pair is a job of its own, run by
  * its own wavefront, and strip s + 1 reads the last row of strip s while strip s is still writing it; pairs with |b| <= 1024 keep their
  * plan and their launch.  Costs and CIGARs are byte for byte those of on = 0.  pa_affine4_batch_align (a code byte per cell) has no
- * chained form and ignores the setting.  Global mode only, as the whole batch type.
+ * chained form and ignores the setting.  The ends-free setting (pa_affine4_ends_hip.h) holds in the chained passes too.
  *
  * Memory: a chained pair needs (strips - 1) * (|a| + 1) * 16 bytes of boundary rows, strips = ceil(|b| / 1024): M, I1, I2 of the
  * strip's last row per column, written and read as two 8-byte halves.  pa_affine4_batch_run cuts the chained pairs into chunks whose

@@ -2,7 +2,7 @@
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
     python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
-                                 [--dt-seg] [--double] [--double-tiled] [--double-chain] [--models affine,unit]
+                                 [--dt-seg] [--double] [--double-tiled] [--double-chain] [--double-ends] [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
 tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
@@ -51,7 +51,10 @@ rounds, tile jobs, the cells re-filled and the bytes of the largest chunk, also 
 says: one 100 kbp pair, 16 of them, 4096 x 10 kbp and the reads (which have no pair to chain), with the long indels of --double.  Cost
 only, the tiled forward pass and traced in all, chained and unchained alternating on one batch, each warmed once and then R times, the
 results compared in every round.  Every shape runs in a process of its own under a wall-clock limit sized for its unchained passes (a
-100 kbp pair alone on a wavefront takes 7 to 10 s a pass)."""
+100 kbp pair alone on a wavefront takes 7 to 10 s a pass).
+
+--double-ends is --ends' protocol and mapping shapes on an Affine4Batch under double_affine(4, 6, 2, 24, 1) (Affine4Batch.set_free_ends):
+cost-only, traced and tiled (at --tile-cols, by default the library's 1024), global and ends-free alternating on one batch."""
 from __future__ import annotations
 
 import argparse
@@ -432,10 +435,10 @@ def dt_ends_legs(title, pairs, cm, mname, fs, fe):
           flush=True)
 
 
-def ends_legs(title, pairs, tp, cm, mname, tile_cols, reps):
+def ends_legs(title, pairs, tp, cm, mname, tile_cols, reps, Batch=AffineBatch):
     """Global and ends-free, alternating: run() on a batch of `pairs`, align() and align_tiled() on a traced batch of `tp`."""
     cells, tcells = float(sum(len(x) * len(y) for x, y in pairs)), float(sum(len(x) * len(y) for x, y in tp))
-    b, tb = AffineBatch(pairs, cm), AffineBatch(tp, cm, trace=True)
+    b, tb = Batch(pairs, cm), Batch(tp, cm, trace=True)
     ms = {(leg, on): [] for leg in ("cost", "traced", "tiled") for on in (False, True)}
     inside = 0
     for rep_ in range(reps + 1):  # the first round warms every route
@@ -447,7 +450,7 @@ def ends_legs(title, pairs, tp, cm, mname, tile_cols, reps):
             tb.align()
             u = tb.last_forward_ms + tb.last_trace_ms
             tb.align_tiled(tile_cols)
-            t = tb.last_forward_ms + tb.last_refill_ms + tb.last_trace_ms
+            t = tb.last_forward_ms + tb.last_refill_ms + getattr(tb, Batch._WALK_MS)
             if on:
                 se = tb.ends()
                 inside = int(((se[:, 0] > 0) & (se[:, 1] < np.array([len(x) for x, _ in tp]))).sum())
@@ -513,6 +516,7 @@ def main():
     ap.add_argument("--double-tiled-100k", action="store_true", help=argparse.SUPPRESS)  # the 100 kbp leg of --double-tiled, in a process of its own
     ap.add_argument("--double-chain", action="store_true", help="measure Affine4Batch's chained route against its unchained one instead (see above)")
     ap.add_argument("--double-chain-shape", default="", help=argparse.SUPPRESS)  # one shape of --double-chain, in a process of its own
+    ap.add_argument("--double-ends", action="store_true", help="measure Affine4Batch's ends-free mode against its global one instead (see above)")
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -564,6 +568,12 @@ def main():
             title, pairs = shape(sname, rng)
             pairs = long_indels(rng, pairs)
             double_legs(title + ", indels of 20-200 bp in a quarter", pairs, None if sname == "reads" else pairs[: args.trace_pairs])
+        return
+    if args.double_ends:
+        for sname in ("map150", "map10k"):
+            title, pairs = ends_shape(sname, rng)
+            ends_legs(title, pairs, pairs if sname == "map150" else pairs[: args.trace_pairs], AffineCost.double_affine(4, 6, 2, 24, 1), "double_affine",
+                      args.tile_cols, args.reps, Affine4Batch)
         return
     if args.ends:
         for sname in ("map150", "map10k"):
