@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = [
     "pa_affine4_batch_create", "pa_affine4_batch_run", "pa_affine4_batch_align", "pa_affine4_batch_info", "pa_affine4_batch_destroy",
     "pa_affine4_batch_align_tiled", "pa_affine4_batch_tiled_info", "pa_affine4_batch_set_chain", "pa_affine4_batch_chain_info",
     "pa_affine4_batch_set_free_ends", "pa_affine4_batch_ends", "pa_affine4_batch_last_row",
+    "pa_affine4_batch_run_dt", "pa_affine4_batch_align_dt", "pa_affine4_batch_run_dt_ends", "pa_affine4_batch_align_dt_ends",
+    "pa_affine4_batch_dt_info",
 ]
 
 _lib = None
@@ -151,6 +153,13 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine4_batch_set_free_ends.argtypes = [vp, C.c_int, C.c_int]
         L.pa_affine4_batch_ends.argtypes = [vp, vp, vp]
         L.pa_affine4_batch_last_row.argtypes = [vp, vp, vp]
+    if hasattr(L, "pa_affine4_batch_run_dt"):
+        L.pa_affine4_batch_run_dt.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_float)]
+        L.pa_affine4_batch_align_dt.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.pa_affine4_batch_run_dt_ends.argtypes = [vp, C.c_int, C.c_int, C.c_int32, vp, vp, C.POINTER(C.c_float)]
+        L.pa_affine4_batch_align_dt_ends.argtypes = [vp, C.c_int, C.c_int, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.pa_affine4_batch_dt_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 6
+        L.pa_affine4_batch_dt_info.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -619,7 +628,8 @@ def _s_max_arg(s_max) -> int:
 class _AffineBatchBase:
     """What AffineBatch (pa_affine_batch_*) and Affine4Batch (pa_affine4_batch_*) share: the C functions of either differ in their
     prefix, `_PREFIX`, in the cost structure they take, `_cost_c`, and in where align_tiled() keeps the walk time, `_WALK_MS`.  Both have
-    the chained route (set_chain, chain_info) and ends-free mode (set_free_ends, ends, last_row)."""
+    the chained route (set_chain, chain_info), ends-free mode (set_free_ends, ends, last_row) and the diagonal-transition route (run_dt,
+    align_dt, run_dt_ends, align_dt_ends, dt_info)."""
 
     _PREFIX = ""
     _WALK_MS = "last_trace_ms"
@@ -763,6 +773,82 @@ class _AffineBatchBase:
         self._check(self._fn("last_row")(self._h, _p(out), _p(offs)), f"{self._PREFIX}_last_row")
         return [out[int(offs[p]): int(offs[p]) + len(self._keep[p][0]) + 1].copy() for p in ids]
 
+    @staticmethod
+    def _s_max(s_max) -> int:
+        return _s_max_arg(s_max)
+
+    def run_dt(self, s_max: int) -> np.ndarray:
+        """Costs only, by diagonal transition (WFA) bounded by s_max: int32[npairs], the cost of run() in global mode where it is
+        <= s_max and -1 ("not found") where it is not.  No retry inside: the caller decides what to do with a -1.  The time is kept in
+        `last_kernel_ms`, the counters in dt_info().  ValueError in ends-free mode."""
+        s_max = self._s_max(s_max)
+        costs = np.zeros(max(self.npairs, 1), np.int32)
+        ms = C.c_float(0)
+        self._check(self._fn("run_dt")(self._h, s_max, _p(costs), C.byref(ms)), f"{self._PREFIX}_run_dt")
+        self.last_kernel_ms = float(ms.value)
+        return costs[: self.npairs]
+
+    def align_dt(self, s_max: int) -> list[tuple[int, str]]:
+        """[(cost, CIGAR)] of every pair by diagonal transition bounded by s_max (trace batches only); (-1, "") where the cost exceeds
+        s_max.  Same cost as align(); where several optimal paths exist the CIGAR may be another one of them (DEVIATIONS.md).  The
+        times are kept in `last_forward_ms` and `last_trace_ms`."""
+        s_max = self._s_max(s_max)
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        cig = (C.c_void_p * max(n, 1))()
+        f, t = C.c_float(0), C.c_float(0)
+        rc = self._fn("align_dt")(self._h, s_max, _p(costs), cig, C.byref(f), C.byref(t))
+        try:
+            self._check(rc, f"{self._PREFIX}_align_dt")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
+        return [(int(costs[p]), cigars[p] if costs[p] >= 0 else "") for p in range(n)]
+
+    def run_dt_ends(self, s_max: int, free_start: bool = True, free_end: bool = True) -> tuple[np.ndarray, np.ndarray]:
+        """Costs and ends by ends-free diagonal transition bounded by s_max: (int32[npairs], int64[npairs]), the cost of run() and the
+        end of ends() under set_free_ends(free_start, free_end) where the cost is <= s_max, and -1, -1 where it is not.  The switches
+        belong to this call: the batch's own setting, ends() and every other route are left alone.  With both off: run_dt(), and
+        end = |a|.  The time is kept in `last_kernel_ms`, the counters in dt_info()."""
+        s_max = self._s_max(s_max)
+        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+        costs, ends = np.zeros(max(self.npairs, 1), np.int32), np.zeros(max(self.npairs, 1), np.int64)
+        ms = C.c_float(0)
+        self._check(self._fn("run_dt_ends")(self._h, fs, fe, s_max, _p(costs), _p(ends), C.byref(ms)), f"{self._PREFIX}_run_dt_ends")
+        self.last_kernel_ms = float(ms.value)
+        return costs[: self.npairs], ends[: self.npairs]
+
+    def align_dt_ends(self, s_max: int, free_start: bool = True, free_end: bool = True) -> list[tuple[int, str, int, int]]:
+        """[(cost, CIGAR, start, end)] of every pair by ends-free diagonal transition bounded by s_max (trace batches only): b is placed
+        in a[start:end], which the CIGAR describes; (-1, "", -1, -1) where the cost exceeds s_max.  Cost and end are those of align()
+        under set_free_ends(free_start, free_end); start and the CIGAR may be another optimal placement (DEVIATIONS.md).  The times are
+        kept in `last_forward_ms` and `last_trace_ms`."""
+        s_max = self._s_max(s_max)
+        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        st, en = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        cig = (C.c_void_p * max(n, 1))()
+        f, t = C.c_float(0), C.c_float(0)
+        rc = self._fn("align_dt_ends")(self._h, fs, fe, s_max, _p(costs), _p(st), _p(en), cig, C.byref(f), C.byref(t))
+        try:
+            self._check(rc, f"{self._PREFIX}_align_dt_ends")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
+        return [(int(costs[p]), cigars[p] if costs[p] >= 0 else "", int(st[p]), int(en[p])) for p in range(n)]
+
+    def dt_info(self) -> dict:
+        """The last run_dt() / align_dt() or run_dt_ends() / align_dt_ends(): pairs found and not found, chunks, front cells computed (layers x live diagonals x cost
+        steps), bytes compared while extending, device bytes of the largest chunk."""
+        vals = [C.c_double(0) for _ in range(6)]
+        self._fn("dt_info")(self._h, *[C.byref(v) for v in vals])
+        return {k: int(v.value) for k, v in zip(("found", "not_found", "chunks", "front_cells", "extend_chars", "bytes_max"), vals)}
+
     def close(self):
         if getattr(self, "_h", None):
             self._fn("destroy")(self._h)
@@ -791,74 +877,6 @@ class AffineBatch(_AffineBatchBase):
             self.set_chain(True)
         if free_start or free_end:
             self.set_free_ends(free_start, free_end)
-
-    @staticmethod
-    def _s_max(s_max) -> int:
-        return _s_max_arg(s_max)
-
-    def run_dt(self, s_max: int) -> np.ndarray:
-        """Costs only, by diagonal transition (WFA) bounded by s_max: int32[npairs], the cost of run() in global mode where it is
-        <= s_max and -1 ("not found") where it is not.  No retry inside: the caller decides what to do with a -1.  The time is kept in
-        `last_kernel_ms`, the counters in dt_info().  ValueError in ends-free mode."""
-        costs = np.zeros(max(self.npairs, 1), np.int32)
-        ms = C.c_float(0)
-        self._check(load().pa_affine_batch_run_dt(self._h, self._s_max(s_max), _p(costs), C.byref(ms)), "pa_affine_batch_run_dt")
-        self.last_kernel_ms = float(ms.value)
-        return costs[: self.npairs]
-
-    def align_dt(self, s_max: int) -> list[tuple[int, str]]:
-        """[(cost, CIGAR)] of every pair by diagonal transition bounded by s_max (trace batches only); (-1, "") where the cost exceeds
-        s_max.  Same cost as align(); where several optimal paths exist the CIGAR may be another one of them (DEVIATIONS.md).  The
-        times are kept in `last_forward_ms` and `last_trace_ms`."""
-        s_max = self._s_max(s_max)
-        L = load()
-        n = self.npairs
-        costs = np.zeros(max(n, 1), np.int32)
-        cig = (C.c_void_p * max(n, 1))()
-        f, t = C.c_float(0), C.c_float(0)
-        rc = L.pa_affine_batch_align_dt(self._h, s_max, _p(costs), cig, C.byref(f), C.byref(t))
-        try:
-            self._check(rc, "pa_affine_batch_align_dt")
-            cigars = _c_strings(cig, n)
-        finally:
-            L.pa_free_cigars(cig, n)
-        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
-        return [(int(costs[p]), cigars[p] if costs[p] >= 0 else "") for p in range(n)]
-
-    def run_dt_ends(self, s_max: int, free_start: bool = True, free_end: bool = True) -> tuple[np.ndarray, np.ndarray]:
-        """Costs and ends by ends-free diagonal transition bounded by s_max: (int32[npairs], int64[npairs]), the cost of run() and the
-        end of ends() under set_free_ends(free_start, free_end) where the cost is <= s_max, and -1, -1 where it is not.  The switches
-        belong to this call: the batch's own setting, ends() and every other route are left alone.  With both off: run_dt(), and
-        end = |a|.  The time is kept in `last_kernel_ms`, the counters in dt_info()."""
-        s_max = self._s_max(s_max)
-        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
-        costs, ends = np.zeros(max(self.npairs, 1), np.int32), np.zeros(max(self.npairs, 1), np.int64)
-        ms = C.c_float(0)
-        self._check(load().pa_affine_batch_run_dt_ends(self._h, fs, fe, s_max, _p(costs), _p(ends), C.byref(ms)), "pa_affine_batch_run_dt_ends")
-        self.last_kernel_ms = float(ms.value)
-        return costs[: self.npairs], ends[: self.npairs]
-
-    def align_dt_ends(self, s_max: int, free_start: bool = True, free_end: bool = True) -> list[tuple[int, str, int, int]]:
-        """[(cost, CIGAR, start, end)] of every pair by ends-free diagonal transition bounded by s_max (trace batches only): b is placed
-        in a[start:end], which the CIGAR describes; (-1, "", -1, -1) where the cost exceeds s_max.  Cost and end are those of align()
-        under set_free_ends(free_start, free_end); start and the CIGAR may be another optimal placement (DEVIATIONS.md).  The times are
-        kept in `last_forward_ms` and `last_trace_ms`."""
-        s_max = self._s_max(s_max)
-        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
-        L = load()
-        n = self.npairs
-        costs = np.zeros(max(n, 1), np.int32)
-        st, en = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
-        cig = (C.c_void_p * max(n, 1))()
-        f, t = C.c_float(0), C.c_float(0)
-        rc = L.pa_affine_batch_align_dt_ends(self._h, fs, fe, s_max, _p(costs), _p(st), _p(en), cig, C.byref(f), C.byref(t))
-        try:
-            self._check(rc, "pa_affine_batch_align_dt_ends")
-            cigars = _c_strings(cig, n)
-        finally:
-            L.pa_free_cigars(cig, n)
-        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
-        return [(int(costs[p]), cigars[p] if costs[p] >= 0 else "", int(st[p]), int(en[p])) for p in range(n)]
 
     def align_dt_seg(self, s_max: int, seg: int = 0, free_start: bool = False, free_end: bool = False) -> list[tuple[int, str, int, int]]:
         """align_dt_ends(s_max, free_start, free_end) in device memory that grows with the square root of the cost: the same
@@ -893,13 +911,6 @@ class AffineBatch(_AffineBatchBase):
         load().pa_affine_batch_dt_seg_info(self._h, *[C.byref(v) for v in vals])
         return {k: int(v.value) for k, v in zip(("chunks", "rounds", "seg_jobs", "refill_cells", "bytes_max"), vals)}
 
-    def dt_info(self) -> dict:
-        """The last run_dt() / align_dt() or run_dt_ends() / align_dt_ends(): pairs found and not found, chunks, front cells computed (layers x live diagonals x cost
-        steps), bytes compared while extending, device bytes of the largest chunk."""
-        vals = [C.c_double(0) for _ in range(6)]
-        load().pa_affine_batch_dt_info(self._h, *[C.byref(v) for v in vals])
-        return {k: int(v.value) for k, v in zip(("found", "not_found", "chunks", "front_cells", "extend_chars", "bytes_max"), vals)}
-
 
 def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False, s_max: int | None = None) -> list[tuple[int, str]]:
     """[(cost, CIGAR)] of every pair under the gap-affine cost model `cm` (one traced AffineBatch); tiled=True takes the
@@ -928,7 +939,10 @@ class Affine4Batch(_AffineBatchBase):
     are the same.  set_free_ends(free_start, free_end) (include/pa_affine4_ends_hip.h) makes the ends of a, the text, free in all of
     these routes: the pattern b is placed in a[start:end] (ends()), and last_row() gives M(i, |b|) of every column; map_affine does
     all of it in one call.  (The constructor keeps its four arguments, which tests/test_affine4_chain_api.py pins: the switches are set
-    on the batch.)  Not supported: diagonal transition, which is AffineBatch's, for two layers."""
+    on the batch.)  run_dt(s_max) / align_dt(s_max) and run_dt_ends / align_dt_ends (include/pa_affine4_dt_hip.h) take the
+    diagonal-transition route over the five layers, bounded by s_max: the choice for long pairs of low divergence (DESIGN.md has the
+    measurements); map_affine_dt does the ends-free traced form in one call.  Not supported: a segmented DT traceback (align_dt_seg),
+    which is AffineBatch's, for two layers."""
 
     _PREFIX = "pa_affine4_batch"
     _WALK_MS = "last_walk_ms"
@@ -987,6 +1001,21 @@ def map_affine(pairs, cm: AffineCost, free_start: bool = True, free_end: bool = 
         res = b.align_tiled() if tiled else b.align()
         se = b.ends()
         return [(c, g, int(se[p, 0]), int(se[p, 1])) for p, (c, g) in enumerate(res)]
+    finally:
+        b.close()
+
+
+def map_affine_dt(pairs, cm: AffineCost, s_max: int, free_start: bool = True, free_end: bool = True) -> list[tuple[int, str, int, int]]:
+    """[(cost, CIGAR, start, end)] of every pair (a the text, b the pattern) by ends-free diagonal transition bounded by s_max, under a
+    model of at most two layers (one traced AffineBatch) or of four (one traced Affine4Batch): align_dt_ends(s_max, free_start,
+    free_end) of either.  (-1, "", -1, -1) for a pair whose cost exceeds s_max."""
+    s_max = _s_max_arg(s_max)
+    free_start, free_end = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+    if not isinstance(cm, AffineCost):
+        raise ValueError("cm must be an AffineCost")
+    b = (Affine4Batch if len(cm.layers) == 4 else AffineBatch)(pairs, cm, trace=True)
+    try:
+        return b.align_dt_ends(s_max, free_start, free_end)
     finally:
         b.close()
 

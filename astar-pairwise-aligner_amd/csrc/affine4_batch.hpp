@@ -12,6 +12,12 @@
 #include <string>
 #include <vector>
 
+namespace pa {
+namespace affine4 {
+struct DtState;  // affine4_dt_view.hpp
+}
+}  // namespace pa
+
 struct pa_affine4_batch : pa::affine_host::Batch<pa::affine4::Pair, pa::affine4::Wave> {
     pa::affine4::Costs C{};
     pa::affine_host::ChainState<pa::affine_host::Plan<pa::affine4::Pair, pa::affine4::Wave>> chain;  // set_chain
@@ -20,6 +26,7 @@ struct pa_affine4_batch : pa::affine_host::Batch<pa::affine4::Pair, pa::affine4:
     uint32_t free_ends = 0;
     pa::DeviceBuf d_end;
     pa::affine_host::EndsState ends;
+    pa::affine4::DtState* dt = nullptr;  // the diagonal-transition route's own state (affine4_dt_unit.hip)
 };
 
 namespace pa {

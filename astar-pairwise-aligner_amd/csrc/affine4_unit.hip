@@ -11,10 +11,12 @@
 // affine_chain_host.hpp's, shared likewise.  set_free_ends() (include/pa_affine4_ends_hip.h) makes the ends of a free in all of these
 // routes: the launches then pick the kernels' ENDS instantiations, which leave every pair's end in d_end; the walks start there, and
 // pa_affine4_batch_ends reports where they started and stopped.  last_row() is a cost-only pass of its own that also stores row |b|.
-// The host side of all three is affine_host.hpp's, shared with the two-layer batch.  Not supported: diagonal transition, other layer
-// lists.
+// The host side of all three is affine_host.hpp's, shared with the two-layer batch.  The diagonal-transition route (run_dt, align_dt and
+// their ends-free forms, include/pa_affine4_dt_hip.h) is a unit of its own, affine4_dt_unit.hip, which sees a batch through dt_view().
+// Not supported: other layer lists.
 #include "affine4_kernel.hpp"
 #include "affine4_batch.hpp"
+#include "affine4_dt_view.hpp"
 #include "../../include/pa_affine4_chain_hip.h"
 #include "../../include/pa_affine4_ends_hip.h"
 
@@ -22,6 +24,20 @@
 
 using namespace pa;
 using namespace pa::affine4;
+
+// What the diagonal-transition route (affine4_dt_unit.hip) reads of a batch: open_t = oe[t] - e[t].
+DtView pa::affine4::dt_view(pa_affine4_batch* ab) {
+    static_assert(dt::kAbsent == kInf, "an absent edge");
+    const Costs& C = ab->C;
+    dt::Costs D{C.sub, C.ins, C.del, {}, {}};
+    for (int t = 0; t < 4; ++t) {
+        D.open[t] = C.oe[t] - C.e[t];
+        D.ext[t] = C.e[t];
+    }
+    const size_t seq_bytes = ab->np ? ab->boff[ab->np - 1] + ab->m[ab->np - 1] : 0;  // (b of the last pair ends d_seq)
+    return DtView{ab->np, ab->trace, D, ab->free_ends, ab->n.data(), ab->m.data(), ab->aoff.data(), ab->boff.data(), ab->d_seq.as<uint8_t>(),
+                  seq_bytes, &ab->dt};
+}
 
 namespace {
 
@@ -167,5 +183,6 @@ extern "C" int pa_affine4_batch_last_row(pa_affine4_batch* ab, int32_t* out, con
 extern "C" void pa_affine4_batch_destroy(pa_affine4_batch* ab) {
     if (!ab) return;
     (void)hipDeviceSynchronize();
+    dt_release(ab->dt);
     delete ab;
 }

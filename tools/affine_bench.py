@@ -2,7 +2,8 @@
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
     python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
-                                 [--dt-seg] [--double] [--double-tiled] [--double-chain] [--double-ends] [--models affine,unit]
+                                 [--dt-seg] [--double] [--double-tiled] [--double-chain] [--double-ends] [--double-dt] [--double-dt-ends]
+                                 [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
 tiled route's are its checkpoint pass, tile fills and walks.  Both routes run on one batch, each warmed once and then R times in turn;
@@ -54,7 +55,15 @@ results compared in every round.  Every shape runs in a process of its own under
 100 kbp pair alone on a wavefront takes 7 to 10 s a pass).
 
 --double-ends is --ends' protocol and mapping shapes on an Affine4Batch under double_affine(4, 6, 2, 24, 1) (Affine4Batch.set_free_ends):
-cost-only, traced and tiled (at --tile-cols, by default the library's 1024), global and ends-free alternating on one batch."""
+cost-only, traced and tiled (at --tile-cols, by default the library's 1024), global and ends-free alternating on one batch.
+
+--double-dt is --dt's protocol on an Affine4Batch under double_affine(4, 6, 2, 24, 1) (Affine4Batch.run_dt), whatever --shapes says (or the
+shapes of --shapes that carry an @): reads@5, 10k@1, 10k@3, 10k@5, 10k@8 and 100k@5 with run() chained.  One batch in one process, run() and
+run_dt(largest cost) alternating, each warmed once and then three times; the fastest repeats, their ratio and dt_info().  The same pairs
+then go through AffineBatch.run_dt under affine(4, 6, 2) at that model's largest cost, the second column: what five layers cost over three.
+
+--double-dt-ends does likewise against the ends-free run() (Affine4Batch.run_dt_ends, both ends free) on the mapping shapes of --dt-ends:
+map150, map10k@1, map10k@3, map10k@5."""
 from __future__ import annotations
 
 import argparse
@@ -353,6 +362,58 @@ def dt_legs(title, pairs, cm, mname, chain):
           flush=True)
 
 
+def double_dt_legs(title, pairs, chain, ends):
+    """Affine4Batch under double_affine(4, 6, 2, 24, 1): run() and run_dt(largest cost) alternating on one batch (ends: the ends-free run()
+    and run_dt_ends, both ends free); then AffineBatch.run_dt under affine(4, 6, 2) on the same pairs."""
+    cm4, cm2 = AffineCost.double_affine(4, 6, 2, 24, 1), AffineCost.affine(4, 6, 2)
+    cells = float(sum(len(x) * len(y) for x, y in pairs))
+    b = Affine4Batch(pairs, cm4, chain=chain)
+    if ends:
+        b.set_free_ends(True, True)
+    want = b.run()
+    want_end = b.ends()[:, 1] if ends else None
+    s_max = int(want.max())
+    nw, dt = [], []
+    for rep in range(4):  # the first round warms both routes
+        c = b.run()
+        k = b.last_kernel_ms
+        if ends:
+            d, e = b.run_dt_ends(s_max, True, True)
+            same = e.tolist() == want_end.tolist()
+        else:
+            d, same = b.run_dt(s_max), True
+        if c.tolist() != want.tolist() or d.tolist() != want.tolist() or not same:
+            raise SystemExit(f"{title}: Affine4Batch.run() and run_dt() disagree")
+        if rep:
+            nw.append(k)
+            dt.append(b.last_kernel_ms)
+    di = b.dt_info()
+    b.close()
+    b2 = AffineBatch(pairs, cm2, chain=chain, free_start=ends, free_end=ends)
+    want2 = b2.run()
+    s2 = int(want2.max())
+    dt2 = []
+    for rep in range(4):
+        d = b2.run_dt_ends(s2, True, True)[0] if ends else b2.run_dt(s2)
+        if d.tolist() != want2.tolist():
+            raise SystemExit(f"{title}: AffineBatch.run() and run_dt() disagree")
+        if rep:
+            dt2.append(b2.last_kernel_ms)
+    di2 = b2.dt_info()
+    b2.close()
+    k0, k1, k2 = min(nw), min(dt), min(dt2)
+    call = "run_dt_ends" if ends else "run_dt"
+    print(f"{title:44s} double_affine  run(){' chained' if chain else ''}{' ends-free' if ends else ''}: {k0:10.2f} ms {cells / k0 / 1e6:8.1f} GCUPS |"
+          f" {call}(s_max={s_max}): {k1:10.2f} ms {len(pairs) / k1 * 1e3:12.0f} pairs/s | run / {call} {k0 / k1:7.3f}"
+          f"  (repeats {' '.join(f'{x:.2f}' for x in nw)} | {' '.join(f'{x:.2f}' for x in dt)})", flush=True)
+    print(f"{'':44s} double_affine  dt_info: front_cells {di['front_cells']:.4g} ({di['front_cells'] / cells:.4f} of |a||b|), extend_chars"
+          f" {di['extend_chars']:.4g}, chunks {di['chunks']}, {di['bytes_max'] / 2**20:.1f} MiB, found {di['found']}, mean cost {float(want.mean()):.1f}",
+          flush=True)
+    print(f"{'':44s} affine(4,6,2)  {call}(s_max={s2}): {k2:10.2f} ms | four-layer / two-layer DT {k1 / k2:7.3f}  (repeats"
+          f" {' '.join(f'{x:.2f}' for x in dt2)}); front_cells {di2['front_cells']:.4g}, extend_chars {di2['extend_chars']:.4g},"
+          f" {di2['bytes_max'] / 2**20:.1f} MiB, mean cost {float(want2.mean()):.1f}", flush=True)
+
+
 def dt_seg_legs(title, pairs, cm, mname):
     """align_dt_ends(largest cost) and align_dt_seg(largest cost), both switches off, in turn on one traced batch."""
     b = AffineBatch(pairs, cm, trace=True)
@@ -517,6 +578,8 @@ def main():
     ap.add_argument("--double-chain", action="store_true", help="measure Affine4Batch's chained route against its unchained one instead (see above)")
     ap.add_argument("--double-chain-shape", default="", help=argparse.SUPPRESS)  # one shape of --double-chain, in a process of its own
     ap.add_argument("--double-ends", action="store_true", help="measure Affine4Batch's ends-free mode against its global one instead (see above)")
+    ap.add_argument("--double-dt", action="store_true", help="measure Affine4Batch.run_dt() against Affine4Batch.run() instead (see above)")
+    ap.add_argument("--double-dt-ends", action="store_true", help="measure Affine4Batch.run_dt_ends() against the ends-free Affine4Batch.run() instead (see above)")
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -568,6 +631,19 @@ def main():
             title, pairs = shape(sname, rng)
             pairs = long_indels(rng, pairs)
             double_legs(title + ", indels of 20-200 bp in a quarter", pairs, None if sname == "reads" else pairs[: args.trace_pairs])
+        return
+    if args.double_dt:
+        for sname in [x for x in args.shapes.split(",") if "@" in x] or ["reads@5", "10k@1", "10k@3", "10k@5", "10k@8", "100k@5"]:
+            title, pairs = shape(sname, rng)
+            if "at 5 %" not in title and sname.endswith("@5"):
+                title += " at 5 %"
+            double_dt_legs(title, pairs, sname.startswith("100k"), False)
+        return
+    if args.double_dt_ends:
+        for sname in [x for x in args.shapes.split(",") if x.startswith("map")] or ["map150", "map10k@1", "map10k@3", "map10k@5"]:
+            name, _, pct = sname.partition("@")
+            title, pairs = ends_shape(name, rng, float(pct or 5) / 100)
+            double_dt_legs(f"{title} at {pct or 5} %", pairs, False, True)
         return
     if args.double_ends:
         for sname in ("map150", "map10k"):
