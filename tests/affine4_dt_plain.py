@@ -87,8 +87,9 @@ def cigar_text(ops) -> str:
     return "".join(("" if k == 1 else str(k)) + _PRINT.get(op, op) for op, k in out)
 
 
-def affine4_dt(a: bytes, b: bytes, cm, s_max: int, free_start: bool = False, free_end: bool = False):
-    """-> (cost, CIGAR, start, end), or (-1, "", -1, -1) when the cost exceeds s_max."""
+def affine4_dt(a: bytes, b: bytes, cm, s_max: int, free_start: bool = False, free_end: bool = False, raw: bool = False):
+    """-> (cost, CIGAR, start, end), or (-1, "", -1, -1) when the cost exceeds s_max; with raw the walk's ops before printing, one
+    character a step (affine4_plain.affine4_nw), in place of the CIGAR."""
     n, m = len(a), len(b)
     A = np.frombuffer(a, np.uint8)
     B = np.frombuffer(b, np.uint8)
@@ -187,4 +188,4 @@ def affine4_dt(a: bytes, b: bytes, cm, s_max: int, free_start: bool = False, fre
                     assert Ls[t].at(s - ex[t], k - 1) + 1 == i
                     s = s - ex[t]
                 k, i = k - 1, i - 1
-    return cost, cigar_text(ops[::-1]), start, end
+    return cost, "".join(ops[::-1]) if raw else cigar_text(ops[::-1]), start, end

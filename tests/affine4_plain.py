@@ -27,8 +27,9 @@ def _model(cm):
     return cm.sub, cm.ins, cm.del_, [int(o) for _, o, _ in cm.layers], [int(e) for _, _, e in cm.layers]
 
 
-def affine4_nw(a: bytes, b: bytes, cm, trace: bool = True):
-    """-> (cost, CIGAR or None)."""
+def affine4_nw(a: bytes, b: bytes, cm, trace: bool = True, raw: bool = False):
+    """-> (cost, CIGAR or None); with raw the walk's ops before printing, one character a step ('=', 'X', linear 'I' / 'D', and
+    _LAYER_OPS for a step inside layer 0 .. 3), in place of the CIGAR."""
     sub, ins, dl, op, ex = _model(cm)
     n, m = len(a), len(b)
     A = np.frombuffer(a, np.uint8).astype(np.int64)
@@ -77,13 +78,13 @@ def affine4_nw(a: bytes, b: bytes, cm, trace: bool = True):
     cost = int(M1[n])
     if not trace:
         return cost, None
-    return cost, _walk(a, b, codes)
+    return cost, _walk(a, b, codes, raw)
 
 
 _LAYER_OPS = "idje"  # a step inside layer 0 .. 3: distinct ops, so that only gaps of one layer merge
 
 
-def _walk(a, b, codes) -> str:
+def _walk(a, b, codes, raw=False) -> str:
     i, j, layer = len(a), len(b), 0  # layer: 0 main, 1 + k for layer k
     ops = []
     while (i, j, layer) != (0, 0, 0):
@@ -112,6 +113,8 @@ def _walk(a, b, codes) -> str:
             if not c & (8 << k):
                 layer = 0
         assert i >= 0 and j >= 0
+    if raw:
+        return "".join(ops[::-1])
     out = []
     for op in ops[::-1]:
         if out and out[-1][0] == op:

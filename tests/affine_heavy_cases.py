@@ -30,6 +30,14 @@ MODELS4 = {
     "asymmetric_heavy": AffineCost(800, None, 850, [("ins", 50, 1000), ("del", 300, 600), ("ins", 900, 450), ("del", 1000, 350)]),
     # no substitution, no linear edge; piece 2 wins from length 3 (1000 + 3 * 500 < 200 + 3 * 800)
     "no_sub4_heavy": AffineCost(None, None, None, [("ins", 200, 800), ("del", 200, 800), ("ins", 1000, 500), ("del", 1000, 500)]),
+    # cheap_sub with four layers: dense fronts, no layer opens before s = 998; the main ring of the DT route has 1001 live slots while
+    # the layer rings have 2, 2, 3 and 4 and wrap hundreds of times for each wrap of the main one.  Both pieces cost 1001 at length 1
+    # (1000 + 1 = 999 + 2 = 998 + 3: the layer order decides); piece 1 wins above that
+    "dense4": AffineCost(1, None, None, [("ins", 1000, 1), ("del", 1000, 1), ("ins", 999, 2), ("del", 998, 3)]),
+    # E = 1000 comes from the main layer's own edges (sub 1000, linear 999 / 998), every open is below 300 and an extend reaches 1000:
+    # layer rings of 1001, 521, 781 and 301 slots.  The linear insert wins at length 1 (999 < 299 + 780), layer 2 from 2; layer 0 never
+    # wins; layer 1 wins a deletion of 1 (530 < 599), layer 3 from 2; the linear delete never wins
+    "main_edge4": AffineCost(1000, 999, 998, [("ins", 290, 1000), ("del", 10, 520), ("ins", 299, 780), ("del", 299, 300)]),
 }
 
 FOREIGN = b"NRYK"  # bytes the flanks do not have: a gap of them has one best place
@@ -97,17 +105,26 @@ def dt_mutated(seed=45):
 FAR = 70
 
 
-def dt_far(seed=46):
-    """|a| - |b| = +-70 around a core of 12 bytes: the end diagonal lies outside the first 64 lanes while a cost step reaches
-    nowhere.  The surplus is foreign and split 30 / 40 around the core: two gaps, 72 000 costs under flat_1000."""
+def dt_far(seed=46, far=FAR, first=30):
+    """|a| - |b| = +-far (70) around a core of 12 bytes: the end diagonal lies outside the first 64 lanes while a cost step reaches
+    nowhere.  The surplus is foreign and split first / far - first (30 / 40) around the core: two gaps, 72 000 costs under flat_1000."""
     rng = np.random.default_rng(seed)
     core = rand_seq(rng, 12)
-    long_ = rand_seq(rng, 30, FOREIGN) + core + rand_seq(rng, FAR - 30, FOREIGN)
+    long_ = rand_seq(rng, first, FOREIGN) + core + rand_seq(rng, far - first, FOREIGN)
     return [(long_, core), (core, long_)]
 
 
 def dt_cases():
     return dict(dt_small=dt_small(), dt_ladder=dt_ladder(), dt_gap=dt_gap(), dt_runs=dt_runs(), dt_mutated=dt_mutated(), dt_far=dt_far())
+
+
+FAR4 = 65  # the smallest surplus with |a| - |b| above 64: the end diagonal stays outside the first wavefront's first pass
+
+
+def dt4_cases():
+    """The lists of the four-layer DT tests: dt_cases() with every second rung of the ladder (2, 4 .. 12 substitutions) and a far pair
+    of surplus FAR4 = 65, split 25 / 40 (12 + 65 against 12): the plain four-layer DT pays for five layers a cost step."""
+    return dict(dt_cases(), dt_ladder=dt_ladder()[1::2], dt_far=dt_far(far=FAR4, first=25))
 
 
 SEG_CASES = ("dt_small", "dt_ladder", "dt_gap", "dt_mutated")  # the batch of the segmented route's test
@@ -128,6 +145,72 @@ def dt_oracle_case(name, case):
 def dt_oracle(name):
     """{case: [(cost, CIGAR)]} of every case under MODELS[name]."""
     return {c: dt_oracle_case(name, c) for c in dt_cases()}
+
+
+DT4_ORACLE = {}  # (model, case) -> [(cost, CIGAR)] of the plain four-layer DT, shared like DT_ORACLE
+
+
+def dt4_oracle_case(name, case):
+    """[(cost, CIGAR)] of dt4_cases()[case] under MODELS4[name] by the plain four-layer DT without a bound, computed once."""
+    from tests.affine4_dt_plain import affine4_dt
+
+    if (name, case) not in DT4_ORACLE:
+        DT4_ORACLE[name, case] = [affine4_dt(x, y, MODELS4[name], LIMIT - 1)[:2] for x, y in dt4_cases()[case]]
+    return DT4_ORACLE[name, case]
+
+
+DT4_ENDS_MODELS = ("double_heavy", "dense4", "main_edge4")  # the models of the ends-free and the pair-by-pair four-layer DT tests
+
+
+def dt4_ends_oracle(name, fs, fe):
+    """[(cost, CIGAR, start, end)] of dt_planted() under MODELS4[name] by the plain ends-free four-layer DT, computed once."""
+    from tests.affine4_dt_plain import affine4_dt
+
+    if (name, fs, fe) not in DT4_ORACLE:
+        DT4_ORACLE[name, fs, fe] = [affine4_dt(x, y, MODELS4[name], LIMIT - 1, fs, fe) for x, y in dt_planted()]
+    return DT4_ORACLE[name, fs, fe]
+
+
+WIDE_N = 300
+
+
+def dt4_wide(seed=50):
+    """Four pairs of about 300 bytes at 10 % for the dense model: a cost of 1130 or more there pays for gaps of 131 bytes each way,
+    so the mean W of the batch at its largest cost is above 256 and its blocks are four wavefronts wide."""
+    rng = np.random.default_rng(seed)
+    pairs = []
+    for _ in range(4):
+        x = rand_seq(rng, WIDE_N)
+        pairs.append((x, mutate(rng, x, 0.10)))
+    return pairs
+
+
+def dt4_wide_oracle():
+    from tests.affine4_dt_plain import affine4_dt
+
+    if "wide" not in DT4_ORACLE:
+        DT4_ORACLE["wide"] = [affine4_dt(x, y, MODELS4["dense4"], LIMIT - 1)[:2] for x, y in dt4_wide()]
+    return DT4_ORACLE["wide"]
+
+
+def fill_dt4_oracle(workers=8):
+    """DT4_ORACLE for every (model, case) of the four-layer DT tests, the ends-free lists and the wide batch that it does not hold
+    yet: about 150 s of the plain oracle in one process, so fresh worker processes take a key each (started, not forked)."""
+    import multiprocessing
+    import os
+    from concurrent.futures import ProcessPoolExecutor
+
+    keys = [(name, c) for name in MODELS4 for c in dt4_cases() if (name, c) not in DT4_ORACLE]
+    ends = [(name, fs, fe) for name in DT4_ENDS_MODELS for fs in (False, True) for fe in (False, True) if (name, fs, fe) not in DT4_ORACLE]
+    if keys or ends or "wide" not in DT4_ORACLE:
+        with ProcessPoolExecutor(max_workers=min(workers, os.cpu_count() or 1), mp_context=multiprocessing.get_context("spawn")) as pool:
+            wide = pool.submit(dt4_wide_oracle)
+            res = list(pool.map(dt4_oracle_case, *zip(*keys))) if keys else []
+            eres = list(pool.map(dt4_ends_oracle, *zip(*ends))) if ends else []
+            DT4_ORACLE["wide"] = wide.result()
+        DT4_ORACLE.update(zip(keys, res))
+        DT4_ORACLE.update(zip(ends, eres))
+    return DT4_ORACLE
 
 
 def dt_planted(seed=47):

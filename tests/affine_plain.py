@@ -24,8 +24,9 @@ def edge_costs(cm):
     return (cm.sub, cm.ins, cm.del_, il and il[0], il and il[1], dl and dl[0], dl and dl[1])
 
 
-def affine_nw(a: bytes, b: bytes, cm, trace: bool = True):
-    """-> (cost, CIGAR or None)."""
+def affine_nw(a: bytes, b: bytes, cm, trace: bool = True, raw: bool = False):
+    """-> (cost, CIGAR or None); with raw the walk's ops before printing, one character a step ('=', 'X', linear 'I' / 'D', affine
+    'i' / 'd'), in place of the CIGAR."""
     if len(cm.layers) > 2 or [k for k, _, _ in cm.layers] not in ([], ["ins", "del"]):
         raise ValueError("N in {0, 2} only")
     n, m = len(a), len(b)
@@ -69,10 +70,10 @@ def affine_nw(a: bytes, b: bytes, cm, trace: bool = True):
     cost = int(M1[n])
     if not trace:
         return cost, None
-    return cost, _walk(a, b, codes)
+    return cost, _walk(a, b, codes, raw)
 
 
-def _walk(a, b, codes) -> str:
+def _walk(a, b, codes, raw=False) -> str:
     i, j, layer = len(a), len(b), 0
     ops = []  # from the end: '=', 'X', 'I', 'D' (linear), 'i', 'd' (affine)
     while (i, j, layer) != (0, 0, 0):
@@ -99,6 +100,8 @@ def _walk(a, b, codes) -> str:
             i -= 1
             layer = 2 if c & 16 else 0
         assert i >= 0 and j >= 0
+    if raw:
+        return "".join(ops[::-1])
     return cigar_text(ops[::-1])
 
 

@@ -4,8 +4,9 @@ are exercised; the gaps have the lengths at which the linear edge and the pieces
 pairs are open at their edges; and the closed forms of the thin pairs next to 2^30 are those of the plain DP.  This is what keeps
 tests/test_gpu_affine_heavy.py from passing for a dull reason.
 
-Measured here: the whole file takes 50 to 55 s on 8 cores: 20 s for the plain DT of every DT pair under the six models (a module
-fixture, spread over worker processes; 100 s in one), 9 s for the two segmented plain walks, 5 s for the count of empty fronts."""
+Measured here: the whole file takes 50 to 55 s on 8 cores: 12 to 20 s for the plain DT of every DT pair under the six models (a module
+fixture, spread over worker processes; 100 s in one), 18 s for the four-layer DT under the five models of MODELS4 with the ends-free
+lists and the wide batch (the same way; 150 s in one), 9 s for the two segmented plain walks, 5 s for the count of empty fronts."""
 import multiprocessing
 import os
 from concurrent.futures import ProcessPoolExecutor
@@ -234,3 +235,94 @@ def test_planted_pairs_for_the_ends_free_route():
     res = [affine_dt_ends(x, y, MODELS["flat_1000"], BIG, True, True) for x, y in pairs]
     assert any(0 < st and en < len(x) and c > 2 * E for (x, _), (c, st, en, _) in zip(pairs, res))
     assert any(en == len(x) for (x, _), (c, st, en, _) in zip(pairs, res)) and any(st == 0 for c, st, en, _ in res)
+
+
+# ---- the four-layer DT route at heavy costs
+
+DT4 = cases.dt4_cases()
+DENSE, MAIN_EDGE = "dense4", "main_edge4"
+
+
+@pytest.fixture(scope="module")
+def dt4():
+    """{model: {case: [(cost, CIGAR)]}} by the plain four-layer DT, once, a (model, case) to a worker process like `dt` above
+    (cases.fill_dt4_oracle); the ends-free lists and the wide batch of the GPU tests go along."""
+    cases.fill_dt4_oracle()
+    return {name: {c: cases.DT4_ORACLE[name, c] for c in DT4} for name in MODELS4}
+
+
+def main_edge4(cm):
+    """pa::affine4::dt main_edge restated: the largest edge at which the main layer is read (sub, ins, del and the four opens)."""
+    return max([v for v in (cm.sub, cm.ins, cm.del_) if v is not None] + [o for _, o, _ in cm.layers])
+
+
+def ring_depths(cm):
+    """The five ring depths of a cost-only four-layer DT call (shape_of restated): main_edge + 1, and extend_t + 1 per layer."""
+    return [main_edge4(cm) + 1] + [e + 1 for _, _, e in cm.layers]
+
+
+def test_four_layer_models_are_what_the_names_say():
+    assert sorted(MODELS4) == ["asymmetric_heavy", "dense4", "double_heavy", "main_edge4", "no_sub4_heavy"]
+    dense, edge = MODELS4[DENSE], MODELS4[MAIN_EDGE]
+    assert ring_depths(dense) == [1001, 2, 2, 3, 4] and dense.sub == 1 and dense.ins is None and dense.del_ is None
+    assert min(o for _, o, _ in dense.layers) >= 998  # no layer opens before s = 998
+    assert ring_depths(edge) == [1001, 1001, 521, 781, 301]
+    assert main_edge4(edge) == edge.sub == E and max(o for _, o, _ in edge.layers) < 300 and max(e for _, _, e in edge.layers) == 1000
+    assert (edge.ins, edge.del_) == (999, 998)
+    # depths the first three models never give
+    old = {d for name in ("double_heavy", "asymmetric_heavy", "no_sub4_heavy") for d in ring_depths(MODELS4[name])}
+    assert not {2, 3, 4, 301, 521, 781} & old
+    for name in (DENSE, MAIN_EDGE):
+        MODELS4[name].to_c4()
+    wi = lambda cm, L: cases.gap_w(L, cm.ins, [(o, e) for k, o, e in cm.layers if k == "ins"])  # noqa: E731
+    wd = lambda cm, L: cases.gap_w(L, cm.del_, [(o, e) for k, o, e in cm.layers if k == "del"])  # noqa: E731
+    assert wi(dense, 1) == wd(dense, 1) == 1001 == 999 + 2 == 998 + 3 and wi(dense, cases.GAP) == wd(dense, cases.GAP) == 1020
+    assert [wi(edge, L) for L in (1, 2)] == [999, 299 + 1560] and [wd(edge, L) for L in (1, 2)] == [530, 299 + 600]
+
+
+def test_four_layer_nw_and_dt_costs_agree(dt4):
+    for name, cm in MODELS4.items():
+        for c, pairs in DT4.items():
+            assert len(dt4[name][c]) == len(pairs)
+            for (x, y), (cost, cigar) in zip(pairs, dt4[name][c]):
+                assert cost == a4.affine4_nw(x, y, cm, trace=False)[0], (name, c, len(x), len(y))
+                assert a4.affine4_verify(cigar, x, y, cm) == cost
+            assert all(len(x) <= 120 and len(y) <= 120 for x, y in pairs)
+    far = DT4["dt_far"]
+    assert [len(x) - len(y) for x, y in far] == [cases.FAR4, -cases.FAR4] and cases.FAR4 == 65 > 64
+    assert len(DT4["dt_ladder"]) == 6
+    for (x, y), (cost, cigar) in zip(cases.dt4_wide(), cases.DT4_ORACLE["wide"]):
+        assert cost == a4.affine4_nw(x, y, MODELS4[DENSE], trace=False)[0] and a4.affine4_verify(cigar, x, y, MODELS4[DENSE]) == cost
+    for name in cases.DT4_ENDS_MODELS:
+        from tests.affine4_ends_plain import affine4_ends
+
+        for fs in (False, True):
+            for fe in (False, True):
+                for (x, y), w in zip(cases.dt_planted(), cases.DT4_ORACLE[name, fs, fe]):
+                    c, _, en, _, _ = affine4_ends(x, y, MODELS4[name], fs, fe, trace=False)
+                    assert (c, en) == (w[0], w[3]), (name, fs, fe, len(x), len(y))
+                    assert a4.affine4_verify(w[1], x[w[2]:w[3]], y, MODELS4[name]) == c
+
+
+def test_four_layer_costs_reach_the_mechanisms(dt4):
+    for name in MODELS4:
+        costs = costs_of(dt4, name)
+        if name != DENSE:  # (under the dense model a substitution costs 1 and nothing reaches 20 E)
+            assert max(costs) > 20 * E, name
+            assert any(0 < c < E for c in costs) or MODELS4[name].sub is None, name
+        assert any(c > E for c in costs) and 0 in costs, name
+    dense = costs_of(dt4, DENSE)
+    assert {1, 1001} <= set(dense) and max(dense) > 1001  # the main ring wraps with live fronts, and the layers open
+    assert [c for c, _ in dt4[DENSE]["dt_gap"]] == [1020, 1020]  # 1000 + 20: as derived
+    edge = costs_of(dt4, MAIN_EDGE)
+    assert any(c < E for c in edge) and E in edge and any(c > E for c in edge)  # below, on and above E
+    assert 999 in edge and 530 in edge  # the linear insert, and layer 1, at length 1
+
+
+def test_the_wide_batch_is_wide(dt4):
+    from tests.affine4_dt_plain import mean_w
+
+    want = cases.DT4_ORACLE["wide"]
+    top = max(c for c, _ in want)
+    assert mean_w(cases.dt4_wide(), MODELS4[DENSE], top) > 256 and top > 1130
+    assert len({c for c, _ in want}) >= 3

@@ -69,7 +69,7 @@ def check_info(b, exp, npairs):
     return info
 
 
-def check_global_at(b, pairs, name, want, s_max):
+def check_global_at(b, pairs, cm, want, s_max):
     exp = bounded(want, s_max)
     costs = b.run_dt(s_max)
     assert costs.dtype == np.int32 and costs.tolist() == [w[0] for w in exp], s_max
@@ -79,18 +79,20 @@ def check_global_at(b, pairs, name, want, s_max):
     for p, ((x, y), e, g) in enumerate(zip(pairs, exp, got)):
         assert g == e[:2], (p, len(x), len(y), s_max)
         if g[0] >= 0:
-            assert affine4_verify(g[1], x, y, MODELS[name]) == g[0] and ap.no_adjacent_same_op(g[1])
+            assert affine4_verify(g[1], x, y, cm) == g[0] and ap.no_adjacent_same_op(g[1])
     assert check_info(b, exp, len(pairs))["found"] == info["found"]
 
 
-def check_global(pairs, name):
-    want = oracle(pairs, name)
-    b = Affine4Batch(pairs, MODELS[name], trace=True)
+def check_global(pairs, name, cm=None, want=None):
+    """Under MODELS[name] against oracle(pairs, name); or under `cm` against `want`, [(cost, CIGAR, ..)] of every pair without a bound."""
+    cm = MODELS[name] if cm is None else cm
+    want = oracle(pairs, name) if want is None else want
+    b = Affine4Batch(pairs, cm, trace=True)
     try:
         nw = b.run().tolist()
         assert nw == [w[0] for w in want]  # the DT cost is the NW cost of the same batch
         for s_max in bounds_of(want):
-            check_global_at(b, pairs, name, want, s_max)
+            check_global_at(b, pairs, cm, want, s_max)
         top = bounds_of(want)[0]
         assert b.run_dt(top).tolist() == nw
         first = (b.run_dt(top).tolist(), b.align_dt(top))
@@ -105,7 +107,7 @@ def test_every_global_case_list_and_model(case, name):
     check_global(GLOBAL[case], name)
 
 
-def check_ends_at(b, pairs, name, fs, fe, want, s_max):
+def check_ends_at(b, pairs, cm, fs, fe, want, s_max):
     exp = bounded(want, s_max)
     costs, ends = b.run_dt_ends(s_max, fs, fe)
     assert costs.dtype == np.int32 and ends.dtype == np.int64
@@ -116,16 +118,17 @@ def check_ends_at(b, pairs, name, fs, fe, want, s_max):
     for p, ((x, y), e, g) in enumerate(zip(pairs, exp, got)):
         assert g == e, (p, len(x), len(y), s_max)
         if g[0] >= 0:
-            assert affine4_verify(g[1], x[g[2]:g[3]], y, MODELS[name]) == g[0] and ap.no_adjacent_same_op(g[1])
+            assert affine4_verify(g[1], x[g[2]:g[3]], y, cm) == g[0] and ap.no_adjacent_same_op(g[1])
     assert check_info(b, exp, len(pairs))["found"] == info["found"]
 
 
-def check_ends(pairs, name, fs, fe):
-    want = oracle(pairs, name, fs, fe)
-    b = Affine4Batch(pairs, MODELS[name], trace=True)
+def check_ends(pairs, name, fs, fe, cm=None, want=None):
+    cm = MODELS[name] if cm is None else cm
+    want = oracle(pairs, name, fs, fe) if want is None else want
+    b = Affine4Batch(pairs, cm, trace=True)
     try:
         for s_max in bounds_of(want):
-            check_ends_at(b, pairs, name, fs, fe, want, s_max)
+            check_ends_at(b, pairs, cm, fs, fe, want, s_max)
         top = bounds_of(want)[0]
         first = ([r.tolist() for r in b.run_dt_ends(top, fs, fe)], b.align_dt_ends(top, fs, fe))
         assert ([r.tolist() for r in b.run_dt_ends(top, fs, fe)], b.align_dt_ends(top, fs, fe)) == first  # a repeated call is identical

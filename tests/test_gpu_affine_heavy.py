@@ -8,12 +8,19 @@ million rows whose costs lie next to kInf against their closed forms.  Every com
 The DT routes never get s_max = 2^30 - 1 here: under these models the clamp gap_cost(|a|) + gap_cost(|b|) alone would ask for gigabytes
 of traced fronts.  The bounds come from the oracle's costs (bounds_of of tests/test_gpu_affine_dt.py).
 
-Measured on an MI355X, the file on its own: 76 tests in 81 s, nearly all of it in the plain oracles (a session that has run
-tests/test_affine_heavy_cases.py before finds the plain DT's results in tests/affine_heavy_cases.DT_ORACLE and skips most of that).
+Measured on an MI355X, the file on its own before the test_dt4_* tests below were added: 76 tests in 81 s, nearly all of it in the
+plain oracles (a session that has run tests/test_affine_heavy_cases.py before finds the plain DT's results in
+tests/affine_heavy_cases.DT_ORACLE and skips most of that).
 Per test: test_dt_global[dt_far-*] 1.9 to 4.8 s (72 000 cost steps a pair under four of the models), test_dt_global[dt_ladder-*] 1.5
 to 2.9 s, every other test_dt_global below 1.5 s; test_dt_ends_free 0.1 to 2.3 s; the near-the-limit tests 1.7 to 2.4 s each (the wide
 pair's million-step walk by one thread is part of 1.9 to 2.4 s, so it stays traced); test_nw_four_layers 1.1 s; test_nw_two_layers and
-its ends-free form 0.6 s; test_dt_every_pair_is_lost_at_its_cost_minus_one 0.7 s; test_dt_segmented at most 0.6 s."""
+its ends-free form 0.6 s; test_dt_every_pair_is_lost_at_its_cost_minus_one 0.7 s; test_dt_segmented at most 0.6 s.
+
+The four-layer DT route (test_dt4_*, 44 tests under the five models of MODELS4; the plain four-layer DT's results come from
+affine_heavy_cases.fill_dt4_oracle, in worker processes unless the session has them).  Measured on an MI355X in a session that had run
+the CPU module before: test_dt4_global[dt_far-*] 0.5 to 1.0 s (52 600 cost steps under main_edge4), test_dt4_global[dt_ladder-*] at
+most 0.5 s, test_dt4_every_pair_is_lost_at_its_cost_minus_one 0.55 s, every other test_dt4_* below 0.5 s; with tests/
+test_affine_heavy_cases.py, tests/test_affine_random_cases.py and tests/test_gpu_affine_random.py before it, 290 tests in 90 s."""
 import numpy as np
 import pytest
 
@@ -335,3 +342,70 @@ def test_one_byte_more_is_refused(cm, Batch):
     create = L.pa_affine4_batch_create if Batch is Affine4Batch else L.pa_affine_batch_create
     assert not create(ap_, capi._p(al), bp_, capi._p(bl), 1, C.byref(c), 0)
     assert "is not below 2^30" in capi.last_error() and "pair 0" in capi.last_error()
+
+
+# ---- the four-layer diagonal-transition route
+
+DT4 = cases.dt4_cases()
+
+
+@pytest.fixture(scope="module")
+def dt4_oracle():
+    """The plain four-layer DT's word on every list below, in worker processes unless the session has it already."""
+    return cases.fill_dt4_oracle(16)
+
+
+@pytest.mark.parametrize("name", sorted(MODELS4))
+@pytest.mark.parametrize("case", sorted(DT4))
+def test_dt4_global(case, name, dt4_oracle):
+    """check_global of tests/test_gpu_affine4_dt.py under the heavy models: run() gives the oracle's costs, run_dt / align_dt its costs
+    and CIGARs at the four bounds of bounds_of, a repeated call the same answer, and run() afterwards is unchanged."""
+    from tests.test_gpu_affine4_dt import check_global
+
+    check_global(DT4[case], name, MODELS4[name], cases.dt4_oracle_case(name, case))
+
+
+def test_dt4_every_pair_is_lost_at_its_cost_minus_one(dt4_oracle):
+    """Pair by pair under three models: s_max = cost - 1 is not found, s_max = cost is."""
+    for name in cases.DT4_ENDS_MODELS:
+        pairs = [p for c in ("dt_small", "dt_gap", "dt_runs") for p in DT4[c]]
+        want = [r for c in ("dt_small", "dt_gap", "dt_runs") for r in cases.dt4_oracle_case(name, c)]
+        for (x, y), (c, g) in zip(pairs, want):
+            if c == 0:
+                continue
+            b = Affine4Batch([(x, y)], MODELS4[name], trace=True)
+            try:
+                assert b.run_dt(c - 1).tolist() == [-1] and b.align_dt(c - 1) == [(-1, "")], (name, len(x), len(y), c)
+                assert b.run_dt(c).tolist() == [c] and b.align_dt(c) == [(c, g)], (name, len(x), len(y), c)
+            finally:
+                b.close()
+
+
+@pytest.mark.parametrize("setting", SETTINGS, ids=["fs%d-fe%d" % s for s in SETTINGS])
+@pytest.mark.parametrize("name", cases.DT4_ENDS_MODELS)
+def test_dt4_ends_free(name, setting, dt4_oracle):
+    """check_ends of tests/test_gpu_affine4_dt.py over dt_planted(): (cost, CIGAR, start, end) of the plain ends-free DT at the bounds
+    of bounds_of, and run() / ends() of the same batch under set_free_ends agree on cost and end."""
+    from tests.test_gpu_affine4_dt import check_ends
+
+    fs, fe = setting
+    check_ends(cases.dt_planted(), name, fs, fe, MODELS4[name], cases.dt4_ends_oracle(name, fs, fe))
+
+
+def test_dt4_wide_block_at_heavy_costs(dt4_oracle):
+    """Four pairs of 300 bytes at 10 % under the dense model: the mean W at the batch's largest cost is above 256, so the block is
+    four wavefronts wide, and it meets a main ring of 1001 slots next to layer rings of 2, 2, 3 and 4 (cost only), and traced fronts."""
+    from tests.affine4_dt_plain import mean_w
+    from tests.test_gpu_affine4_dt import check_global
+
+    cm, pairs, want = MODELS4["dense4"], cases.dt4_wide(), cases.dt4_wide_oracle()
+    top = max(c for c, _ in want)
+    assert mean_w(pairs, cm, top) > 256
+    b = Affine4Batch(pairs, cm)  # cost only: the rings
+    try:
+        assert b.run_dt(top).tolist() == [c for c, _ in want]
+        assert b.run_dt(top - 1).tolist() == [c if c < top else -1 for c, _ in want]
+        assert b.run_dt(BIG).tolist() == [c for c, _ in want]
+    finally:
+        b.close()
+    check_global(pairs, "dense4", cm, want)
