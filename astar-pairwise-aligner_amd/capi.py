@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine4_batch_set_free_ends", "pa_affine4_batch_ends", "pa_affine4_batch_last_row",
     "pa_affine4_batch_run_dt", "pa_affine4_batch_align_dt", "pa_affine4_batch_run_dt_ends", "pa_affine4_batch_align_dt_ends",
     "pa_affine4_batch_dt_info",
+    "pa_affine4_batch_align_dt_seg", "pa_affine4_batch_dt_seg_info",
 ]
 
 _lib = None
@@ -160,6 +161,10 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine4_batch_align_dt_ends.argtypes = [vp, C.c_int, C.c_int, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.pa_affine4_batch_dt_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 6
         L.pa_affine4_batch_dt_info.restype = None
+    if hasattr(L, "pa_affine4_batch_align_dt_seg"):
+        L.pa_affine4_batch_align_dt_seg.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp, vp, vp] + [C.POINTER(C.c_float)] * 3
+        L.pa_affine4_batch_dt_seg_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
+        L.pa_affine4_batch_dt_seg_info.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -941,8 +946,8 @@ class Affine4Batch(_AffineBatchBase):
     all of it in one call.  (The constructor keeps its four arguments, which tests/test_affine4_chain_api.py pins: the switches are set
     on the batch.)  run_dt(s_max) / align_dt(s_max) and run_dt_ends / align_dt_ends (include/pa_affine4_dt_hip.h) take the
     diagonal-transition route over the five layers, bounded by s_max: the choice for long pairs of low divergence (DESIGN.md has the
-    measurements); map_affine_dt does the ends-free traced form in one call.  Not supported: a segmented DT traceback (align_dt_seg),
-    which is AffineBatch's, for two layers."""
+    measurements); map_affine_dt does the ends-free traced form in one call.  align_dt_segmented(s_max, seg) gives align_dt_ends' results
+    in device memory that grows with the square root of the bound (include/pa_affine4_dt_seg_hip.h), for traced long pairs."""
 
     _PREFIX = "pa_affine4_batch"
     _WALK_MS = "last_walk_ms"
@@ -953,6 +958,40 @@ class Affine4Batch(_AffineBatchBase):
         self.last_walk_ms = 0.0
         if chain:
             self.set_chain(True)
+
+    def align_dt_segmented(self, s_max: int, seg: int = 0, free_start: bool = False, free_end: bool = False) -> list[tuple[int, str, int, int]]:
+        """align_dt_ends(s_max, free_start, free_end) in device memory that grows with the square root of the bound: the same
+        [(cost, CIGAR, start, end)], byte for byte (AffineBatch.align_dt_seg's counterpart).  A checkpoint pass keeps, below every
+        segment of `seg` costs, the E fronts of the main layer and the extend_t fronts of layer t that the segment reads (E the largest
+        of sub, ins, del and the opens; H rows in all); then, segment by segment from the top, the fronts are computed again and
+        walked.  seg = 0: per pair the smallest S with 5 S^2 >= (bound + 1) H; else an integer in [Ew, 2^30), Ew the largest of E and
+        the extends.  The times are kept in `last_forward_ms` (checkpoint pass), `last_refill_ms` (fills) and `last_trace_ms` (walks),
+        the shape in dt_segmented_info(), the checkpoint pass's counters in dt_info()."""
+        s_max = self._s_max(s_max)
+        if not isinstance(seg, (int, np.integer)) or isinstance(seg, (bool, np.bool_)) or not 0 <= seg < 1 << 30:
+            raise ValueError(f"seg must be 0 or an integer in [Ew, 2^30), got {seg!r}")
+        fs, fe = _switch(free_start, "free_start"), _switch(free_end, "free_end")
+        L = load()
+        n = self.npairs
+        costs = np.zeros(max(n, 1), np.int32)
+        st, en = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        cig = (C.c_void_p * max(n, 1))()
+        f, r, t = C.c_float(0), C.c_float(0), C.c_float(0)
+        rc = L.pa_affine4_batch_align_dt_seg(self._h, fs, fe, s_max, int(seg), _p(costs), _p(st), _p(en), cig, C.byref(f), C.byref(r), C.byref(t))
+        try:
+            self._check(rc, "pa_affine4_batch_align_dt_seg")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_refill_ms, self.last_trace_ms = float(f.value), float(r.value), float(t.value)
+        return [(int(costs[p]), cigars[p] if costs[p] >= 0 else "", int(st[p]), int(en[p])) for p in range(n)]
+
+    def dt_segmented_info(self) -> dict:
+        """Shape of the last align_dt_segmented(): chunks, rounds (a fill launch and a walk launch each), segment jobs, front cells the
+        fills computed, device bytes of the largest chunk."""
+        vals = [C.c_double(0) for _ in range(5)]
+        load().pa_affine4_batch_dt_seg_info(self._h, *[C.byref(v) for v in vals])
+        return {k: int(v.value) for k, v in zip(("chunks", "rounds", "seg_jobs", "refill_cells", "bytes_max"), vals)}
 
 
 def align_affine4(pairs, cm: AffineCost, trace: bool = True, tiled: bool = False):

@@ -7,15 +7,15 @@
 //
 // The driver below restates affine_dt_unit.hip's dt_call (event timing, the chunk loop, the copy-back of the ops) over this unit's
 // plan, job record and kernels; sharing it is left to a change that may touch that unit ("Double-affine diagonal
-// transition").  A segmented traceback (align_dt_seg's counterpart) is not built.
+// transition").  The segmented traceback is affine4_dt_seg_unit.hip's; the state of both is affine4_dt_host.hpp's.
 #include "pa_hip_internal.hpp"
 #include "affine4_dt_kernel.hpp"
 #include "affine4_dt_plan.hpp"
+#include "affine4_dt_host.hpp"
 #include "affine4_dt_view.hpp"
 #include "../../include/pa_affine4_dt_hip.h"
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <string>
@@ -24,38 +24,9 @@
 using namespace pa;
 using namespace pa::affine4;
 
-struct pa::affine4::DtState {
-    DeviceBuf d_seq;  // the batch's sequences, with kSeqPad bytes after the last
-    bool seq_ready = false;
-    DeviceBuf d_cost, d_stat, d_jobs, d_fronts, d_wout;
-    double found = 0, not_found = 0, chunks = 0, front_cells = 0, extend_chars = 0, bytes_max = 0;  // the last DT call
-};
-
 void pa::affine4::dt_release(DtState* st) { delete st; }
 
 namespace {
-
-constexpr int32_t kSMaxLimit = 1 << 30;
-
-// The CIGAR text of a walk's ops (recorded from the end backwards): equal ops merge, the ops of every layer print as I / D
-// (affine4_batch.hpp's cigar_of, restated: that header is the DP units').
-std::string cigar_of(const uint8_t* op, int32_t nops) {
-    std::string out;
-    char num[16];
-    for (int32_t x = nops - 1; x >= 0;) {
-        int32_t y = x;
-        while (y >= 0 && op[y] == op[x]) --y;
-        const int32_t k = x - y;
-        if (k > 1) {
-            std::snprintf(num, sizeof num, "%d", k);
-            out += num;
-        }
-        const uint8_t c = op[x];
-        out += c == 'i' || c == 'j' ? 'I' : c == 'd' || c == 'e' ? 'D' : (char)c;
-        x = y;
-    }
-    return out;
-}
 
 struct Events {
     hipEvent_t e[3] = {nullptr, nullptr, nullptr};

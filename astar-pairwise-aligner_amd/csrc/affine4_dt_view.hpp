@@ -1,4 +1,4 @@
-// affine4_dt_view.hpp -- what the double-affine diagonal-transition unit (affine4_dt_unit.hip) sees of a pa_affine4_batch, which
+// affine4_dt_view.hpp -- what the double-affine diagonal-transition units (affine4_dt_unit.hip, affine4_dt_seg_unit.hip) see of a pa_affine4_batch, which
 // affine4_batch.hpp defines and affine4_unit.hip opens: the pairs, the cost model, the uploaded sequences, the batch's ends-free setting,
 // and one slot for the DT route's own state.  The analogue of affine_dt_view.hpp.
 #pragma once
@@ -12,7 +12,7 @@ struct pa_affine4_batch;
 namespace pa {
 namespace affine4 {
 
-struct DtState;  // affine4_dt_unit.hip: the padded sequences, the buffers and the counters of the last DT call
+struct DtState;  // affine4_dt_host.hpp: the padded sequences, the buffers and the counters of the last DT call
 
 struct DtView {
     size_t np;

@@ -16,8 +16,8 @@
  * The tiled traceback, pa_affine4_batch_align in bounded device memory, is declared in pa_affine4_tiled_hip.h, and chained strips (a
  * wavefront per strip of a long pair, in run and in the tiled traceback's checkpoint pass) in pa_affine4_chain_hip.h, and ends-free (semi-global) mode with
  * pa_affine4_batch_set_free_ends, pa_affine4_batch_ends and pa_affine4_batch_last_row in pa_affine4_ends_hip.h.  Not supported: layer lists
- * other than [insert, delete, insert, delete]; the diagonal-transition route is declared in pa_affine4_dt_hip.h, without a segmented
- * traceback (pa_affine_hip.h has one for the models with at most two layers).
+ * other than [insert, delete, insert, delete]; the diagonal-transition route is declared in pa_affine4_dt_hip.h and its segmented
+ * traceback in pa_affine4_dt_seg_hip.h.
  *
  * Errors follow pa_bitpacking_hip.h: 0 or a negative PA_E_* code, pa_last_error() for the message.
  */

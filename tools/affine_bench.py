@@ -2,7 +2,7 @@
 affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C, built here with the system compiler).
 
     python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
-                                 [--dt-seg] [--double] [--double-tiled] [--double-chain] [--double-ends] [--double-dt] [--double-dt-ends]
+                                 [--dt-seg] [--double] [--double-tiled] [--double-chain] [--double-ends] [--double-dt] [--double-dt-ends] [--double-dt-seg]
                                  [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
@@ -63,7 +63,11 @@ run_dt(largest cost) alternating, each warmed once and then three times; the fas
 then go through AffineBatch.run_dt under affine(4, 6, 2) at that model's largest cost, the second column: what five layers cost over three.
 
 --double-dt-ends does likewise against the ends-free run() (Affine4Batch.run_dt_ends, both ends free) on the mapping shapes of --dt-ends:
-map150, map10k@1, map10k@3, map10k@5."""
+map150, map10k@1, map10k@3, map10k@5.
+
+--double-dt-seg is --dt-seg's protocol on an Affine4Batch under double_affine(4, 6, 2, 24, 1) (Affine4Batch.align_dt_segmented, default seg,
+against Affine4Batch.align_dt_ends), whatever --shapes says (or the shapes of --shapes that carry an @): 10k@1, 10k@3, 10k@5, reads@5
+and 100k@5.  Where align_dt_ends refuses the batch its error is printed and align_dt_segmented runs alone."""
 from __future__ import annotations
 
 import argparse
@@ -414,9 +418,11 @@ def double_dt_legs(title, pairs, chain, ends):
           f" {di2['bytes_max'] / 2**20:.1f} MiB, mean cost {float(want2.mean()):.1f}", flush=True)
 
 
-def dt_seg_legs(title, pairs, cm, mname):
-    """align_dt_ends(largest cost) and align_dt_seg(largest cost), both switches off, in turn on one traced batch."""
-    b = AffineBatch(pairs, cm, trace=True)
+def dt_seg_legs(title, pairs, cm, mname, Batch=AffineBatch):
+    """align_dt_ends(largest cost) and align_dt_seg(largest cost), both switches off, in turn on one traced batch (with
+    Batch = Affine4Batch the segmented call is align_dt_segmented)."""
+    b = Batch(pairs, cm, trace=True)
+    seg_call, seg_info = (b.align_dt_segmented, b.dt_segmented_info) if Batch is Affine4Batch else (b.align_dt_seg, b.dt_seg_info)
     s_max = int(b.run_dt((1 << 30) - 1).max())
     every, seg, err = [], [], None
     for rep in range(4):  # the first round warms both routes
@@ -428,13 +434,13 @@ def dt_seg_legs(title, pairs, cm, mname):
                     every.append((b.last_forward_ms, b.last_trace_ms, b.dt_info()))
             except ValueError as e:
                 err = str(e)
-        got = b.align_dt_seg(s_max, 0, False, False)
+        got = seg_call(s_max, 0, False, False)
         if want is not None and got != want:
             raise SystemExit(f"{title} {mname}: align_dt_ends() and align_dt_seg() disagree")
         if any(g[0] < 0 for g in got):
             raise SystemExit(f"{title} {mname}: align_dt_seg() did not find a pair within the largest cost")
         if rep:
-            seg.append((b.last_forward_ms, b.last_refill_ms, b.last_trace_ms, b.dt_seg_info()))
+            seg.append((b.last_forward_ms, b.last_refill_ms, b.last_trace_ms, seg_info()))
     b.close()
     f1, r1, w1, si = min(seg, key=lambda x: sum(x[:3]))
     t1 = f1 + r1 + w1
@@ -580,6 +586,7 @@ def main():
     ap.add_argument("--double-ends", action="store_true", help="measure Affine4Batch's ends-free mode against its global one instead (see above)")
     ap.add_argument("--double-dt", action="store_true", help="measure Affine4Batch.run_dt() against Affine4Batch.run() instead (see above)")
     ap.add_argument("--double-dt-ends", action="store_true", help="measure Affine4Batch.run_dt_ends() against the ends-free Affine4Batch.run() instead (see above)")
+    ap.add_argument("--double-dt-seg", action="store_true", help="measure Affine4Batch.align_dt_segmented() against Affine4Batch.align_dt_ends() instead (see above)")
     ap.add_argument("--models", default="affine,unit", help="cost models to run: affine (affine(4, 6, 2)), unit")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="time spent on the CPU core per shape and model")
     args = ap.parse_args()
@@ -638,6 +645,13 @@ def main():
             if "at 5 %" not in title and sname.endswith("@5"):
                 title += " at 5 %"
             double_dt_legs(title, pairs, sname.startswith("100k"), False)
+        return
+    if args.double_dt_seg:
+        for sname in [x for x in args.shapes.split(",") if "@" in x] or ["10k@1", "10k@3", "10k@5", "reads@5", "100k@5"]:
+            title, pairs = shape(sname, rng)
+            if "at 5 %" not in title and sname.endswith("@5"):
+                title += " at 5 %"
+            dt_seg_legs(title, pairs, AffineCost.double_affine(4, 6, 2, 24, 1), "double_affine", Affine4Batch)
         return
     if args.double_dt_ends:
         for sname in [x for x in args.shapes.split(",") if x.startswith("map")] or ["map150", "map10k@1", "map10k@3", "map10k@5"]:
