@@ -8,7 +8,7 @@ from . import _build, aligner, capi, generate  # noqa: F401
 from .aligner import (AstarPa2, AstarPa2Params, BlockParams, astarpa2_full, astarpa2_nw,  # noqa: F401
                       astarpa2_simple, c_abi_align)
 from .capi import (Affine4Batch, AffineBatch, AffineCost, align_affine4, Batch, OperatorContext, PaError, SearchBatch, align_file, align_multi, compute, fill, profile_build, read_pairs,  # noqa: F401
-                   align_affine, map_affine, map_affine_dt, require_gpu, search, search_trace)
+                   align_affine, align_local, map_affine, map_affine_dt, require_gpu, search, search_trace)
 
 
 def align_batch(pairs):

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine_batch_run_dt", "pa_affine_batch_align_dt", "pa_affine_batch_dt_info",
     "pa_affine_batch_run_dt_ends", "pa_affine_batch_align_dt_ends",
     "pa_affine_batch_align_dt_seg", "pa_affine_batch_dt_seg_info",
+    "pa_affine_batch_run_local", "pa_affine_batch_align_local", "pa_affine_batch_local_info",
     "pa_affine4_batch_create", "pa_affine4_batch_run", "pa_affine4_batch_align", "pa_affine4_batch_info", "pa_affine4_batch_destroy",
     "pa_affine4_batch_align_tiled", "pa_affine4_batch_tiled_info", "pa_affine4_batch_set_chain", "pa_affine4_batch_chain_info",
     "pa_affine4_batch_set_free_ends", "pa_affine4_batch_ends", "pa_affine4_batch_last_row",
@@ -133,6 +134,11 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine_batch_align_dt_seg.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp, vp, vp] + [C.POINTER(C.c_float)] * 3
         L.pa_affine_batch_dt_seg_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
         L.pa_affine_batch_dt_seg_info.restype = None
+    if hasattr(L, "pa_affine_batch_run_local"):
+        L.pa_affine_batch_run_local.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(C.c_float)]
+        L.pa_affine_batch_align_local.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.pa_affine_batch_local_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 2
+        L.pa_affine_batch_local_info.restype = None
     if hasattr(L, "pa_affine4_batch_create"):
         L.pa_affine4_batch_create.argtypes = [vp, vp, vp, vp, sz, vp, C.c_int]
         L.pa_affine4_batch_create.restype = vp
@@ -623,6 +629,16 @@ def _switch(v, name: str) -> int:
     raise ValueError(f"{name} must be a bool (or 0 / 1), got {v!r}")
 
 
+AFFINE_MAX_MATCH = 1000
+
+
+def _match_arg(match) -> int:
+    """The bonus per match of a local-alignment call: an integer in [1, 1000]."""
+    if not isinstance(match, (int, np.integer)) or isinstance(match, (bool, np.bool_)) or not 1 <= match <= AFFINE_MAX_MATCH:
+        raise ValueError(f"match must be an integer in [1, {AFFINE_MAX_MATCH}], got {match!r}")
+    return int(match)
+
+
 def _s_max_arg(s_max) -> int:
     """The bound of a diagonal-transition call: an integer in [0, 2^30)."""
     if not isinstance(s_max, (int, np.integer)) or isinstance(s_max, bool) or not 0 <= s_max < 1 << 30:
@@ -915,6 +931,58 @@ class AffineBatch(_AffineBatchBase):
         vals = [C.c_double(0) for _ in range(5)]
         load().pa_affine_batch_dt_seg_info(self._h, *[C.byref(v) for v in vals])
         return {k: int(v.value) for k, v in zip(("chunks", "rounds", "seg_jobs", "refill_cells", "bytes_max"), vals)}
+
+    def run_local(self, match: int) -> tuple[np.ndarray, np.ndarray]:
+        """Local (Smith-Waterman) alignment under the batch's cost model and a bonus of `match` per matching pair of bytes
+        (include/pa_affine_local_hip.h), scores only: (scores int32[npairs], ends int64[npairs, 2] of (a_end, b_end)), the highest
+        H(i, j) and its lowest i, then lowest j; score 0 is the empty alignment at (0, 0).  Independent of the batch's ends-free and
+        chain settings.  The kernel time is kept in `last_kernel_ms`."""
+        match = _match_arg(match)
+        n = self.npairs
+        scores = np.zeros(max(n, 1), np.int32)
+        ae, be = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        ms = C.c_float(0)
+        self._check(load().pa_affine_batch_run_local(self._h, match, _p(scores), _p(ae), _p(be), C.byref(ms)), "pa_affine_batch_run_local")
+        self.last_kernel_ms = float(ms.value)
+        return scores[:n], np.stack([ae[:n], be[:n]], axis=1)
+
+    def align_local(self, match: int) -> list[tuple[int, str, int, int, int, int]]:
+        """[(score, CIGAR, a_start, a_end, b_start, b_end)] of every pair's local alignment (trace batches only): the CIGAR describes
+        a[a_start:a_end] against b[b_start:b_end], the clipped flanks are not printed.  In chunks whose traceback codes stay within
+        PA_AFFINE_TRACE_BUDGET_MB (local_info()); ValueError naming a pair whose codes alone exceed it.  The times are kept in
+        `last_forward_ms` and `last_trace_ms`."""
+        match = _match_arg(match)
+        L = load()
+        n = self.npairs
+        scores = np.zeros(max(n, 1), np.int32)
+        ends = [np.zeros(max(n, 1), np.int64) for _ in range(4)]  # a_start, a_end, b_start, b_end
+        cig = (C.c_void_p * max(n, 1))()
+        f, t = C.c_float(0), C.c_float(0)
+        rc = L.pa_affine_batch_align_local(self._h, match, _p(scores), *[_p(e) for e in ends], cig, C.byref(f), C.byref(t))
+        try:
+            self._check(rc, "pa_affine_batch_align_local")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
+        return [(int(scores[p]), cigars[p], *[int(e[p]) for e in ends]) for p in range(n)]
+
+    def local_info(self) -> dict:
+        """Shape of the last align_local(): chunks, device bytes of traceback codes of the largest one."""
+        vals = [C.c_double(0) for _ in range(2)]
+        load().pa_affine_batch_local_info(self._h, *[C.byref(v) for v in vals])
+        return {k: int(v.value) for k, v in zip(("chunks", "bytes_max"), vals)}
+
+
+def align_local(pairs, cm: AffineCost, match: int) -> list[tuple[int, str, int, int, int, int]]:
+    """[(score, CIGAR, a_start, a_end, b_start, b_end)] of every pair's local alignment under the gap-affine cost model `cm` and a bonus
+    of `match` per match (one traced AffineBatch, AffineBatch.align_local)."""
+    match = _match_arg(match)
+    b = AffineBatch(pairs, cm, trace=True)
+    try:
+        return b.align_local(match)
+    finally:
+        b.close()
 
 
 def align_affine(pairs, cm: AffineCost, tiled: bool = False, chain: bool = False, s_max: int | None = None) -> list[tuple[int, str]]:

@@ -11,7 +11,8 @@
 // chained through their boundary rows (planned by affine_chain_plan.hpp).  set_free_ends() makes the ends of a free in all of these
 // routes: the launches then pick the kernels' ENDS instantiations, which leave every pair's end in d_end; the walks start there, and
 // pa_affine_batch_ends reports where they started and stopped.  last_row() is a cost-only pass of its own that also stores row |b|.
-// The diagonal-transition route (run_dt, align_dt) is a unit of its own, affine_dt_unit.hip, which sees a batch through dt_view().
+// The diagonal-transition route (run_dt, align_dt) is a unit of its own, affine_dt_unit.hip, which sees a batch through dt_view();
+// local alignment (run_local, align_local) likewise, affine_local_unit.hip through local_view().
 // The plan, the chunking and the drivers of align() and align_tiled() are affine_host.hpp's and the chained route's host side is
 // affine_chain_host.hpp's, both shared with the four-layer batch, as is the host side of ends-free mode and last_row(); this unit gives
 // them its records and launches (Host) and keeps what only two layers have: dt_view().
@@ -19,6 +20,7 @@
 #include "affine_kernel.hpp"
 #include "affine_chain_host.hpp"
 #include "affine_dt_view.hpp"
+#include "affine_local_view.hpp"
 #include "../../include/pa_affine_hip.h"
 
 #include <algorithm>
@@ -47,7 +49,11 @@ struct pa_affine_batch : affine_host::Batch<Pair, Wave> {
     DeviceBuf d_end;
     affine_host::EndsState ends;
     DtState* dt = nullptr;  // the diagonal-transition route's own state (affine_dt_unit.hip)
+    LocalInfo local;        // the shape of the last align_local() (affine_local_unit.hip)
 };
+
+// What the local-alignment route (run_local, align_local: affine_local_unit.hip) reads of a batch.
+LocalView pa::affine::local_view(pa_affine_batch* ab) { return LocalView{ab, ab->C, &ab->local}; }
 
 // What the diagonal-transition route (run_dt, align_dt: affine_dt_unit.hip) reads of a batch.
 DtView pa::affine::dt_view(pa_affine_batch* ab) {
@@ -75,6 +81,7 @@ struct Host {
     using ChainJob = affine::ChainJob;
     // 8-byte boundary values (M | I << 32) and checkpoint rows (M | D << 32): a pair's checkpoints are whole 8-byte values as they are
     static constexpr affine_plan::Layout kLayout{kRows, 8, 8, 8};
+    static_assert(kLayout.rows == kLocalLayout.rows && kLayout.bnd_bytes == kLocalLayout.bnd_bytes, "affine_local_view.hpp restates the layout");
     static constexpr const char* kName = "pa_affine_batch";
     static constexpr int32_t kMaxLayer = 2;
     static constexpr uint32_t kVisitSlack = 1;

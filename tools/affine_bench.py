@@ -54,6 +54,11 @@ only, the tiled forward pass and traced in all, chained and unchained alternatin
 results compared in every round.  Every shape runs in a process of its own under a wall-clock limit sized for its unchained passes (a
 100 kbp pair alone on a wavefront takes 7 to 10 s a pass).
 
+--local measures what local alignment costs over the global mode (AffineBatch.run_local / align_local at match = 2), whatever --shapes
+says: 100 000 x 150 bp reads in 400 bp windows (cost-only and traced), 4096 x 10 kbp cost-only and --trace-pairs of them traced.  On one
+batch, run() against run_local() and align() against align_local(), alternating, each warmed once and then three times; the fastest
+repeat of each and their ratio.
+
 --double-ends is --ends' protocol and mapping shapes on an Affine4Batch under double_affine(4, 6, 2, 24, 1) (Affine4Batch.set_free_ends):
 cost-only, traced and tiled (at --tile-cols, by default the library's 1024), global and ends-free alternating on one batch.
 
@@ -537,6 +542,47 @@ def ends_legs(title, pairs, tp, cm, mname, tile_cols, reps, Batch=AffineBatch):
           f" {ti['refill_cells'] / tcells:.3f} of the cells filled", flush=True)
 
 
+def local_legs(title, pairs, tp, cm, mname, match=2):
+    """Global and local (run_local / align_local at `match`), alternating on one batch each: run() against run_local() on `pairs` (if
+    any), align() against align_local() on a traced batch of `tp` (if any); each warmed once, then three times, the fastest of each."""
+    legs = []
+    if pairs:
+        b = AffineBatch(pairs, cm)
+        g, l = [], []
+        for rep in range(4):  # the first round warms both routes
+            b.run()
+            k = b.last_kernel_ms
+            b.run_local(match)
+            if rep:
+                g.append(k)
+                l.append(b.last_kernel_ms)
+        b.close()
+        legs.append(("cost", pairs, g, l, ""))
+    if tp:
+        tb = AffineBatch(tp, cm, trace=True)
+        g, l, gf, lf = [], [], [], []  # totals, and the forward (fill) part of each
+        for rep in range(4):
+            tb.align()
+            k, kf = tb.last_forward_ms + tb.last_trace_ms, tb.last_forward_ms
+            res = tb.align_local(match)
+            if rep:
+                g.append(k)
+                gf.append(kf)
+                l.append(tb.last_forward_ms + tb.last_trace_ms)
+                lf.append(tb.last_forward_ms)
+        li = tb.local_info()
+        tb.close()
+        cover = sum(r[5] - r[4] for r in res) / max(sum(len(y) for _, y in tp), 1)
+        legs.append(("traced", tp, g, l, f"; fills {min(gf):.2f} | {min(lf):.2f} ms; {li['chunks']} chunks, {li['bytes_max'] / 2**20:.0f} MiB,"
+                                         f" {cover:.3f} of b aligned"))
+    for leg, ps, g, l, note in legs:
+        cells = float(sum(len(x) * len(y) for x, y in ps))
+        g0, l0 = min(g), min(l)
+        print(f"{title:44s} {mname:14s} {leg + ':':10s} global {g0:10.2f} ms {cells / g0 / 1e6:8.1f} GCUPS | local(match={match}) {l0:10.2f} ms"
+              f" {cells / l0 / 1e6:8.1f} GCUPS | local / global {l0 / g0:6.3f}  ({len(ps)} pairs; repeats {' '.join(f'{x:.2f}' for x in g)} |"
+              f" {' '.join(f'{x:.2f}' for x in l)}{note})", flush=True)
+
+
 def traced(tp, cm, mname, untiled, tile_cols, reps, warm=True, note=""):
     """The traced lines of one batch: the untiled route (if asked for) and the tiled one, alternating."""
     tcells = float(sum(len(x) * len(y) for x, y in tp))
@@ -575,6 +621,7 @@ def main():
     ap.add_argument("--trace-pairs", type=int, default=512, help="traced runs of the 10 kbp shape use this many of its pairs")
     ap.add_argument("--chain", action="store_true", help="measure the chained route against the unchained one instead (see above)")
     ap.add_argument("--ends", action="store_true", help="measure the ends-free mode against the global one instead (see above)")
+    ap.add_argument("--local", action="store_true", help="measure local alignment (run_local / align_local) against the global calls instead (see above)")
     ap.add_argument("--dt", action="store_true", help="measure the diagonal-transition route against run() instead (see above)")
     ap.add_argument("--dt-ends", action="store_true", help="measure the ends-free diagonal-transition route against the ends-free run() instead (see above)")
     ap.add_argument("--dt-seg", action="store_true", help="measure the segmented DT traceback against align_dt_ends instead (see above)")
@@ -664,6 +711,14 @@ def main():
             title, pairs = ends_shape(sname, rng)
             ends_legs(title, pairs, pairs if sname == "map150" else pairs[: args.trace_pairs], AffineCost.double_affine(4, 6, 2, 24, 1), "double_affine",
                       args.tile_cols, args.reps, Affine4Batch)
+        return
+    if args.local:
+        title, pairs = ends_shape("map150", rng)
+        for mname, cm in models.items():
+            local_legs(title, pairs, pairs, cm, mname)
+        title, pairs = shape("10k", rng)
+        for mname, cm in models.items():
+            local_legs(title, pairs, pairs[: args.trace_pairs], cm, mname)
         return
     if args.ends:
         for sname in ("map150", "map10k"):
