@@ -10,7 +10,7 @@ PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libastarpa_c_hip.so"
 
-HIP_SOURCES = ["pa_hip.hip", "apa2_jobs_unit.hip", "runtime_unit.hip", "rect_unit.hip", "search_unit.hip", "debug_unit.hip", "engine_hip.hip", "combine_unit.hip", "astarpa_c.hip", "pairs_io.hip", "apa2_simple_unit.hip", "apa2_full_unit.hip", "gcsh_build_unit.hip", "sketch_unit.hip", "slice_unit.hip", "search_batch_unit.hip", "affine_unit.hip", "affine_dt_unit.hip", "affine_local_unit.hip", "affine4_unit.hip", "affine4_tiled_unit.hip", "affine4_dt_unit.hip", "affine4_dt_seg_unit.hip"]
+HIP_SOURCES = ["pa_hip.hip", "apa2_jobs_unit.hip", "runtime_unit.hip", "rect_unit.hip", "search_unit.hip", "debug_unit.hip", "engine_hip.hip", "combine_unit.hip", "astarpa_c.hip", "pairs_io.hip", "apa2_simple_unit.hip", "apa2_full_unit.hip", "gcsh_build_unit.hip", "sketch_unit.hip", "slice_unit.hip", "search_batch_unit.hip", "affine_unit.hip", "affine_dt_unit.hip", "affine_local_unit.hip", "affine4_unit.hip", "affine4_tiled_unit.hip", "affine4_dt_unit.hip", "affine4_dt_seg_unit.hip", "affine4_local_unit.hip"]
 
 
 def _hipcc() -> str:

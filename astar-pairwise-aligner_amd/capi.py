@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "pa_affine4_batch_run_dt", "pa_affine4_batch_align_dt", "pa_affine4_batch_run_dt_ends", "pa_affine4_batch_align_dt_ends",
     "pa_affine4_batch_dt_info",
     "pa_affine4_batch_align_dt_seg", "pa_affine4_batch_dt_seg_info",
+    "pa_affine4_batch_run_local", "pa_affine4_batch_align_local", "pa_affine4_batch_local_info",
 ]
 
 _lib = None
@@ -171,6 +172,11 @@ def load(build_if_stale: bool = True) -> C.CDLL:
         L.pa_affine4_batch_align_dt_seg.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp, vp, vp] + [C.POINTER(C.c_float)] * 3
         L.pa_affine4_batch_dt_seg_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 5
         L.pa_affine4_batch_dt_seg_info.restype = None
+    if hasattr(L, "pa_affine4_batch_run_local"):
+        L.pa_affine4_batch_run_local.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(C.c_float)]
+        L.pa_affine4_batch_align_local.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.pa_affine4_batch_local_info.argtypes = [vp] + [C.POINTER(C.c_double)] * 2
+        L.pa_affine4_batch_local_info.restype = None
     L.pa_search_batch_destroy.restype = None
     L.pa_batch_create.argtypes = [vp, vp, vp, vp, sz]
     L.pa_batch_create.restype = vp
@@ -976,11 +982,13 @@ class AffineBatch(_AffineBatchBase):
 
 def align_local(pairs, cm: AffineCost, match: int) -> list[tuple[int, str, int, int, int, int]]:
     """[(score, CIGAR, a_start, a_end, b_start, b_end)] of every pair's local alignment under the gap-affine cost model `cm` and a bonus
-    of `match` per match (one traced AffineBatch, AffineBatch.align_local)."""
+    of `match` per match: one traced AffineBatch (AffineBatch.align_local), or with a four-layer `cm` (AffineCost.double_affine) one
+    traced Affine4Batch (Affine4Batch.align_sw)."""
     match = _match_arg(match)
-    b = AffineBatch(pairs, cm, trace=True)
+    four = isinstance(cm, AffineCost) and len(cm.layers) == 4
+    b = (Affine4Batch if four else AffineBatch)(pairs, cm, trace=True)
     try:
-        return b.align_local(match)
+        return b.align_sw(match) if four else b.align_local(match)
     finally:
         b.close()
 
@@ -1015,7 +1023,10 @@ class Affine4Batch(_AffineBatchBase):
     on the batch.)  run_dt(s_max) / align_dt(s_max) and run_dt_ends / align_dt_ends (include/pa_affine4_dt_hip.h) take the
     diagonal-transition route over the five layers, bounded by s_max: the choice for long pairs of low divergence (DESIGN.md has the
     measurements); map_affine_dt does the ends-free traced form in one call.  align_dt_segmented(s_max, seg) gives align_dt_ends' results
-    in device memory that grows with the square root of the bound (include/pa_affine4_dt_seg_hip.h), for traced long pairs."""
+    in device memory that grows with the square root of the bound (include/pa_affine4_dt_seg_hip.h), for traced long pairs.
+    run_sw(match) / align_sw(match) (include/pa_affine4_local_hip.h) are local (Smith-Waterman) alignment under the same costs and a
+    bonus per match, AffineBatch.run_local / align_local's counterparts under names of their own; align_local(pairs, cm, match) picks
+    the batch by the number of layers."""
 
     _PREFIX = "pa_affine4_batch"
     _WALK_MS = "last_walk_ms"
@@ -1060,6 +1071,47 @@ class Affine4Batch(_AffineBatchBase):
         vals = [C.c_double(0) for _ in range(5)]
         load().pa_affine4_batch_dt_seg_info(self._h, *[C.byref(v) for v in vals])
         return {k: int(v.value) for k, v in zip(("chunks", "rounds", "seg_jobs", "refill_cells", "bytes_max"), vals)}
+
+    def run_sw(self, match: int) -> tuple[np.ndarray, np.ndarray]:
+        """Local (Smith-Waterman) alignment under the batch's two-piece gap costs and a bonus of `match` per matching pair of bytes
+        (include/pa_affine4_local_hip.h; AffineBatch.run_local's counterpart), scores only: (scores int32[npairs], ends
+        int64[npairs, 2] of (a_end, b_end)), the highest H(i, j) and its lowest i, then lowest j; score 0 is the empty alignment at
+        (0, 0).  Independent of the batch's ends-free and chain settings.  The kernel time is kept in `last_kernel_ms`."""
+        match = _match_arg(match)
+        n = self.npairs
+        scores = np.zeros(max(n, 1), np.int32)
+        ae, be = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        ms = C.c_float(0)
+        self._check(load().pa_affine4_batch_run_local(self._h, match, _p(scores), _p(ae), _p(be), C.byref(ms)), "pa_affine4_batch_run_local")
+        self.last_kernel_ms = float(ms.value)
+        return scores[:n], np.stack([ae[:n], be[:n]], axis=1)
+
+    def align_sw(self, match: int) -> list[tuple[int, str, int, int, int, int]]:
+        """[(score, CIGAR, a_start, a_end, b_start, b_end)] of every pair's local alignment (trace batches only; AffineBatch.align_local's
+        counterpart): the CIGAR describes a[a_start:a_end] against b[b_start:b_end], gaps of different layers stay separate elements,
+        the clipped flanks are not printed.  In chunks whose traceback codes stay within PA_AFFINE_TRACE_BUDGET_MB (sw_info());
+        ValueError naming a pair whose codes alone exceed it.  The times are kept in `last_forward_ms` and `last_trace_ms`."""
+        match = _match_arg(match)
+        L = load()
+        n = self.npairs
+        scores = np.zeros(max(n, 1), np.int32)
+        ends = [np.zeros(max(n, 1), np.int64) for _ in range(4)]  # a_start, a_end, b_start, b_end
+        cig = (C.c_void_p * max(n, 1))()
+        f, t = C.c_float(0), C.c_float(0)
+        rc = L.pa_affine4_batch_align_local(self._h, match, _p(scores), *[_p(e) for e in ends], cig, C.byref(f), C.byref(t))
+        try:
+            self._check(rc, "pa_affine4_batch_align_local")
+            cigars = _c_strings(cig, n)
+        finally:
+            L.pa_free_cigars(cig, n)
+        self.last_forward_ms, self.last_trace_ms = float(f.value), float(t.value)
+        return [(int(scores[p]), cigars[p], *[int(e[p]) for e in ends]) for p in range(n)]
+
+    def sw_info(self) -> dict:
+        """Shape of the last align_sw(): chunks, device bytes of traceback codes of the largest one."""
+        vals = [C.c_double(0) for _ in range(2)]
+        load().pa_affine4_batch_local_info(self._h, *[C.byref(v) for v in vals])
+        return {k: int(v.value) for k, v in zip(("chunks", "bytes_max"), vals)}
 
 
 def align_affine4(pairs, cm: AffineCost, trace: bool = True, tiled: bool = False):

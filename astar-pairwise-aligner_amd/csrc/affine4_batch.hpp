@@ -3,6 +3,7 @@
 // launches of its own kernels; no kernel is launched here.  The chained route (set_chain) is split the same way: its state is the
 // batch's, its host side affine_chain_host.hpp's, and of affine4_chain_kernel<CKPT> (a template: each unit instantiates what it
 // launches) affine4_unit.hip runs the cost-only form in run() and affine4_tiled_unit.hip the checkpointing one in align_tiled().
+// affine4_local_unit.hip (run_local, align_local) reads the batch from here too and keeps one host-only slot in it, LocalInfo.
 #pragma once
 #include "affine4_common.hpp"
 #include "affine4_chain_kernel.hpp"
@@ -15,6 +16,9 @@
 namespace pa {
 namespace affine4 {
 struct DtState;  // affine4_dt_view.hpp
+struct LocalInfo {
+    double chunks = 0, bytes_max = 0;  // of the last align_local(): chunks, device bytes of traceback codes of the largest one
+};
 }
 }  // namespace pa
 
@@ -27,6 +31,7 @@ struct pa_affine4_batch : pa::affine_host::Batch<pa::affine4::Pair, pa::affine4:
     pa::DeviceBuf d_end;
     pa::affine_host::EndsState ends;
     pa::affine4::DtState* dt = nullptr;  // the diagonal-transition route's own state (affine4_dt_unit.hip)
+    pa::affine4::LocalInfo local;        // the shape of the last align_local() (affine4_local_unit.hip); host only
 };
 
 namespace pa {

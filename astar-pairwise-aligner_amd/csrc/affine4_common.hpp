@@ -2,7 +2,8 @@
 // affine4_tile_kernel.hpp (affine4_tiled_unit.hip) and affine4_chain_kernel.hpp (both).  Constants, the cost model, the pair / wave
 // records, and the pieces of the step as __forceinline__ functions: the cost-only row loop (rows_step), the row-0 step (row0_step), the
 // column-checkpoint store (store_col_ckpt), the cost pick (row_m_of) and the walk step (walk_step).  No kernel is defined here, so
-// both units may include it.
+// both units may include it.  affine4_local_kernel.hpp (local alignment, affine4_local_unit.hip) takes the records, Walk and walk_step
+// from here; its step, in signed scores with a floor at 0, is its own.
 //
 // A kernel calls a piece where it compiles to the instructions it had with the piece in its body, or where it timed within the spread
 // of the written-out form built twice, on one MI355X; elsewhere the piece stays in the kernel's body under a note with its numbers:
@@ -200,6 +201,17 @@ __device__ __forceinline__ void store_col_ckpt(PA_GLOBAL uint32_t* ck, uint32_t 
 }
 
 // ---- the walk (affine4_walk_kernel; affine4_tile_walk_kernel keeps its own copy of walk_step, see there) ----
+
+// One walk over a pair's whole code matrix (affine4_walk_kernel, and affine4_local_walk_kernel of affine4_local_kernel.hpp).
+struct Walk {
+    const uint8_t* a;
+    const uint8_t* b;
+    const uint8_t* codes;
+    uint8_t* ops;
+    uint32_t n, m, H, cap;
+    uint32_t out, pad_;  // out: Pair::out, the walk's index into ends[] (local: into the fill's results)
+};
+static_assert(sizeof(Walk) == 56, "Walk layout");
 
 // The op byte of a step inside layer k: distinct per layer, so that the host merges only the gaps of one layer.
 __device__ __forceinline__ uint8_t layer_op(int k) { return k == 0 ? 'i' : k == 1 ? 'd' : k == 2 ? 'j' : 'e'; }

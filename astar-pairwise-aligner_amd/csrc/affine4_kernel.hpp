@@ -225,16 +225,8 @@ __global__ __launch_bounds__(64 * kBlockWaves) void affine4_kernel(const Wave* _
 
 // One traceback (AffineNwFronts::trace): from (n, m, main) back to (0, 0, main), the first matching parent of every state as the FILL
 // codes recorded it (walk_step).  ops[] receives the steps from the end backwards: '=', 'X', 'I', 'D' (linear), and layer_op(k) for a
-// step inside layer k, so that the host can keep the gaps of different layers apart before it prints them as I / D.
-struct Walk {
-    const uint8_t* a;
-    const uint8_t* b;
-    const uint8_t* codes;
-    uint8_t* ops;
-    uint32_t n, m, H, cap;
-    uint32_t out, pad_;  // out: Pair::out, the walk's index into ends[]
-};
-static_assert(sizeof(Walk) == 56, "Walk layout");
+// step inside layer k, so that the host can keep the gaps of different layers apart before it prints them as I / D.  (The walk's record,
+// Walk, is in affine4_common.hpp: the local-alignment walk takes it too.)
 struct WalkOut {
     int32_t status;  // 0 ok, 1 bad code, 2 ops over capacity
     int32_t nops;

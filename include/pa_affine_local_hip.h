@@ -24,7 +24,8 @@
  *
  * Limits.  A pair with match * min(|a|, |b|) >= 2^30 is refused (PA_E_ARG naming the pair) before anything is launched.
  *
- * Out of scope: the double-affine batch (pa_affine4_hip.h), tiled and chained forms, diagonal transition, and a banded form.
+ * Out of scope: tiled and chained forms, diagonal transition, and a banded form.  The double-affine batch (pa_affine4_hip.h) has the
+ * same calls in a header of its own, pa_affine4_local_hip.h.
  */
 #ifndef PA_AFFINE_LOCAL_HIP_H
 #define PA_AFFINE_LOCAL_HIP_H

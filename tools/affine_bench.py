@@ -3,6 +3,7 @@ affine(4, 6, 2) and unit(), next to one CPU core running a plain scalar Gotoh (C
 
     python tools/affine_bench.py [--shapes reads,10k,100k,100k1] [--trace-100k] [--tile-cols C] [--reps R] [--chain] [--ends] [--dt] [--dt-ends]
                                  [--dt-seg] [--double] [--double-tiled] [--double-chain] [--double-ends] [--double-dt] [--double-dt-ends] [--double-dt-seg]
+                                 [--local] [--double-local]
                                  [--models affine,unit]
 
 Cells are |a| |b| per pair.  Traced times are the forward (code-writing) kernels plus the walks, summed over the budget's chunks; the
@@ -58,6 +59,9 @@ results compared in every round.  Every shape runs in a process of its own under
 says: 100 000 x 150 bp reads in 400 bp windows (cost-only and traced), 4096 x 10 kbp cost-only and --trace-pairs of them traced.  On one
 batch, run() against run_local() and align() against align_local(), alternating, each warmed once and then three times; the fastest
 repeat of each and their ratio.
+
+--double-local is --local's protocol and shapes on an Affine4Batch under double_affine(4, 6, 2, 24, 1): run() against run_sw(2) and align()
+against align_sw(2), alternating on one batch.
 
 --double-ends is --ends' protocol and mapping shapes on an Affine4Batch under double_affine(4, 6, 2, 24, 1) (Affine4Batch.set_free_ends):
 cost-only, traced and tiled (at --tile-cols, by default the library's 1024), global and ends-free alternating on one batch.
@@ -542,35 +546,37 @@ def ends_legs(title, pairs, tp, cm, mname, tile_cols, reps, Batch=AffineBatch):
           f" {ti['refill_cells'] / tcells:.3f} of the cells filled", flush=True)
 
 
-def local_legs(title, pairs, tp, cm, mname, match=2):
-    """Global and local (run_local / align_local at `match`), alternating on one batch each: run() against run_local() on `pairs` (if
-    any), align() against align_local() on a traced batch of `tp` (if any); each warmed once, then three times, the fastest of each."""
+def local_legs(title, pairs, tp, cm, mname, match=2, Batch=AffineBatch):
+    """Global and local (run_local / align_local at `match`; run_sw / align_sw of an Affine4Batch), alternating on one batch each: run()
+    against run_local() on `pairs` (if any), align() against align_local() on a traced batch of `tp` (if any); each warmed once, then
+    three times, the fastest of each."""
+    run_local, align_local, local_info = ("run_sw", "align_sw", "sw_info") if Batch is Affine4Batch else ("run_local", "align_local", "local_info")
     legs = []
     if pairs:
-        b = AffineBatch(pairs, cm)
+        b = Batch(pairs, cm)
         g, l = [], []
         for rep in range(4):  # the first round warms both routes
             b.run()
             k = b.last_kernel_ms
-            b.run_local(match)
+            getattr(b, run_local)(match)
             if rep:
                 g.append(k)
                 l.append(b.last_kernel_ms)
         b.close()
         legs.append(("cost", pairs, g, l, ""))
     if tp:
-        tb = AffineBatch(tp, cm, trace=True)
+        tb = Batch(tp, cm, trace=True)
         g, l, gf, lf = [], [], [], []  # totals, and the forward (fill) part of each
         for rep in range(4):
             tb.align()
             k, kf = tb.last_forward_ms + tb.last_trace_ms, tb.last_forward_ms
-            res = tb.align_local(match)
+            res = getattr(tb, align_local)(match)
             if rep:
                 g.append(k)
                 gf.append(kf)
                 l.append(tb.last_forward_ms + tb.last_trace_ms)
                 lf.append(tb.last_forward_ms)
-        li = tb.local_info()
+        li = getattr(tb, local_info)()
         tb.close()
         cover = sum(r[5] - r[4] for r in res) / max(sum(len(y) for _, y in tp), 1)
         legs.append(("traced", tp, g, l, f"; fills {min(gf):.2f} | {min(lf):.2f} ms; {li['chunks']} chunks, {li['bytes_max'] / 2**20:.0f} MiB,"
@@ -622,6 +628,7 @@ def main():
     ap.add_argument("--chain", action="store_true", help="measure the chained route against the unchained one instead (see above)")
     ap.add_argument("--ends", action="store_true", help="measure the ends-free mode against the global one instead (see above)")
     ap.add_argument("--local", action="store_true", help="measure local alignment (run_local / align_local) against the global calls instead (see above)")
+    ap.add_argument("--double-local", action="store_true", help="measure Affine4Batch.run_sw / align_sw against its global calls instead (see above)")
     ap.add_argument("--dt", action="store_true", help="measure the diagonal-transition route against run() instead (see above)")
     ap.add_argument("--dt-ends", action="store_true", help="measure the ends-free diagonal-transition route against the ends-free run() instead (see above)")
     ap.add_argument("--dt-seg", action="store_true", help="measure the segmented DT traceback against align_dt_ends instead (see above)")
@@ -711,6 +718,13 @@ def main():
             title, pairs = ends_shape(sname, rng)
             ends_legs(title, pairs, pairs if sname == "map150" else pairs[: args.trace_pairs], AffineCost.double_affine(4, 6, 2, 24, 1), "double_affine",
                       args.tile_cols, args.reps, Affine4Batch)
+        return
+    if args.double_local:
+        cm4 = AffineCost.double_affine(4, 6, 2, 24, 1)
+        title, pairs = ends_shape("map150", rng)
+        local_legs(title, pairs, pairs, cm4, "double_affine", Batch=Affine4Batch)
+        title, pairs = shape("10k", rng)
+        local_legs(title, pairs, pairs[: args.trace_pairs], cm4, "double_affine", Batch=Affine4Batch)
         return
     if args.local:
         title, pairs = ends_shape("map150", rng)
